@@ -1,6 +1,11 @@
 """Benchmark: particle-updates/s of the VE time step (Sedov lattice) on N MI355X, one process per GPU.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--side S] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--side S] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run sets up, runs W warm-up and K timed steps, writes the last step's fields if --dump-outputs is given and
+prints the result line (value, ms_per_step, the timed steps' kernel and stage times).  --full adds what takes work of
+its own after the timed steps: the "roofline" entry (with self-gravity one more step that counts interactions) and the
+reference CPU baseline ("cpu_baseline").
 
 A step is one full HydroVeProp step (ve_hydro.hpp:132-218): sync (keys, sort, reorder, tree), neighbor search with
 h iteration, XMass, VeDefGradh, EOS, IAD+divv/curlv, AV switches, momentum/energy, [self-gravity], time-step,
@@ -11,7 +16,7 @@ N (strong scaling: N=1 holds all 64M particles on one MI355X, N=8 holds 8M + hal
 BASELINE config 2.
 With skin lists (one rank, the default) the timed window starts with a forced full sync + skin build, so the headline
 carries the builds' cost (1 per K steps; the steady state has 1 per max_reuse = 24, reported as amortized_*).
-Rank 0 prints ONE JSON line.  Its "roofline" is the dominant kernel's (largest share of the step): HBM bytes per
+Rank 0 prints ONE JSON line.  Its "roofline" (--full) is the dominant kernel's (largest share of the step): HBM bytes per
 launch from the committed rocprofv3 PMC passes of the same workload (profiles/pmc_<init>_n<side>.json) over the kernel's
 average launch time measured here with HIP events on its stream.
 """
@@ -199,7 +204,13 @@ def parse():
                     help="total lattice side (default: the metric's Sedov -n 400 at every N; noh/evrard 300)")
     ap.add_argument("--bucket", type=int, default=64)
     ap.add_argument("--exact", action="store_true", help="use the no-FMA (bit-reproducible) kernels")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also the roofline entry (with self-gravity: one more, counting, step) "
+                         "and the reference CPU baseline; a plain run sets up, warms up, times and prints")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's fields as DIR/<name>.npy, rows ordered by "
+                         "DIR/id.npy (above 2^18 particles a fixed, seeded sample of them); one GPU only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--no-build-step", action="store_true",
                     help="do not force a full sync + skin build at the start of the timed window (profiling runs of "
                          "filter-served steps only: the PMC summary normalises its counters by steps + warmup)")
@@ -282,9 +293,130 @@ def cpu_baseline(seconds, side):
                       f"OMP_PLACES={os.environ.get('OMP_PLACES', 'unset')}"}
 
 
+def full_roofline(args, sim, side, n_local, ms_step, skin, kern_ms, workload, ng, union_pp):
+    """--full: the "roofline" entry of the result line, from the timed steps' kernel times, the committed PMC
+    summaries of the same workload and, with self-gravity, the interaction counts of one more step"""
+    std_prop = args.prop == "std"
+    inter = None
+    if args.init == "evrard":  # self-gravity on (g = 1); the same decision on every rank: the extra step is collective
+        # the interaction counts (BhStats) of one more step after the timed region: counting is a separate, slower
+        # instantiation of the traversal, so the timed steps run without it
+        sim.set_gravity_counting(True)
+        sim.step()
+        inter = sim.gravity_interactions()
+        sim.set_gravity_counting(False)
+    pmc_key = f"{args.init}_n{side}" + ("_avclean" if args.av_clean else "") + ("_std" if std_prop else "")
+    pmc = load_pmc(pmc_key, n_local, workload) if not std_prop else None
+    per_kernel = {}
+    for k, ms in kern_ms.items():
+        if ms > 0.01 and k in EDGE_MODEL:
+            # every timed step served by the skin filter: the search slot's counters are the filter's alone (the
+            # PMC run's first step is a full build, whose kernels would be averaged in)
+            ex = SEARCH_BUILD_KERNELS if (k == "findNeighbors" and skin.get("builds", 1) == 0 and
+                                          skin.get("plain_steps", 1) == 0 and skin.get("reuse_steps", 0) > 0) else ()
+            per_kernel[k] = kernel_roofline(k, ms, n_local, ng, union_pp, pmc, ex)
+        elif ms > 0.01 and k == "gravity" and inter is not None:  # (without self-gravity the slot times no kernel)
+            per_kernel[k] = gravity_roofline(ms, n_local, inter, pmc)
+    dominant = max(per_kernel, key=lambda k: per_kernel[k]["avg_launch_ms"]) if per_kernel else "momentumEnergy"
+    dom = per_kernel.get(dominant, {})
+    grav_dom = dominant == "gravity"
+    roofline = {"bound": "valu" if grav_dom else "hbm", "kernel": dominant,
+                "achieved": dom.get("tflops_reference_model") if grav_dom else dom.get("achieved"),
+                "peak": FP32_PEAK_TFLOPS if grav_dom else HBM_PEAK_GBS,
+                "unit": "TFLOP/s" if grav_dom else "GB/s",
+                "frac": dom.get("flop_frac") if grav_dom else dom.get("frac"), "traffic": dom.get("traffic"),
+                "avg_launch_ms": dom.get("avg_launch_ms"),
+                "share_of_step": dom.get("avg_launch_ms", 0.0) / ms_step,
+                "binding": ("FP32 VALU / latency: flop roofline from the per-target P2P/M2P counts (see "
+                            "tflops (this kernel's own count), valu_issue_frac, hbm_frac)" if grav_dom else
+                            "valu-issue/latency (HBM frac < 0.5; see valu_issue_frac, lds_conflict_frac)"
+                            if (dom.get("frac") or 0) < 0.5 else "hbm"),
+                "traffic_source": os.path.relpath(pmc_file(pmc_key), ROOT) if pmc else None,
+                "definition": "achieved = rocprofv3 PMC HBM bytes per launch (FETCH_SIZE x2 + WRITE_SIZE, same "
+                              "workload; FETCH_SIZE x2 equals the bytes read for coalesced 4/8/16-B streams and "
+                              "leaf-run record gathers, profiles/r3_fetch_calib.json; for random 16-B/4-B gathers "
+                              "the calibration only shows FETCH_SIZE x2 at 3.3x/8.2x the useful bytes, i.e. whole "
+                              "lines, so the x2 reading is inferred there, not measured) / avg launch time measured "
+                              "live with HIP events; frac = achieved / 8 TB/s; "
+                              "valu_issue_frac = SQ_INSTS_VALU / (time x 1.23e12 wave64 ops/s: 2 cycles per "
+                              "instruction per SIMD-32 at 2.4 GHz, the chip's rate; one wave alone issues at most "
+                              "half of it, profiles/r4_issue_calib.jsonl); valu_frac = SURVEY 8(d) flop "
+                              "per pair x pairs / time / 157.3 TF (FP32 peak at 2.4 GHz); gravity: achieved and "
+                              "flop_frac = the reference's accounting (traversal.cuh:632: 20 per P2P + 16 per M2P) / "
+                              "time / 157.3 TF, flop_frac_impl_model = this kernel's (23 P2P + 54 M2P); "
+                              "lds_conflict_frac = "
+                              "SQ_LDS_BANK_CONFLICT / 256 CUs / (time x 2.4 GHz); effective_gbs = SURVEY 8(d) edge "
+                              "model (neighbor records served from LDS/L2, not a roofline)",
+                **{k: dom[k] for k in ("valu_issue_frac", "lds_conflict_frac", "effective_gbs",
+                                       "algorithmic_bytes_per_launch", "algorithmic_frac", "hbm_frac",
+                                       "tflops", "flop_frac_impl_model", "p2p_per_target", "m2p_per_target",
+                                       "valu_lane_ops_per_pair") if k in dom},
+                "per_kernel": per_kernel}
+    st_bytes = step_traffic(pmc, skin.get("builds", 1) == 0 and skin.get("plain_steps", 1) == 0 and
+                            skin.get("reuse_steps", 0) > 0)
+    if st_bytes:
+        roofline["step_traffic"] = st_bytes
+        roofline["step_hbm_gbs"] = st_bytes / (ms_step * 1e-3) / 1e9
+        roofline["step_hbm_frac"] = roofline["step_hbm_gbs"] / HBM_PEAK_GBS
+    cal = calibration()
+    if cal:
+        roofline["counter_calibration"] = {"source": os.path.relpath(CALIB_FILE, ROOT),
+                                           "known_bytes_per_counter_byte": cal}
+    mom = per_kernel.get("momentumEnergy")
+    if mom and not std_prop:
+        roofline["momentum_valu"] = {"flop_per_pair": MOM_FLOP_PER_PAIR,
+                                     "achieved_tflops": n_local * ng * MOM_FLOP_PER_PAIR /
+                                     (mom["avg_launch_ms"] * 1e-3) / 1e12, "peak_tflops": FP32_PEAK_TFLOPS}
+    if std_prop:
+        mom_ms = kern_ms.get("momentumEnergy", float("nan"))
+        roofline["effective_gbs_momentumStd"] = n_local * (MOM_STD_OWN_BYTES + ng * MOM_STD_EDGE_BYTES) / \
+            (mom_ms * 1e-3) / 1e9
+    return roofline
+
+
+# --dump-outputs: the fields a caller of sx_sim_step reads back (the propagated state and the step's derived
+# quantities; rho and p exist with the std propagator only)
+DUMP_FIELDS = ["x", "y", "z", "vx", "vy", "vz", "h", "temp", "x_m1", "y_m1", "z_m1", "du_m1", "alpha", "xm", "kx",
+               "prho", "c", "divv", "du", "ax", "ay", "az", "nc", "rho", "p"]
+DUMP_SAMPLE = 1 << 18  # particles written at most: 26 arrays of at most 8 B each stay under 64 MB (54.5 MB)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, sim, n_total):
+    """<path>/<field>.npy of the last step's fields, float32 or float64 as on the device (nc: float32), in the order
+    of the particle ids in <path>/id.npy; more than DUMP_SAMPLE particles: a fixed, seeded sample of the ids 0 ..
+    n_total - 1 that every initial condition here assigns.  <path>/scalars.npy: minDt, minDt_m1, ttot, minDtCourant,
+    minDtRho, egrav (float64).  The particle order on the device is the sort's, so the rows are matched by id."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    ids = sim.get(["id"])["id"]
+    if n_total > DUMP_SAMPLE:
+        want = np.sort(np.random.default_rng(DUMP_SEED).choice(n_total, DUMP_SAMPLE, replace=False)).astype(np.uint64)
+        rows = np.flatnonzero(np.isin(ids, want))
+    else:
+        rows = np.arange(ids.size)
+    rows = rows[np.argsort(ids[rows], kind="stable")]
+    if rows.size != min(n_total, DUMP_SAMPLE) or np.any(np.diff(ids[rows].astype(np.int64)) <= 0):
+        raise SystemExit("--dump-outputs: the particle ids are not the distinct 0 .. n-1 the sample is drawn from")
+    np.save(os.path.join(path, "id.npy"), ids[rows].astype(np.float64))
+    f, _ = sim.fields()
+    for name in DUMP_FIELDS:
+        if not getattr(f, name):  # not allocated by this propagator
+            continue
+        a = sim.get([name])[name][rows]
+        np.save(os.path.join(path, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+    sc = sim.scalars()
+    np.save(os.path.join(path, "scalars.npy"), np.array(list(sc.values()), dtype=np.float64))
+
+
 def main():
     args = parse()
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--dump-outputs writes one process's particles: run it on one GPU")
+    if args.dump_outputs and args.seam:
+        raise SystemExit("--dump-outputs writes the fields of the sx_sim path: run it without --seam")
+    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.full and not args.no_cpu_baseline:
         # the reference CPU baseline's OpenMP threads pinned to cores, close together (SURVEY 8(d)); set before any
         # OpenMP runtime is loaded (the reference library is loaded only by cpu_baseline)
         os.environ.setdefault("OMP_PROC_BIND", "close")
@@ -433,14 +565,8 @@ def main():
                                   f"({skin['builds']} build(s) in {args.steps} steps); amortized: one build every {R} "
                                   "steps (max_reuse), the other steps filter-served; both from the same window's "
                                   "per-step host times")
-    inter = None
-    if args.init == "evrard":  # self-gravity on (g = 1); the same decision on every rank: the extra step is collective
-        # the interaction counts (BhStats) of one more step after the timed region: counting is a separate, slower
-        # instantiation of the traversal, so the timed steps run without it
-        sim.set_gravity_counting(True)
-        sim.step()
-        inter = sim.gravity_interactions()
-        sim.set_gravity_counting(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sim, n_total)
     ng = stats["sumNeighbors"] / max(1, n_local)
     union_pp = stats["sumUnion"] / max(1, n_local)
     std_prop = args.prop == "std"
@@ -449,72 +575,9 @@ def main():
                 f"{'std (HydroProp)' if std_prop else 'VE'} propagator"
                 f"{' + self-gravity' if args.init == 'evrard' else ''}"
                 f"{' + AV cleaning' if args.av_clean else ''}, {args.steps} steps")
-    pmc_key = f"{args.init}_n{side}" + ("_avclean" if args.av_clean else "") + ("_std" if std_prop else "")
-    pmc = load_pmc(pmc_key, n_local, workload) if not std_prop else None
-    per_kernel = {}
-    for k, ms in kern_ms.items():
-        if ms > 0.01 and k in EDGE_MODEL:
-            # every timed step served by the skin filter: the search slot's counters are the filter's alone (the
-            # PMC run's first step is a full build, whose kernels would be averaged in)
-            ex = SEARCH_BUILD_KERNELS if (k == "findNeighbors" and skin.get("builds", 1) == 0 and
-                                          skin.get("plain_steps", 1) == 0 and skin.get("reuse_steps", 0) > 0) else ()
-            per_kernel[k] = kernel_roofline(k, ms, n_local, ng, union_pp, pmc, ex)
-        elif ms > 0.01 and k == "gravity" and inter is not None:  # (without self-gravity the slot times no kernel)
-            per_kernel[k] = gravity_roofline(ms, n_local, inter, pmc)
-    dominant = max(per_kernel, key=lambda k: per_kernel[k]["avg_launch_ms"]) if per_kernel else "momentumEnergy"
-    dom = per_kernel.get(dominant, {})
-    grav_dom = dominant == "gravity"
-    roofline = {"bound": "valu" if grav_dom else "hbm", "kernel": dominant,
-                "achieved": dom.get("tflops_reference_model") if grav_dom else dom.get("achieved"),
-                "peak": FP32_PEAK_TFLOPS if grav_dom else HBM_PEAK_GBS,
-                "unit": "TFLOP/s" if grav_dom else "GB/s",
-                "frac": dom.get("flop_frac") if grav_dom else dom.get("frac"), "traffic": dom.get("traffic"),
-                "avg_launch_ms": dom.get("avg_launch_ms"),
-                "share_of_step": dom.get("avg_launch_ms", 0.0) / ms_step,
-                "binding": ("FP32 VALU / latency: flop roofline from the per-target P2P/M2P counts (see "
-                            "tflops (this kernel's own count), valu_issue_frac, hbm_frac)" if grav_dom else
-                            "valu-issue/latency (HBM frac < 0.5; see valu_issue_frac, lds_conflict_frac)"
-                            if (dom.get("frac") or 0) < 0.5 else "hbm"),
-                "traffic_source": os.path.relpath(pmc_file(pmc_key), ROOT) if pmc else None,
-                "definition": "achieved = rocprofv3 PMC HBM bytes per launch (FETCH_SIZE x2 + WRITE_SIZE, same "
-                              "workload; FETCH_SIZE x2 equals the bytes read for coalesced 4/8/16-B streams and "
-                              "leaf-run record gathers, profiles/r3_fetch_calib.json; for random 16-B/4-B gathers "
-                              "the calibration only shows FETCH_SIZE x2 at 3.3x/8.2x the useful bytes, i.e. whole "
-                              "lines, so the x2 reading is inferred there, not measured) / avg launch time measured "
-                              "live with HIP events; frac = achieved / 8 TB/s; "
-                              "valu_issue_frac = SQ_INSTS_VALU / (time x 1.23e12 wave64 ops/s: 2 cycles per "
-                              "instruction per SIMD-32 at 2.4 GHz, the chip's rate; one wave alone issues at most "
-                              "half of it, profiles/r4_issue_calib.jsonl); valu_frac = SURVEY 8(d) flop "
-                              "per pair x pairs / time / 157.3 TF (FP32 peak at 2.4 GHz); gravity: achieved and "
-                              "flop_frac = the reference's accounting (traversal.cuh:632: 20 per P2P + 16 per M2P) / "
-                              "time / 157.3 TF, flop_frac_impl_model = this kernel's (23 P2P + 54 M2P); "
-                              "lds_conflict_frac = "
-                              "SQ_LDS_BANK_CONFLICT / 256 CUs / (time x 2.4 GHz); effective_gbs = SURVEY 8(d) edge "
-                              "model (neighbor records served from LDS/L2, not a roofline)",
-                **{k: dom[k] for k in ("valu_issue_frac", "lds_conflict_frac", "effective_gbs",
-                                       "algorithmic_bytes_per_launch", "algorithmic_frac", "hbm_frac",
-                                       "tflops", "flop_frac_impl_model", "p2p_per_target", "m2p_per_target",
-                                       "valu_lane_ops_per_pair") if k in dom},
-                "per_kernel": per_kernel}
-    st_bytes = step_traffic(pmc, skin.get("builds", 1) == 0 and skin.get("plain_steps", 1) == 0 and
-                            skin.get("reuse_steps", 0) > 0)
-    if st_bytes:
-        roofline["step_traffic"] = st_bytes
-        roofline["step_hbm_gbs"] = st_bytes / (ms_step * 1e-3) / 1e9
-        roofline["step_hbm_frac"] = roofline["step_hbm_gbs"] / HBM_PEAK_GBS
-    cal = calibration()
-    if cal:
-        roofline["counter_calibration"] = {"source": os.path.relpath(CALIB_FILE, ROOT),
-                                           "known_bytes_per_counter_byte": cal}
-    mom = per_kernel.get("momentumEnergy")
-    if mom and not std_prop:
-        roofline["momentum_valu"] = {"flop_per_pair": MOM_FLOP_PER_PAIR,
-                                     "achieved_tflops": n_local * ng * MOM_FLOP_PER_PAIR /
-                                     (mom["avg_launch_ms"] * 1e-3) / 1e12, "peak_tflops": FP32_PEAK_TFLOPS}
-    if std_prop:
-        mom_ms = kern_ms.get("momentumEnergy", float("nan"))
-        roofline["effective_gbs_momentumStd"] = n_local * (MOM_STD_OWN_BYTES + ng * MOM_STD_EDGE_BYTES) / \
-            (mom_ms * 1e-3) / 1e9
+    # --full: the roofline figures (on every rank: with self-gravity they take one more, collective, step)
+    roofline = full_roofline(args, sim, side, n_local, ms_step, skin, kern_ms, workload, ng, union_pp) \
+        if args.full else None
     sc = sim.scalars()
     out = {
         "metric": "particle-updates/sec (whole node), Sedov -n 400, 1/2/4/8 MI355X + HBM roofline %",
@@ -544,7 +607,7 @@ def main():
                                              "2h(1+s) (sx_skin.hpp; several ranks: halos of the build refreshed, "
                                              "displacement grid all-reduced); same neighbor sets, nc, h",
                                      **skin}},
-        "roofline": roofline,
+        **({"roofline": roofline} if args.full else {}),
         "kernels_ms": {(STD_KERNEL_NAMES.get(k) if std_prop else k): v for k, v in kern_ms.items()
                        if not std_prop or k in STD_KERNEL_NAMES},
         "stages_ms": {k: v / args.steps for k, v in stage_sum.items()},
@@ -556,7 +619,7 @@ def main():
         "union_per_particle": union_pp,
         "minDt": sc["minDt"],
     }
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, args.cpu_side)
     sim.close()
     if comm is not None:

@@ -16,7 +16,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smok
 cat $OUT/smoke.log
 if [ "${BENCH:-1}" = "1" ]; then
   echo "== bench"; date
-  timeout -k 10 600 python bench.py --steps $STEPS --warmup 2 ${BENCH_ARGS:-} > $OUT/bench.log 2>&1 || { rc=$?; tail -20 $OUT/bench.log; exit $rc; }
+  timeout -k 10 600 python bench.py --full --steps $STEPS --warmup 2 ${BENCH_ARGS:-} > $OUT/bench.log 2>&1 || { rc=$?; tail -20 $OUT/bench.log; exit $rc; }
   tail -1 $OUT/bench.log
 fi
 if [ "${PROF:-1}" = "1" ]; then

@@ -17,5 +17,6 @@ if [ "${PMC:-1}" = "1" ]; then
   mkdir -p profiles && cp gpurun_out/pmc_$KEY/summary.json profiles/pmc_$KEY.json
 fi
 echo "== bench $KEY"; date
+BENCH_EXTRA="--full ${BENCH_EXTRA:-}"  # the roofline entry is the part of the line that reads the counters
 timeout -k 10 500 python bench.py $A ${BENCH_EXTRA:-} > gpurun_out/bench_$KEY.log 2>&1 || { tail -5 gpurun_out/bench_$KEY.log; exit 1; }
 tail -1 gpurun_out/bench_$KEY.log

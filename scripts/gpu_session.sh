@@ -18,7 +18,7 @@ if [ "${TESTS:-1}" = "1" ]; then
 fi
 if [ "${BENCH:-1}" = "1" ]; then
   echo "== bench"; date
-  timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > $OUT/bench.log 2>&1 || { rc=$?; tail -20 $OUT/bench.log; exit $rc; }
+  timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > $OUT/bench.log 2>&1 || { rc=$?; tail -20 $OUT/bench.log; exit $rc; }
   tail -1 $OUT/bench.log
 fi
 if [ "${PROF:-1}" = "1" ]; then

@@ -22,6 +22,7 @@ buildOctreeGpu, halo gathers ...) and ryoanji's MultipoleHolder, which are outsi
 import os
 import re
 import shutil
+import stat
 import subprocess
 
 import pytest
@@ -68,6 +69,10 @@ def prepare(dst):
     skip = shutil.ignore_patterns("test", "tests", "*.md", "docs", ".git*")
     for d in ("domain", "sph", "main", "ryoanji", "physics"):
         shutil.copytree(os.path.join(REF, d), os.path.join(dst, d), ignore=skip)
+    # the copy keeps the modes of a read-only reference tree: the patches below and hipify -inplace write into it
+    for r, ds, fs in os.walk(dst):
+        for p in [r] + [os.path.join(r, f) for f in fs]:
+            os.chmod(p, os.stat(p).st_mode | stat.S_IWUSR)
     pd = os.path.join(dst, "sph", "include", "sph", "particles_data.hpp")
     lines = open(pd).read().split("\n")
     assert lines[269].strip() == "#endif", "F1 moved"
