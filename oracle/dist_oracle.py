@@ -447,7 +447,94 @@ def _mi_dist2(a, b, box):
     return d2
 
 
-def skin_premise(d, full, glob_pos0, h_of, s, disps, global_grid=True):
+def sfc_owners(ora, st, box, P):
+    """owner rank of every particle of the global state st in the decomposition of the first sync, computed as
+    DistOracle._exchange_particles does: SFC keys, the histogram of 2^18 key bins, the product's splitters"""
+    import sphexa_amd as sx
+
+    keys = ora.sfc_keys(st, box).copy()
+    bins = (keys >> np.uint64(63 - HIST_BITS)).astype(np.int64)
+    split = sx.domain_splitters(np.bincount(bins, minlength=1 << HIST_BITS).astype(np.uint32), HIST_BITS, P)
+    return np.clip(np.searchsorted(split, keys, side="right") - 1, 0, P - 1)
+
+
+def converging_patch(pos, owner, box, spacing, ball, reach, tilt=(0.0, 0.0, 0.0)):
+    """The patch of the converging-patch scenario on a lattice (one particle per cell of `spacing`), from the data.
+    The faces between a cell owned by a rank M and a neighbouring cell owned by a rank R are their common boundary.
+    R's request boxes are bounding boxes of its particles grown by the search radius (`reach`, in spacings): where R's
+    extent along the face's axis plus twice the reach leaves part of the (periodic) box free and the face lies at the
+    end of that extent, the boxes end one reach behind the face and particles of M beyond are no halos of R --
+    elsewhere the boxes reach far into M and every particle that could come near is a halo anyway.  The pair (resting
+    R, moving M) with the most such faces is taken (the lowest ranks among equals), the patch is centred on the one of
+    those faces nearest to their centroid and holds the particles of M within `ball` spacings of it; the direction is
+    the one from their centroid to that of the particles of R in the same ball (minimum image), plus `tilt`.
+    Returns (mask of the patch, unit direction, centre, (R, M))."""
+    lo = np.array([box.lim[0], box.lim[2], box.lim[4]])
+    L = np.array([box.lim[1] - box.lim[0], box.lim[3] - box.lim[2], box.lim[5] - box.lim[4]])
+    n = np.rint(L / spacing).astype(np.int64)
+    cell = np.clip(np.floor((pos - lo) / spacing).astype(np.int64), 0, n - 1)
+    own = np.full(tuple(n), -1, np.int64)
+    own[cell[:, 0], cell[:, 1], cell[:, 2]] = owner
+    P = int(owner.max()) + 1
+    ext = [(c.min(axis=0), c.max(axis=0)) for c in (np.argwhere(own == r) for r in range(P))]
+    best = None
+    for resting in range(P):
+        for moving in range(P):
+            if moving == resting:
+                continue
+            faces = []
+            for k in range(3):
+                rmin, rmax = int(ext[resting][0][k]), int(ext[resting][1][k])
+                if box.bnd[k] == 1 and (rmax - rmin) + 2.0 * reach >= n[k] - 1:
+                    continue  # R's boxes cover the whole axis
+                for sgn in (-1, 1):
+                    if box.bnd[k] == 1:
+                        nb = np.roll(own, -sgn, axis=k)  # nb[i] = own[i + sgn]
+                    else:
+                        nb = np.full_like(own, -1)
+                        src, dst = [slice(None)] * 3, [slice(None)] * 3
+                        src[k], dst[k] = (slice(1, None), slice(0, -1)) if sgn > 0 else (slice(0, -1), slice(1, None))
+                        nb[tuple(dst)] = own[tuple(src)]
+                    idx = np.argwhere((own == moving) & (nb == resting))
+                    rc = np.mod(idx[:, k] + sgn, n[k])  # the resting cell behind the face
+                    idx = idx[rc == (rmin if sgn > 0 else rmax)].astype(np.float64)
+                    mid = lo + (idx + 0.5) * spacing
+                    mid[:, k] += 0.5 * sgn * spacing
+                    faces.append(mid)
+            faces = np.concatenate(faces) if faces else np.zeros((0, 3))
+            if best is None or faces.shape[0] > best[0].shape[0]:
+                best = (faces, resting, moving)
+    faces, resting, moving = best
+    assert faces.shape[0] > 0, "no two ranks share a boundary beyond which the peer's particles are no halos"
+    centre = faces[np.argmin(np.sum((faces - faces.mean(axis=0)) ** 2, axis=1))]
+    rel = np.stack([_fold(pos[:, k] - centre[k], box, k) for k in range(3)], axis=1)
+    inside = np.sum(rel * rel, axis=1) <= (ball * spacing) ** 2
+    patch = inside & (owner == moving)
+    rest = inside & (owner == resting)
+    assert patch.any() and rest.any()
+    v = rel[rest].mean(axis=0) - rel[patch].mean(axis=0)
+    v = v / np.linalg.norm(v) + np.asarray(tilt, np.float64)
+    return patch, v / np.linalg.norm(v), centre, (resting, moving)
+
+
+COVER_RULES = ("build-box", "build-box+drift")
+COVER_RADII = ("rebuilt skin 2h(1+s)", "exact search 2h")
+
+
+def _cover_inside(d, centre, Rt, sel, drift):
+    """coverListKernel (sx_sim.cpp), per target of one re-searched cluster: the sphere of radius Rt, grown by the
+    kernel's 1 + 1e-6, the key-quantisation margin and `drift`, around `centre` inside the request box of the target's
+    chunk of 2048 locals as the build sent it to the peers (d.my_boxes; minimum image)"""
+    qm = quant_margin(d.box)
+    b = d.my_boxes[sel // CHUNK]
+    r = Rt * (1.0 + 1e-6) + qm + drift
+    ok = np.ones(len(sel), bool)
+    for k in range(3):
+        ok &= np.abs(_fold(centre[:, k] - b[:, k], d.box, k)) + r <= b[:, 3 + k]
+    return ok
+
+
+def skin_premise(d, full, glob_pos0, h_of, s, disps, global_grid=True, cover=False):
     """Restatement of the multi-rank skin argument on this rank (test infrastructure).
 
     Build: the halos of `full` were requested with the skin radius (d._discover(..., HALO_MARGIN * (1 + s))); every
@@ -460,7 +547,22 @@ def skin_premise(d, full, glob_pos0, h_of, s, disps, global_grid=True):
     2 h_a + d_a + A_C <= R_a (1 - 2^-16) (d_a = sum_t |d_a(t) - u(t)|, A_C = sum_t max over the cells around the
     cluster's targets grown by max R of the largest |d - u|).  Check 2: every target of every cluster the bound admits
     has all its current neighbours (global truth within 2 h_a, minimum image) in S_a.
-    Returns (skin_mismatch, admitted clusters per step, violations per step)."""
+    Returns (skin_mismatch, admitted clusters per step, violations per step).
+
+    cover=True adds the clusters the bound does NOT admit: on the GPU a reuse step searches them again (a skin rebuilt
+    from the current positions, radius 2 h_a (1 + s), or the exact search, radius 2 h_a) over this rank's locals and
+    the BUILD's halos at their current positions, and coverListKernel decides whether that search can stand or every
+    rank redoes the step from a full sync.  Per step, rule of COVER_RULES and radius of COVER_RADII: the re-searched
+    clusters the rule accepts, and among their targets those whose candidate set (locals + build halos within the
+    radius now) differs from the truth over every particle of every rank.  "build-box": the current sphere inside the
+    build's request box.  "build-box+drift": the kernel's corrected rule.  A particle that was outside the box at
+    the build, hence no halo, has moved by sum_t d_p(t) since; for any vectors w(t) it was, at the build, within
+    R + sum_t max_q |d_q(t) - w(t)| of the target's current position minus sum_t w(t), so it cannot be inside the
+    target's sphere now if that larger sphere fits the box.  The maxima over every particle q of every rank come from
+    the component ranges of the all-reduced grid.  w = 0: the current position, R + D, D = sum_t max |d_q(t)|; w = the
+    target's own moves: its position at the build, R + sum_t max |d_q(t) - d_a(t)|.  A target is covered when either
+    sphere fits; a cluster is accepted when every target is.
+    Then a fourth value is returned: {rule: (accepted[step, radius], wrong[step, radius])}."""
     import torch
 
     dist = _dist()
@@ -486,6 +588,11 @@ def skin_premise(d, full, glob_pos0, h_of, s, disps, global_grid=True):
     acc = np.zeros(ncl)
     G = SKIN_GRID_N
     admitted, violations = [], []
+    halo_or_local = np.zeros(n_glob, bool)
+    halo_or_local[ids_full] = True
+    drift = 0.0  # "build-box+drift": D, and per local target its drift relative to every particle of the grid
+    relg = np.zeros(len(loc))
+    cov = {rule: ([], []) for rule in COVER_RULES}
     for disp in disps:
         pos = pos + disp
         for k in range(3):
@@ -505,6 +612,19 @@ def skin_premise(d, full, glob_pos0, h_of, s, disps, global_grid=True):
             dist.all_reduce(tl, op=dist.ReduceOp.MIN)
             dist.all_reduce(th, op=dist.ReduceOp.MAX)
             lo_, hi_ = tl.numpy(), th.numpy()
+        if cover:
+            # the largest displacement in the grid of every rank's particles (per cell the length of the largest
+            # components, as skinGridMaxKernel takes it: an upper bound of every particle's move)
+            tl, th = torch.from_numpy(lo_.copy()), torch.from_numpy(hi_.copy())
+            dist.all_reduce(tl, op=dist.ReduceOp.MIN)
+            dist.all_reduce(th, op=dist.ReduceOp.MAX)
+            full_cells = np.isfinite(tl.numpy()[0])
+            e = np.maximum(np.abs(tl.numpy()), np.abs(th.numpy()))[:, full_cells]
+            drift += float(np.sqrt(np.sum(e * e, axis=0)).max())
+            glo, ghi = tl.numpy()[:, full_cells].min(axis=1), th.numpy()[:, full_cells].max(axis=1)
+            e = np.maximum(np.abs(glo[None, :] - disp[loc]), np.abs(ghi[None, :] - disp[loc]))
+            relg += np.sqrt(np.sum(e * e, axis=1))
+            cstep = {rule: (np.zeros(2, np.int64), np.zeros(2, np.int64)) for rule in COVER_RULES}
         n_ok, n_bad = 0, 0
         for c in range(ncl):
             sel = np.arange(c * DistOracle.CLUSTER, min(len(loc), (c + 1) * DistOracle.CLUSTER))
@@ -533,6 +653,20 @@ def skin_premise(d, full, glob_pos0, h_of, s, disps, global_grid=True):
                     g = max(g, float(np.sqrt(e[0] ** 2 + e[1] ** 2 + e[2] ** 2)))
             acc[c] += g
             if not np.all(2.0 * h_of[ids] + rel[sel] + acc[c] <= R[sel] * (1.0 - 2.0 ** -16)):
+                for kind, Rt in enumerate((R[sel], 2.0 * h_of[ids])) if cover else ():
+                    ok = {"build-box": bool(np.all(_cover_inside(d, pos[ids], Rt, sel, 0.0))),
+                          "build-box+drift": bool(np.all(_cover_inside(d, pos[ids], Rt, sel, drift) |
+                                                         _cover_inside(d, glob_pos0[ids], Rt, sel, relg[sel])))}
+                    if not any(ok.values()):
+                        continue
+                    wrong = 0
+                    for q_, a in enumerate(ids):
+                        near = _mi_dist2(pos, pos[a][None, :], box) < Rt[q_] ** 2
+                        wrong += bool(np.any(near & ~halo_or_local))  # a particle the re-search cannot see
+                    for rule in COVER_RULES:
+                        if ok[rule]:
+                            cstep[rule][0][kind] += 1
+                            cstep[rule][1][kind] += wrong
                 continue
             n_ok += 1
             for q_, a in zip(sel, ids):
@@ -541,4 +675,9 @@ def skin_premise(d, full, glob_pos0, h_of, s, disps, global_grid=True):
                 n_bad += not truth <= skin[q_]
         admitted.append(n_ok)
         violations.append(n_bad)
+        for rule in COVER_RULES if cover else ():
+            cov[rule][0].append(cstep[rule][0])
+            cov[rule][1].append(cstep[rule][1])
+    if cover:
+        return mismatch, admitted, violations, {r: (np.array(v[0]), np.array(v[1])) for r, v in cov.items()}
     return mismatch, admitted, violations

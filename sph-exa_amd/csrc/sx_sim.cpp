@@ -327,21 +327,89 @@ __global__ void chunkCoverKernel(const double* x, const double* y, const double*
  *  current positions, or the exact search), over the locals and the halos of the last build only.  That search saw
  *  every particle within a target's radius only if the target's sphere lies inside its chunk's request box of that
  *  build: radius 2 r_i scale, r = hb (rebuilt skins: the h of their build, scale 1 + s) or h (exact search, scale 1).
+ *  The halos are the particles that were inside the box AT THE BUILD, at their current positions.  A peer's particle p
+ *  that was outside the box then and is within R of the target i now is no halo, though it is inside the box now: the
+ *  sphere inside the box is not enough.  Let d_q(t) be the move of particle q in reuse step t since the build, and
+ *  w(t) any vector per step.  p_build - (x_i - sum_t w(t)) = (p_now - x_i) - sum_t (d_p(t) - w(t)), so with
+ *  |p_now - x_i| <= R the particle was, at the build, within R + sum_t max_q |d_q(t) - w(t)| of the centre
+ *  x_i - sum_t w(t): if that sphere lies inside the box, p was inside the box at the build, hence a halo.  Every
+ *  particle of every rank is in the all-reduced displacement grid, so its component ranges bound max_q.  Two choices:
+ *    w = 0:      centre x_i (now), radius R + D, D = sum_t max_q |d_q(t)| (drift[0]);
+ *    w = d_i(t): centre the target's position at the build, radius R + relg_i, relg_i = sum_t max_q |d_q(t) - d_i(t)|
+ *                (Galilean-invariant: nothing under a uniform translation of everything; a target moving through
+ *                resting peers pays for the motion once, not twice as with w = 0).
+ *  A target is covered when either sphere lies inside its box.  (The filter's own relative bound, d_i + A_C, does not
+ *  serve here: A_C only counts the grid cells within the largest skin radius of the cluster, and a particle coming
+ *  from beyond the box starts outside them -- its first steps would be missing from the sum.  The ranges of the whole
+ *  grid have no such region.)
  *  One workgroup per listed cluster; flag |= 1 when some sphere leaves its box (then every rank redoes the step from
  *  a full sync) */
 __global__ void coverListKernel(const uint32_t* list, uint32_t maxList, uint32_t first, uint32_t last, const double* x,
                                 const double* y, const double* z, const float* r, float scale, const ReqBox* boxes,
-                                DevBox box, double qmargin, unsigned* flag)
+                                DevBox box, double qmargin, const double* drift, const double* x0, const double* y0,
+                                const double* z0, const double* relg, unsigned* flag)
 {
     const uint32_t k = blockIdx.x;
     if (k >= min(list[0], maxList)) return;
     const uint32_t i = first + list[1 + k] * kCluster + threadIdx.x;
     if (i >= last) return;
-    const ReqBox& b = boxes[(i - first) / kChunk];
-    const double  R = 2.0 * (double)r[i] * (double)scale * (1.0 + 1e-6) + qmargin;
-    const bool    out = fabs(foldPbc(x[i] - b.c[0], box, 0)) + R > b.s[0] ||
-                     fabs(foldPbc(y[i] - b.c[1], box, 1)) + R > b.s[1] || fabs(foldPbc(z[i] - b.c[2], box, 2)) + R > b.s[2];
-    if (out) atomicOr(flag, 1u);
+    const ReqBox& b  = boxes[(i - first) / kChunk];
+    const double  R  = 2.0 * (double)r[i] * (double)scale * (1.0 + 1e-6) + qmargin;
+    const double  Ra = R + drift[0], Rr = R + relg[i];
+    const bool    outNow = fabs(foldPbc(x[i] - b.c[0], box, 0)) + Ra > b.s[0] ||
+                        fabs(foldPbc(y[i] - b.c[1], box, 1)) + Ra > b.s[1] ||
+                        fabs(foldPbc(z[i] - b.c[2], box, 2)) + Ra > b.s[2];
+    const bool    outBuild = fabs(foldPbc(x0[i] - b.c[0], box, 0)) + Rr > b.s[0] ||
+                          fabs(foldPbc(y0[i] - b.c[1], box, 1)) + Rr > b.s[1] ||
+                          fabs(foldPbc(z0[i] - b.c[2], box, 2)) + Rr > b.s[2];
+    if (outNow && outBuild) atomicOr(flag, 1u);
+}
+
+/*! the last position update's displacements over the all-reduced grid (every particle of every rank lies in some
+ *  cell), reduced to red[0]: the largest length (per cell the length of the largest components, rounded upwards; float
+ *  bits -- non-negative floats order like their bits), red[1..3]: the smallest, red[4..6]: the largest x, y, z
+ *  component (ordered bits; initialised like a cell: 0xffffffff, 0 -- an empty cell changes nothing) */
+__global__ void skinGridMaxKernel(const uint32_t* cells, uint32_t nc, uint32_t* red)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    float          m = 0.0f;
+    uint32_t       lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
+    if (i < nc && cells[i] != 0xffffffffu) // a cell without particles has no range
+    {
+        for (int d = 0; d < 3; ++d)
+            lo[d] = cells[d * nc + i], hi[d] = cells[(3 + d) * nc + i];
+        const float ex = fmaxf(fabsf(orderedFloat(lo[0])), fabsf(orderedFloat(hi[0])));
+        const float ey = fmaxf(fabsf(orderedFloat(lo[1])), fabsf(orderedFloat(hi[1])));
+        const float ez = fmaxf(fabsf(orderedFloat(lo[2])), fabsf(orderedFloat(hi[2])));
+        m              = sqrtf(fmaf(ex, ex, fmaf(ey, ey, ez * ez))) * (1.0f + 0x1p-18f) + 1e-30f;
+    }
+    m = waveMax(m);
+    for (int d = 0; d < 3; ++d)
+        lo[d] = waveMin(lo[d]), hi[d] = waveMax(hi[d]);
+    if ((threadIdx.x & 63) == 0 && m > 0.0f)
+    {
+        atomicMax(&red[0], __float_as_uint(m));
+        for (int d = 0; d < 3; ++d)
+            atomicMin(&red[1 + d], lo[d]), atomicMax(&red[4 + d], hi[d]);
+    }
+}
+
+/*! the drift bounds of coverListKernel after a reuse step's grid reduction: drift[0] += the step's largest displacement;
+ *  per local i, relg[i] += the largest |d_q - d_i| over the grid's component ranges, rounded upwards.  The float
+ *  displacements are within 2^-24 (relative) of the moves themselves: 2^-22 of the largest covers both ends */
+__global__ void skinDriftKernel(const uint32_t* red, uint32_t first, uint32_t last, const float* dx, const float* dy,
+                                const float* dz, double* drift, double* relg)
+{
+    const uint32_t t  = blockIdx.x * blockDim.x + threadIdx.x;
+    const float    mx = __uint_as_float(red[0]);
+    if (t == 0) drift[0] += (double)mx * (1.0 + 1e-6);
+    const uint32_t i = first + t;
+    if (i >= last || red[1] == 0xffffffffu) return;
+    const float ex = fmaxf(fabsf(orderedFloat(red[1]) - dx[i]), fabsf(orderedFloat(red[4]) - dx[i]));
+    const float ey = fmaxf(fabsf(orderedFloat(red[2]) - dy[i]), fabsf(orderedFloat(red[5]) - dy[i]));
+    const float ez = fmaxf(fabsf(orderedFloat(red[3]) - dz[i]), fabsf(orderedFloat(red[6]) - dz[i]));
+    const float e  = sqrtf(fmaf(ex, ex, fmaf(ey, ey, ez * ez))) * (1.0f + 0x1p-18f) + 0x1p-22f * mx + 1e-30f;
+    relg[i] += (double)e * (1.0 + 1e-6);
 }
 
 /*! one wave per peer request box: traverse the local tree, mark local particles inside the box (minimum image)
@@ -1976,6 +2044,20 @@ int skinHaloRefresh(sx_sim* s, hipStream_t st)
     if (!cells) return SX_ERR_NOMEM;
     SIM_COMM(s->comm->allreduceMinU32(cells, 3 * nc, st));
     SIM_COMM(s->comm->allreduceMaxU32(cells + 3 * nc, 3 * nc, st));
+    // how far any particle of any rank can have moved since the build (coverListKernel's D)
+    double*   drift = s->mem.get<double>("skin.drift", 8);
+    double*   relg  = s->mem.get<double>("skin.relg", s->cap);
+    const float *dx = s->mem.get<float>("skin.dx", s->cap), *dy = s->mem.get<float>("skin.dy", s->cap),
+                *dz = s->mem.get<float>("skin.dz", s->cap);
+    if (!drift || !relg || !dx || !dy || !dz) return SX_ERR_NOMEM;
+    uint32_t* red = reinterpret_cast<uint32_t*>(drift + 2); // 7 words
+    SIM_HIP(hipMemsetAsync(red, 0, 7 * 4, st));
+    SIM_HIP(hipMemsetAsync(red + 1, 0xff, 3 * 4, st));
+    skinGridMaxKernel<<<grid(nc), 256, 0, st>>>(cells, (uint32_t)nc, red);
+    const size_t nl = s->last - s->first;
+    skinDriftKernel<<<std::max(1u, grid(nl)), 256, 0, st>>>(red, (uint32_t)s->first, (uint32_t)s->last, dx, dy, dz, drift,
+                                                           relg);
+    SIM_HIP(hipGetLastError());
     return SX_OK;
 }
 
@@ -2407,6 +2489,22 @@ extern "C"
                     SIM_HIP(hipMemcpyAsync(s->h + s->first, h0, (s->last - s->first) * 4, hipMemcpyDeviceToDevice, st));
                 if (int e = distributedSync(s, st, margin * skinMargin)) return e;
                 SIM_HIP(hipMemcpyAsync(h0, s->h + s->first, (s->last - s->first) * 4, hipMemcpyDeviceToDevice, st));
+                if (skinOn)
+                {
+                    // the halo set is this sync's: no particle has moved since (coverListKernel's drift bounds and
+                    // the locals' positions at the build)
+                    double* drift = s->mem.get<double>("skin.drift", 8);
+                    double* relg  = s->mem.get<double>("skin.relg", s->cap);
+                    double* p0[3] = {s->mem.get<double>("skin.x0", s->cap), s->mem.get<double>("skin.y0", s->cap),
+                                     s->mem.get<double>("skin.z0", s->cap)};
+                    if (!drift || !relg || !p0[0] || !p0[1] || !p0[2]) return SX_ERR_NOMEM;
+                    const size_t f0 = s->first, nl0 = s->last - s->first;
+                    SIM_HIP(hipMemsetAsync(drift, 0, 8 * sizeof(double), st));
+                    SIM_HIP(hipMemsetAsync(relg + f0, 0, nl0 * sizeof(double), st));
+                    const double* pc[3] = {s->x, s->y, s->z};
+                    for (int d = 0; d < 3; ++d)
+                        SIM_HIP(hipMemcpyAsync(p0[d] + f0, pc[d] + f0, nl0 * sizeof(double), hipMemcpyDeviceToDevice, st));
+                }
             }
             else if (!reuse && !synced)
             {
@@ -2531,16 +2629,22 @@ extern "C"
             }
             else
             {
-                const double qm = quantMargin(s->dbox);
+                const double  qm    = quantMargin(s->dbox);
+                // (skinHaloRefresh: this step's drift bounds; the build's positions)
+                const double *drift = s->mem.get<double>("skin.drift", 8), *relg = s->mem.get<double>("skin.relg", 1),
+                             *x0 = s->mem.get<double>("skin.x0", 1), *y0 = s->mem.get<double>("skin.y0", 1),
+                             *z0 = s->mem.get<double>("skin.z0", 1);
+                if (!drift || !relg || !x0 || !y0 || !z0) return SX_ERR_NOMEM;
                 if (skc.rebuilt)
                     coverListKernel<<<skc.rebuilt, kCluster, 0, st>>>(
                         s->mem.get<uint32_t>("skin.l1", 1), skc.rebuilt, (uint32_t)s->first, (uint32_t)s->last, s->x,
                         s->y, s->z, s->mem.get<float>("skin.hb", 1), 1.0f + s->skin.built, myBoxes, s->dbox, qm,
-                        flg + 1);
+                        drift, x0, y0, z0, relg, flg + 1);
                 if (skc.exact)
                     coverListKernel<<<skc.exact, kCluster, 0, st>>>(s->mem.get<uint32_t>("skin.l2", 1), skc.exact,
                                                                     (uint32_t)s->first, (uint32_t)s->last, s->x, s->y,
-                                                                    s->z, s->h, 1.0f, myBoxes, s->dbox, qm, flg + 1);
+                                                                    s->z, s->h, 1.0f, myBoxes, s->dbox, qm, drift,
+                                                                    x0, y0, z0, relg, flg + 1);
             }
             if (skinOn) SIM_HIP(hipMemcpyAsync(flg + 4, s->stats + 13, 4, hipMemcpyDeviceToDevice, st));
             unsigned hf = 0;

@@ -31,6 +31,11 @@ def main():
                     help="skin factor s: check the multi-rank skin argument (dist_oracle.skin_premise) over --steps "
                          "displacement steps of a sliding + sheared lattice instead of running VE steps")
     ap.add_argument("--premise-speed", type=float, default=0.04, help="slide per step in lattice spacings")
+    ap.add_argument("--premise-field", default="slide", choices=["slide", "converge"],
+                    help="slide: the sliding + sheared lattice; converge: a patch of one rank at its boundary with "
+                         "another closing on that resting rank, everything else at rest "
+                         "(dist_oracle.converging_patch)")
+    ap.add_argument("--premise-ball", type=float, default=4.0, help="radius of the converging patch in spacings")
     args = ap.parse_args()
     import torch.distributed as dist
 
@@ -58,18 +63,36 @@ def main():
         # plus a shear: --premise-speed lattice spacings per step
         V = args.premise_speed / args.side
         disps, pos = [], pos0.copy()
+        if args.premise_field == "converge":
+            # the owners of this decomposition (by id), the same on every rank
+            import torch
+
+            own = torch.zeros(st.n, dtype=torch.int64)
+            own[torch.from_numpy(full.id[d.first:d.last].astype(np.int64))] = args.rank
+            dist.all_reduce(own, op=dist.ReduceOp.SUM)
+            reach = 2.0 * float(st.h.max()) * do.HALO_MARGIN * (1.0 + s) * args.side  # of a request box, in spacings
+            patch, direction, _, pair = do.converging_patch(pos0, own.numpy(), box, 1.0 / args.side,
+                                                            args.premise_ball, reach)
+            out["patch"] = np.array([int(patch.sum()), *pair])
         for _ in range(args.steps):
             dsp = np.zeros_like(pos)
-            dsp[:, 0] = -V * (pos[:, 0] > 0) + 0.3 * V * np.sin(2 * np.pi * pos[:, 1])
-            dsp[:, 1] = 0.2 * V * np.cos(2 * np.pi * pos[:, 2])
+            if args.premise_field == "converge":
+                dsp[patch] = V * direction
+            else:
+                dsp[:, 0] = -V * (pos[:, 0] > 0) + 0.3 * V * np.sin(2 * np.pi * pos[:, 1])
+                dsp[:, 1] = 0.2 * V * np.cos(2 * np.pi * pos[:, 2])
             disps.append(dsp)
             pos = pos + dsp
             pos = -0.5 + np.mod(pos + 0.5, 1.0)
         for tag, glob in (("global", True), ("local", False)):
-            mm, adm, vio = do.skin_premise(d, full, pos0, st.h.astype(np.float64), s, disps, global_grid=glob)
+            mm, adm, vio, *cov = do.skin_premise(d, full, pos0, st.h.astype(np.float64), s, disps, global_grid=glob,
+                                                 cover=glob)
             out[f"{tag}_mismatch"] = np.array([mm])
             out[f"{tag}_admitted"] = np.array(adm)
             out[f"{tag}_violations"] = np.array(vio)
+            for rule, (accepted, wrong) in (cov[0].items() if cov else ()):
+                out[f"cover_accepted_{rule}"] = accepted  # [step, radius kind]
+                out[f"cover_wrong_{rule}"] = wrong
         out["halos"] = np.array([d.total - (d.last - d.first)])
         np.savez(os.path.join(args.out, f"rank{args.rank}.npz"), **out)
         dist.barrier()

@@ -1,12 +1,17 @@
 """Worker of the multi-rank skin-list test (tests/test_gpu_distributed_skin.py), launched by torch.distributed.run.
 
-  python -m torch.distributed.run --nproc-per-node P ... tests/dist_skin_worker.py --out DIR --ic sedov|noh
-      [--side S] [--steps K] [--skin 0.08] [--max-reuse 24]
+  python -m torch.distributed.run --nproc-per-node P ... tests/dist_skin_worker.py --out DIR
+      --ic sedov|noh|evrard|converge [--side S] [--steps K] [--skin 0.08] [--max-reuse 24]
 
 Every rank runs two simulations over the host-staged transport: `a` with skin lists (filter-served steps between
 full builds), `b` with the skin off (a fresh distributed sync + search every step).  Before each step b is handed a's
 state of this rank, so both step from the same global state; the rank writes, per step, ids / nc / h and the compared
 fields of both, and a's skin statistics, to DIR/rank<r>.npz.
+
+--ic converge: the cold uniform lattice (Sedov's, its energy spike replaced by the background value, h converged) at
+rest, but for a patch of one rank inside a ball on its boundary with another rank, which moves towards that resting
+rank (dist_oracle.converging_patch on the owners of the first sync): the clusters around the patch go stale and are
+searched again at a rank boundary while particles of the peer close in.
 """
 import argparse
 import os
@@ -34,6 +39,10 @@ def main():
     ap.add_argument("--g", type=float, default=0.0, help="gravitational constant (self-gravity; evrard: 1)")
     ap.add_argument("--std", action="store_true", help="std propagator (HydroProp)")
     ap.add_argument("--av-clean", action="store_true", help="HydroVeProp<avClean=true>")
+    ap.add_argument("--ball", type=float, default=3.0, help="converge: radius of the patch in lattice spacings")
+    ap.add_argument("--patch-step", type=float, default=0.04,
+                    help="converge: the patch's move in the step before the first, in lattice spacings (dt0 = this / "
+                         "speed; dt may grow by 1.1 per step)")
     args = ap.parse_args()
 
     import torch.distributed as dist
@@ -46,6 +55,28 @@ def main():
     ctx = sx.Context(0)
     comm = sx.Comm("host")
     st, obox = {"noh": po.noh_state, "evrard": po.evrard_state}.get(args.ic, po.sedov_state)(args.side)
+    if args.ic == "converge":
+        import dist_oracle as do
+
+        ora = po.load_oracle()
+        st.temp[:] = np.float64(st.temp.min())
+        po.converge_h(ora, st, obox)
+        # owners as the first sync assigns them, computed on the host from the whole IC
+        owner = do.sfc_owners(ora, st, obox, size)
+        pos = np.stack([st.x, st.y, st.z], axis=1).astype(np.float64)
+        reach = 2.0 * float(st.h.max()) * do.HALO_MARGIN * (1.0 + args.skin) * args.side  # request box, in spacings
+        # tilted off the lattice axes: with the velocity along an axis, a resting particle whose only moving neighbours
+        # lie in its own lattice plane has divv = 0 up to rounding, and the AV switch's test divv < 0 then puts alpha
+        # at alphamin or near alphamax with the order of the neighbour sum (no lattice vector up to 3 spacings is
+        # perpendicular to the tilted direction)
+        patch, direction, _, pair = do.converging_patch(pos, owner, obox, 1.0 / args.side, args.ball, reach,
+                                                        tilt=(0.113, 0.171, 0.067))
+        dt0 = args.patch_step / args.side  # unit speed
+        for k, d in enumerate(("x", "y", "z")):
+            st.arrays["v" + d][patch] = np.float32(direction[k])
+            # the integrator's previous displacement, as pyoracle.noh_state sets it
+            st.arrays[d + "_m1"][:] = (st.arrays["v" + d].astype(np.float64) * dt0).astype(np.float32)
+        st.minDt = st.minDt_m1 = dt0
     if args.ic in ("evrard", "noh"):
         po.converge_h(po.load_oracle(), st, obox)  # the IC's h would iterate in the first search
     box = sx.make_box(list(obox.lim), list(obox.bnd))
@@ -72,8 +103,19 @@ def main():
             out[f"s{s}_{tag}_egrav"] = np.array([sim.conserved()["egrav"]])
         ks = a.skin_stats()
         out[f"s{s}_skin"] = np.array([ks[k] for k in SKIN] + [ks["factor"], ks["next_factor"], ks["kept_clusters"],
-                                                             ks["frozen_clusters"]], np.float64)
+                                                             ks["frozen_clusters"], ks["early_exact"]], np.float64)
         out[f"s{s}_layout"] = np.array(list(a.layout().values()), np.int64)
+        if args.ic == "converge":
+            # how far this rank's patch particles are from where they started (minimum image): sum, count
+            g = a.get(["id", "x", "y", "z"])
+            sel = patch[g["id"].astype(np.int64)]
+            d = np.stack([g[k][sel] for k in ("x", "y", "z")], axis=1) - pos[g["id"].astype(np.int64)[sel]]
+            d -= np.rint(d)  # the unit periodic box
+            out[f"s{s}_drift"] = np.array([np.sqrt(np.sum(d * d, axis=1)).sum(), sel.sum()], np.float64)
+    if args.ic == "converge":
+        out["patch"] = np.array([int(patch.sum()), *pair], np.int64)
+        out["spacing"] = np.array([1.0 / args.side, float(st.h.max())])
+        out["patch_ids"] = st.id[patch].astype(np.int64)
     np.savez(os.path.join(args.out, f"rank{rank}.npz"), **out)
     a.close()
     b.close()

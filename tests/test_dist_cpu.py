@@ -196,3 +196,40 @@ def test_skin_premise_several_ranks(tmp_path, nproc, side, speed):
     assert adm > 0
     if speed > 0.1:
         assert loc_vio > 0
+
+
+CONVERGE_SPEED = 0.16  # spacings per step: six steps carry the patch 0.96 spacings, see the test's docstring
+
+
+@pytest.mark.parametrize("nproc,side,field,speed", [(2, 14, "converge", CONVERGE_SPEED),
+                                                    (3, 14, "converge", CONVERGE_SPEED),
+                                                    (2, 14, "slide", 0.04), (3, 14, "slide", 0.04),
+                                                    (3, 14, "slide", 0.12)])
+def test_skin_research_cover_several_ranks(tmp_path, nproc, side, field, speed):
+    """the clusters the drift bound does NOT admit on a reuse step are searched again over the rank's locals and the
+    halos of the last build (sx_sim.cpp coverListKernel; dist_oracle.skin_premise(cover=True)), with the radius of a
+    rebuilt skin and of the exact search.  A particle of another rank that was outside the request box at the build
+    and has moved in since is no halo: that search cannot see it.  Under the corrected acceptance rule (the sphere
+    grown by a bound of every particle's motion since the build inside the build's box, "build-box+drift") no accepted target's
+    candidate set differs from the truth over all ranks, and the rule still accepts re-searched clusters (it does not
+    turn every stale step into a resync).  In the converging patch (the part of one rank inside a ball on its boundary
+    with a resting rank moving towards that rank, dist_oracle.converging_patch) the rule without the drift term accepts targets that miss a neighbour:
+    the scenario reaches the gap.  On the lattice the nearest particle that is no halo stands a plane of the lattice
+    behind the box face, about 0.9 spacings from the sphere of a target at the boundary (2 h (1 + s) = 3.11 spacings,
+    the box face at 3.27, the next plane at 4), hence 6 steps of 0.16 spacings"""
+    ranks = run_ranks(tmp_path, nproc, side, 6, extra=("--skin-premise", "0.08", "--premise-speed", str(speed),
+                                                       "--premise-field", field))
+    fixed, old = "build-box+drift", "build-box"
+    acc = {r: sum(int(q[f"cover_accepted_{r}"].sum()) for q in ranks) for r in (fixed, old)}
+    wrong = {r: sum(int(q[f"cover_wrong_{r}"].sum()) for q in ranks) for r in (fixed, old)}
+    for r in (fixed, old):
+        print(field, nproc, r, "accepted [step][rebuilt, exact] per rank",
+              [q[f"cover_accepted_{r}"].tolist() for q in ranks], "wrong targets",
+              [q[f"cover_wrong_{r}"].tolist() for q in ranks])
+    for q in ranks:
+        assert int(q["global_mismatch"][0]) == 0
+        assert int(q[f"cover_wrong_{fixed}"].sum()) == 0
+    if field == "converge":
+        assert acc[fixed] > 0
+        assert wrong[old] > 0
+        assert all(int(q["patch"][0]) == int(ranks[0]["patch"][0]) > 0 for q in ranks)

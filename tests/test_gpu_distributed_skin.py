@@ -39,13 +39,9 @@ def merged(ranks, s, tag, keys):
     return {k: v[o] for k, v in out.items()}
 
 
-@pytest.mark.parametrize("nproc,port,ic,side,steps,skin", [(2, 29651, "sedov", 20, 10, 0.08),
-                                                           (3, 29652, "sedov", 20, 8, 0.08),
-                                                           (2, 29653, "noh", 20, 8, 0.08),
-                                                           (3, 29654, "noh", 22, 8, 0.3),
-                                                           (8, 29655, "sedov", 24, 6, 0.08)])
-def test_distributed_skin_equals_fresh_search(tmp_path, nproc, port, ic, side, steps, skin):
-    ranks = run(tmp_path, nproc, port, ic, side, steps, skin)
+def check_equals_fresh_search(ranks, ic, nproc, steps):
+    """after every step, by id over all ranks: nc and h of the skin run equal those of the fresh distributed search of
+    the same state, the fields agree to float summation order, one dt, the same build decisions on every rank"""
     keys = ["id", "nc", "h", "xm", "kx", "divv", "alpha", "ax", "ay", "az", "du", "x", "vx"]
     n = None
     for s in range(steps):
@@ -65,6 +61,16 @@ def test_distributed_skin_equals_fresh_search(tmp_path, nproc, port, ic, side, s
         sk = np.array([d[f"s{s}_skin"] for d in ranks])
         for col in (0, 1, 4, 5, 6, 7):  # builds, reuse steps, plain steps, resyncs, skin factor, next factor
             assert np.all(sk[:, col] == sk[0, col]), (s, col, sk[:, col])
+
+
+@pytest.mark.parametrize("nproc,port,ic,side,steps,skin", [(2, 29651, "sedov", 20, 10, 0.08),
+                                                           (3, 29652, "sedov", 20, 8, 0.08),
+                                                           (2, 29653, "noh", 20, 8, 0.08),
+                                                           (3, 29654, "noh", 22, 8, 0.3),
+                                                           (8, 29655, "sedov", 24, 6, 0.08)])
+def test_distributed_skin_equals_fresh_search(tmp_path, nproc, port, ic, side, steps, skin):
+    ranks = run(tmp_path, nproc, port, ic, side, steps, skin)
+    check_equals_fresh_search(ranks, ic, nproc, steps)
     last = np.array([d[f"s{steps - 1}_skin"] for d in ranks])
     kept, frozen = int(last[:, 8].sum()), int(last[:, 9].sum())  # clusters whose lists were kept (of them frozen)
     print(ic, nproc, side, skin, dict(zip(SKIN, last[0][:6])), "stale per rank", last[:, 2], "kept", kept,
@@ -73,6 +79,47 @@ def test_distributed_skin_equals_fresh_search(tmp_path, nproc, port, ic, side, s
     if ic == "sedov":
         # the lattice outside the blast: steps whose hits match a recorded list set keep it on every rank's clusters
         assert kept > 0, last
+
+
+@pytest.mark.parametrize("nproc,port,skin", [(2, 29660, 0.05), (2, 29661, 0.08), (3, 29662, 0.05), (3, 29663, 0.08)])
+def test_distributed_skin_converging_patch(tmp_path, nproc, port, skin):
+    """clusters searched again on a reuse step at a rank boundary while the peer's particles close in
+    (tests/dist_skin_worker.py --ic converge): a cold lattice at rest but for a patch of one rank, a ball of 4
+    spacings on its boundary with a resting rank, which moves towards that rank, 0.02 spacings in the step before the
+    first and up to 1.1 times more with every step.  The re-search of a stale cluster only sees the halos of the last
+    full build; a particle that was outside the request box then is no halo however close it has come
+    (sx_sim.cpp coverListKernel: the sphere grown by a bound of the motion since the build must fit the box, or
+    every rank redoes the step from a full sync).  Same assertions as test_distributed_skin_equals_fresh_search after
+    every step.  And the path was taken: the patch's mean drift passes the box's slack over the search sphere plus the
+    skin, (kHaloMargin - 1) (1 + s) 2 h + s 2 h; some reuse step served stale clusters (searched them again) with
+    neither a full build nor a resync on that step.  Side 40: 64000 particles, 250 clusters of 256 -- the clusters
+    around the patch stay below the share of 1/8 that makes the next step a full build"""
+    side, steps = 40, 16
+    ranks = run(tmp_path, nproc, port, "converge", side, steps, skin, extra=("--ball", "4", "--patch-step", "0.02"))
+    # per step, summed over the ranks: stale, exact-search and early exact clusters; of rank 0: builds, reuse steps,
+    # resyncs (the same on every rank); the patch's mean drift in units of h
+    sk = np.array([[d[f"s{s}_skin"] for d in ranks] for s in range(steps)])  # [step, rank, column]
+    cum = np.concatenate([np.zeros((1,) + sk.shape[1:]), sk])
+    per = np.diff(cum, axis=0)
+    spacing, h = ranks[0]["spacing"]
+    drift = np.array([sum(d[f"s{s}_drift"][0] for d in ranks) / sum(d[f"s{s}_drift"][1] for d in ranks)
+                      for s in range(steps)])
+    wrong = []
+    for s in range(steps):
+        ga, gb = merged(ranks, s, "a", ["id", "nc"]), merged(ranks, s, "b", ["id", "nc"])
+        wrong.append(int(np.sum(ga["nc"] != gb["nc"])))
+    print("converge", nproc, "ranks, s =", skin, "patch (particles, resting rank, moving rank)", ranks[0]["patch"])
+    served = []
+    for s in range(steps):
+        stale, exact, early = (int(per[s, :, c].sum()) for c in (2, 3, 10))
+        build, reuse, resync = (int(per[s, 0, c]) for c in (0, 1, 5))
+        print(f"  step {s}: stale {stale} exact {exact} (early exact {early}) build {build} reuse {reuse} "
+              f"resync {resync} drift {drift[s] / h:.3f} h = {drift[s] / spacing:.3f} spacings, wrong nc {wrong[s]}")
+        if reuse and stale > 0 and build == 0 and resync == 0:
+            served.append(s)
+    check_equals_fresh_search(ranks, "converge", nproc, steps)
+    assert drift[-1] >= ((1.05 - 1.0) * (1.0 + skin) + skin) * 2.0 * h, (drift[-1] / h, skin)
+    assert served, per[:, 0, :6]
 
 
 @pytest.mark.parametrize("nproc,port,side", [(2, 29656, 20), (3, 29657, 22)])
