@@ -39,6 +39,10 @@
  *   sx_extract_groups      sph::extractGroupGpu                 sph/include/sph/groups.hpp:31-48
  *   sx_update_h            sph::updateSmoothingLengthGpu        sph_gpu.hpp:78, update_h_gpu.cu:49-60
  *   sx_max_divv            cstone::MinMaxGpu (rhoTimestep)      sph/ts_global.hpp:72-94
+ *   sx_turb_*              sph::TurbulenceData, updateNoise, computePhases  sph/include/sph/hydro_turb/turbulence_data.hpp:46-184,
+ *                                                               driver.hpp:80-92, phases.hpp:47-72, create_modes.hpp:59-244
+ *   sx_stir                sph::computeStirringGpu              hydro_turb/stirring.hpp:123-126 (stirParticle :44-79)
+ *   sx_sim_set_turbulence  TurbVeProp::computeForces            main/src/propagator/turb_ve.hpp:114-119
  *   sx_sim_*               one HydroVeProp step (sync + computeForces + integrate), main/src/propagator/ve_hydro.hpp:132-218
  *
  * Conventions (reference semantics preserved):
@@ -525,6 +529,86 @@ int    sx_sim_skin_stats(sx_sim* sim, uint64_t out[14]);
  *  out[(i - first) * ngmax + k] for k < min(nc - 1, ngmax) (device buffer of (last - first) * ngmax words; the lists
  *  the step's pair kernels used, cstone::findNeighbors' layout) */
 int    sx_sim_export_neighbors(sx_sim* sim, uint32_t* out);
+
+/* ---- turbulence stirring (TurbVeProp, main/src/propagator/turb_ve.hpp:98-136, over sph/include/sph/hydro_turb/) ----
+ * An Ornstein-Uhlenbeck process per Fourier mode drives a large-scale acceleration field.  The host object sx_turb is
+ * sph::TurbulenceData (turbulence_data.hpp:46-184) without its device vectors; everything is double and follows the
+ * reference's order of operations, the generator is std::mt19937 with std::normal_distribution<double> /
+ * std::uniform_real_distribution<double>, so seeds give the reference's sequences. */
+/*! the entries of TurbulenceConstants() (main/src/init/turbulence_init.hpp:48-71) that TurbulenceData::initModes
+ *  reads (turbulence_data.hpp:150-183); numDim is 3 */
+typedef struct sx_turb_settings
+{
+    double   solWeight;      /* 0.5 */
+    uint64_t stMaxModes;     /* 100000 */
+    double   Lbox;           /* 1.0 */
+    double   stEnergyPrefac; /* 5.0e-3 */
+    double   stMachVelocity; /* 0.3 */
+    double   epsilon;        /* 1e-15 */
+    uint64_t rngSeed;        /* 251299 */
+    uint32_t stSpectForm;    /* 1: parabola; 0: band; 2: power law, randomly sampled angles */
+    double   powerLawExp;    /* 5/3 */
+    double   anglesExp;      /* 2.0 */
+} sx_turb_settings;
+typedef struct sx_turb sx_turb;
+/*! the defaults above */
+int sx_turb_default_settings(sx_turb_settings* s);
+/*! TurbulenceData's constructor: initModes (turbulence_data.hpp:150-183) with createStirringModes
+ *  (create_modes.hpp:59-244, spectral forms 0, 1, 2, its mode cap included), then the 6 numModes OU phases drawn with
+ *  mean 0 and standard deviation `variance`.  SX_ERR_ARG for a spectral form > 2, stMaxModes == 0 or Lbox,
+ *  stMachVelocity <= 0. */
+int  sx_turb_create(sx_turb** turb, const sx_turb_settings* s);
+void sx_turb_destroy(sx_turb* turb);
+/*! what TurbulenceData::loadOrStore saves (turbulence_data.hpp:90-120).  sx_turb_get_scalars: {variance, decayTime,
+ *  solWeight, solWeightNorm}; sx_turb_get_arrays: modes (3 numModes), amplitudes (numModes), phases (6 numModes), each
+ *  nullable; sx_turb_get_rng: the generator in the text form of operator<< on std::mt19937 (the reference's
+ *  rngEngineState), NUL-terminated into buf of cap bytes, returns the length without the NUL (call with cap 0 for the
+ *  size).  sx_turb_set_state restores all of it (rng NULL: the generator is kept); SX_ERR_ARG for text that is not a
+ *  generator state. */
+uint64_t sx_turb_num_modes(const sx_turb* turb);
+int      sx_turb_get_scalars(const sx_turb* turb, double out[4]);
+int      sx_turb_get_arrays(const sx_turb* turb, double* modes, double* amplitudes, double* phases);
+int64_t  sx_turb_get_rng(const sx_turb* turb, char* buf, size_t cap);
+int      sx_turb_set_state(sx_turb* turb, const double scalars[4], uint64_t numModes, const double* modes,
+                           const double* amplitudes, const double* phases, const char* rng);
+/*! largest |i|, |j|, |k| of the mode table on its own lattice w0 (i, j, k): w0 is the largest (smallest nonzero
+ *  |component|) / n, n <= 16, that every component is a multiple of -- 2 pi / Lbox for the tables sx_turb_create makes;
+ *  taken from the table, not from the settings, so it holds after sx_turb_set_state.  -1 when there is no such w0. */
+int sx_turb_max_index(const sx_turb* turb);
+/*! the largest lattice index the fast variant of sx_stir keeps in registers (tables beyond it run the exact one) */
+int sx_turb_fast_limit(void);
+/*! updateNoise (driver.hpp:80-92): one OU step of every phase over dt with 6 numModes fresh normal draws */
+int sx_turb_update_noise(sx_turb* turb, double dt);
+/*! computePhases (phases.hpp:47-72): the projected phases, 3 numModes each, from the current OU phases */
+int sx_turb_compute_phases(const sx_turb* turb, double* phasesReal, double* phasesImag);
+/*! computeStirringGpu<double, float, double> (stirring.hpp:123-126, :44-121) with the projected phases of turb's
+ *  current OU phases: adds solWeightNorm sum_m amplitude_m (Re_m cos(k_m x) - Im_m sin(k_m x)) to f->ax, ay, az of the
+ *  view's particles: [firstBody, lastBody), or the explicit groups when groupStart is set (particles outside the view
+ *  are not touched).  sx_set_exact(1): the reference's loop (per-mode cos/sin in double, float accumulators, no
+ *  contraction).  Otherwise, for tables on an integer lattice with indices up to sx_turb_fast_limit(): three sincos
+ *  per particle (angles reduced in double), harmonics by recurrence and the sum in float; other tables run the exact
+ *  loop.
+ *  Synchronises (as driveTurbulence does, driver.hpp:120). */
+int sx_stir(sx_ctx* ctx, const sx_groups* g, const sx_fields* f, const sx_turb* turb);
+/*! the same with the reference's arguments: device arrays modes, phaseReal, phaseImag (3 numModes each), amplitudes
+ *  (numModes) */
+int sx_stir_device(sx_ctx* ctx, const sx_groups* g, const sx_fields* f, uint64_t numModes, const double* modes,
+                   const double* phaseReal, const double* phaseImag, const double* amplitudes, double solWeightNorm);
+/*! from now on every step of sim stirs as TurbVeProp::computeForces (turb_ve.hpp:114-119): after momentum/energy and
+ *  self-gravity, before the time-step and the position update, driveTurbulence (driver.hpp:102-128) with the minDt
+ *  current at that point.  The host draws the step's normals, the OU update and the projection run on the device (no
+ *  host synchronisation).  SX_ERR_ARG (sx_last_error has the reason) for the std and ve-bdt propagators and for a sim
+ *  with a communicator; sx_sim_set_comm on a stirred sim is refused likewise. */
+int sx_sim_set_turbulence(sx_sim* sim, const sx_turb_settings* s);
+/*! the sim's turbulence state, owned by the sim (valid until the sim is destroyed): synchronises and brings the OU
+ *  phases back from the device.  SX_ERR_ARG without sx_sim_set_turbulence. */
+int sx_sim_turbulence(sx_sim* sim, sx_turb** turb);
+/*! restart: sx_turb_set_state on the sim's turbulence state, uploaded to the device */
+int sx_sim_set_turbulence_state(sx_sim* sim, const double scalars[4], uint64_t numModes, const double* modes,
+                                const double* amplitudes, const double* phases, const char* rng);
+/*! device time (ms, HIP events) of the last step's {noise advance, stirring kernel}; both are part of the
+ *  UpdateQuantities stage of sx_sim_stage_times */
+int sx_sim_turbulence_times(sx_sim* sim, float out[2]);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,7 @@
 #include "sx_observables.hpp"
 #include "sx_tree.hpp"
 #include "sx_timestep.hpp"
+#include "sx_turb.hpp"
 
 using namespace sx;
 
@@ -177,6 +178,7 @@ extern "C"
     int           sx_ctx_exact_internal(sx_ctx* c) { return c->exact ? 1 : 0; }
     const float2* sx_ctx_table_internal(sx_ctx* c, int which) { return which ? c->whd : c->wh; }
     const float*  sx_ctx_powtab_internal(sx_ctx* c, uint32_t ng0) { return ensurePowTab(c, ng0); }
+    void          sx_ctx_set_error_internal(sx_ctx* c, const char* msg) { fail(c, SX_ERR_ARG, msg); }
 
     int sx_kernel_poly(const float* v, size_t n, float* w, float* dw)
     {
@@ -1064,6 +1066,90 @@ extern "C"
         SX_HIP(c, updateHGroups(GroupArgs{g->firstBody, g->lastBody, ng, g->groupStart, g->groupEnd}, ng0, nc, h, tab,
                                 c->stream));
         return SX_OK;
+    }
+
+    // ---- turbulence stirring (sph/include/sph/hydro_turb/stirring.hpp:81-126) ------------------------------------
+
+    //! stirring with host copies of the reference's arrays: the exact loop, or the fast kernel for a lattice table
+    static int stirHostTables(sx_ctx* c, const sx_groups* g, const sx_fields* f, uint64_t numModes, const double* modes,
+                              const double* phasesReal, const double* phasesImag, const double* amplitudes,
+                              double solWeightNorm)
+    {
+        namespace st = sx::turb;
+        st::StirArgs a{};
+        a.first = g->firstBody, a.last = g->lastBody, a.start = g->groupStart, a.end = g->groupEnd;
+        a.numGroups = g->groupStart ? g->numGroups
+                                    : (g->lastBody > g->firstBody ? (g->lastBody - g->firstBody + 63) / 64 : 0);
+        a.x = f->x, a.y = f->y, a.z = f->z, a.ax = f->ax, a.ay = f->ay, a.az = f->az;
+        a.numModes      = numModes;
+        a.solWeightNorm = solWeightNorm;
+        if (!a.numGroups || !numModes) return SX_OK;
+        st::Lattice lat;
+        if (!c->exact) lat = st::latticeOf(numModes, modes);
+        if (lat.ok)
+        {
+            std::vector<float> table(st::kSlots * st::kSlotCoefs);
+            st::denseTable(lat, numModes, amplitudes, solWeightNorm, phasesReal, phasesImag, table.data());
+            float* d = c->arena.get<float>("turb.table", table.size());
+            if (!d) return fail(c, SX_ERR_NOMEM, "sx_stir: coefficient table");
+            SX_HIP(c, hipMemcpyAsync(d, table.data(), table.size() * 4, hipMemcpyHostToDevice, c->stream));
+            a.table = d, a.present = lat.present, a.w0 = lat.w0;
+            SX_HIP(c, st::stirFast(a, c->stream));
+        }
+        else
+        {
+            double* d = c->arena.get<double>("turb.modes", 10 * numModes);
+            if (!d) return fail(c, SX_ERR_NOMEM, "sx_stir: mode tables");
+            const double* src[4] = {modes, phasesReal, phasesImag, amplitudes};
+            const size_t  cnt[4] = {3 * numModes, 3 * numModes, 3 * numModes, numModes};
+            double*       dst    = d;
+            for (int k = 0; k < 4; ++k)
+            {
+                SX_HIP(c, hipMemcpyAsync(dst, src[k], cnt[k] * 8, hipMemcpyHostToDevice, c->stream));
+                dst += cnt[k];
+            }
+            a.modes = d, a.phasesReal = d + 3 * numModes, a.phasesImag = d + 6 * numModes, a.amplitudes = d + 9 * numModes;
+            SX_HIP(c, st::stirExact(a, c->stream));
+        }
+        // the host tables are the caller's (or locals): done with them before returning (driver.hpp:120 syncGpu)
+        SX_HIP(c, hipStreamSynchronize(c->stream));
+        return SX_OK;
+    }
+
+    static bool stirArgsOk(const sx_groups* g, const sx_fields* f)
+    {
+        return groupsOk(g) && f && f->x && f->y && f->z && f->ax && f->ay && f->az &&
+               (g->groupStart || g->lastBody <= f->n);
+    }
+
+    int sx_stir(sx_ctx* c, const sx_groups* g, const sx_fields* f, const sx_turb* t)
+    {
+        if (!stirArgsOk(g, f) || !t) return fail(c, SX_ERR_ARG, "sx_stir: bad arguments");
+        std::vector<double> pr(3 * t->numModes), pi(3 * t->numModes);
+        sx::turb::computePhases(t->numModes, t->phases.data(), t->solWeight, t->modes.data(), pr.data(), pi.data());
+        return stirHostTables(c, g, f, t->numModes, t->modes.data(), pr.data(), pi.data(), t->amplitudes.data(),
+                              t->solWeightNorm);
+    }
+
+    int sx_stir_device(sx_ctx* c, const sx_groups* g, const sx_fields* f, uint64_t numModes, const double* modes,
+                       const double* phaseReal, const double* phaseImag, const double* amplitudes,
+                       double solWeightNorm)
+    {
+        if (!stirArgsOk(g, f) || (numModes && (!modes || !phaseReal || !phaseImag || !amplitudes)))
+            return fail(c, SX_ERR_ARG, "sx_stir_device: bad arguments");
+        // the tables are a few hundred doubles: the variant is chosen and the coefficients are formed on the host
+        std::vector<double> h(10 * numModes);
+        const double*       src[4] = {modes, phaseReal, phaseImag, amplitudes};
+        const size_t        cnt[4] = {3 * numModes, 3 * numModes, 3 * numModes, numModes};
+        double*             dst    = h.data();
+        for (int k = 0; k < 4 && numModes; ++k)
+        {
+            SX_HIP(c, hipMemcpyAsync(dst, src[k], cnt[k] * 8, hipMemcpyDeviceToHost, c->stream));
+            dst += cnt[k];
+        }
+        SX_HIP(c, hipStreamSynchronize(c->stream));
+        return stirHostTables(c, g, f, numModes, h.data(), h.data() + 3 * numModes, h.data() + 6 * numModes,
+                              h.data() + 9 * numModes, solWeightNorm);
     }
 
     int sx_max_divv(sx_ctx* c, uint32_t first, uint32_t last, const float* divv, float* out)

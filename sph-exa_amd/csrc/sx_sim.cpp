@@ -42,6 +42,7 @@
 #include "sx_skin.hpp"
 #include "sx_traverse.hpp"
 #include "sx_tree.hpp"
+#include "sx_turb.hpp"
 
 using namespace sx;
 using namespace sx::sim;
@@ -51,6 +52,7 @@ extern "C" int            sx_ctx_exact_internal(sx_ctx* c);
 extern "C" const float2*  sx_ctx_table_internal(sx_ctx* c, int which);
 extern "C" const float*   sx_ctx_powtab_internal(sx_ctx* c, uint32_t ng0);
 extern "C" sx::Transport* sx_comm_transport_internal(sx_comm* c);
+extern "C" void           sx_ctx_set_error_internal(sx_ctx* c, const char* msg);
 
 namespace
 {
@@ -2084,6 +2086,113 @@ int localSync(sx_sim* s, hipStream_t st)
     return SX_OK;
 }
 
+// ---- turbulence stirring (sx_turb.hpp) ----------------------------------------------------------------------------
+
+void turbDestroy(sx::turb::SimTurb* T)
+{
+    if (!T) return;
+    for (auto& e : T->ringEv)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& e : T->ev)
+        if (e) (void)hipEventDestroy(e);
+    sx_turb_destroy(T->host);
+    delete T;
+}
+
+//! the host turbulence state onto the device (sx_sim_set_turbulence, a restart): buffers for its mode count, the mode
+//! table, the OU phases and, for a table on the lattice, the slot of each mode.  Synchronous.
+int turbUpload(sx_sim* s)
+{
+    using namespace sx::turb;
+    SimTurb&       T = *s->turb;
+    const sx_turb& h = *T.host;
+    const size_t   M = h.numModes;
+    hipStream_t    st = (hipStream_t)sx_ctx_stream_internal(s->ctx);
+    SIM_HIP(hipStreamSynchronize(st));
+    T.phases     = s->mem.get<double>("turb.phases", 6 * M);
+    T.modes      = s->mem.get<double>("turb.modes", 3 * M);
+    T.amplitudes = s->mem.get<double>("turb.amplitudes", M);
+    T.phasesReal = s->mem.get<double>("turb.phasesReal", 3 * M);
+    T.phasesImag = s->mem.get<double>("turb.phasesImag", 3 * M);
+    T.normals    = s->mem.get<double>("turb.normals", 6 * M);
+    T.table      = s->mem.get<float>("turb.table", kSlots * kSlotCoefs);
+    T.slot       = s->mem.get<int32_t>("turb.slot", M);
+    bool ok      = T.phases && T.modes && T.amplitudes && T.phasesReal && T.phasesImag && T.normals && T.table && T.slot;
+    for (int k = 0; k < SimTurb::kRing; ++k)
+    {
+        T.ring[k]     = s->mem.pinned<double>("turb.ring" + std::to_string(k), 6 * M);
+        T.ringBusy[k] = false;
+        ok            = ok && T.ring[k];
+    }
+    if (!ok) return SX_ERR_NOMEM;
+    T.lat = latticeOf(M, h.modes.data());
+    if (M)
+    {
+        SIM_HIP(hipMemcpy(T.phases, h.phases.data(), 6 * M * 8, hipMemcpyHostToDevice));
+        SIM_HIP(hipMemcpy(T.modes, h.modes.data(), 3 * M * 8, hipMemcpyHostToDevice));
+        SIM_HIP(hipMemcpy(T.amplitudes, h.amplitudes.data(), M * 8, hipMemcpyHostToDevice));
+        if (T.lat.ok) SIM_HIP(hipMemcpy(T.slot, T.lat.slot.data(), M * 4, hipMemcpyHostToDevice));
+    }
+    return SX_OK;
+}
+
+/*! driveTurbulence (driver.hpp:102-128) inside the step: the host draws the step's normals (they do not depend on dt)
+ *  and queues them; one small kernel reads minDt from the device scalars -- the previous step's, or set_state's, as
+ *  d.minDt at driver.hpp:106 -- and does updateNoise, computePhases and the coefficient table; then the stirring kernel
+ *  over the locals.  Nothing here waits for work of this step.  The one wait is the ring slot's event, four steps old;
+ *  as long as sx_sim_step ends in a stream synchronise it has always completed and a single buffer would do -- the ring
+ *  is what keeps this function correct should that final synchronise go. */
+int turbStep(sx_sim* s, hipStream_t st)
+{
+    using namespace sx::turb;
+    SimTurb&     T = *s->turb;
+    sx_turb&     h = *T.host;
+    const size_t M = h.numModes;
+    SIM_HIP(hipEventRecord(T.ev[0], st));
+    if (M)
+    {
+        const int k = T.next;
+        // the copy queued from this slot kRing steps ago (see above)
+        if (T.ringBusy[k]) SIM_HIP(hipEventSynchronize(T.ringEv[k]));
+        drawNormals(h.gen, T.ring[k], 6 * M);
+        SIM_HIP(hipMemcpyAsync(T.normals, T.ring[k], 6 * M * 8, hipMemcpyHostToDevice, st));
+        SIM_HIP(hipEventRecord(T.ringEv[k], st));
+        T.ringBusy[k] = true;
+        T.next        = (k + 1) % SimTurb::kRing;
+        NoiseArgs na{};
+        na.dt       = &s->sc->minDt;
+        na.variance = h.variance, na.decayTime = h.decayTime, na.solWeight = h.solWeight;
+        na.solWeightNorm = h.solWeightNorm;
+        na.numModes      = M;
+        na.normals = T.normals, na.phases = T.phases, na.modes = T.modes, na.amplitudes = T.amplitudes;
+        na.phasesReal = T.phasesReal, na.phasesImag = T.phasesImag;
+        na.slot  = T.lat.ok ? T.slot : nullptr;
+        na.table = T.table;
+        SIM_HIP(advanceNoise(na, st));
+    }
+    SIM_HIP(hipEventRecord(T.ev[1], st));
+    if (M && s->last > s->first)
+    {
+        StirArgs a{};
+        a.first = (uint32_t)s->first, a.last = (uint32_t)s->last;
+        a.numGroups = (a.last - a.first + 63) / 64;
+        a.x = s->x, a.y = s->y, a.z = s->z, a.ax = s->ax, a.ay = s->ay, a.az = s->az;
+        a.numModes = M, a.solWeightNorm = h.solWeightNorm;
+        a.modes = T.modes, a.phasesReal = T.phasesReal, a.phasesImag = T.phasesImag, a.amplitudes = T.amplitudes;
+        a.table = T.table, a.present = T.lat.present, a.w0 = T.lat.w0;
+        const bool exact = sx_ctx_exact_internal(s->ctx) || !T.lat.ok;
+        SIM_HIP(exact ? stirExact(a, st) : stirFast(a, st));
+    }
+    SIM_HIP(hipEventRecord(T.ev[2], st));
+    if (s->p.g != 0.0)
+    {
+        // accelerationTimestep takes the stirred accelerations (computeForces ends with the stirring)
+        SIM_HIP(hipMemsetAsync(&s->sc->maxAccSqBits, 0, sizeof(unsigned long long), st));
+        maxAccSq(s, st);
+    }
+    return SX_OK;
+}
+
 } // namespace sx::sim
 
 extern "C"
@@ -2167,11 +2276,17 @@ extern "C"
         if (s->evAuxIn) (void)hipEventDestroy(s->evAuxIn);
         if (s->evAuxOut) (void)hipEventDestroy(s->evAuxOut);
         if (s->auxStream) (void)hipStreamDestroy(s->auxStream);
+        turbDestroy(s->turb);
         delete s;
     }
 
     int sx_sim_set_comm(sx_sim* s, sx_comm* c)
     {
+        if (s->turb)
+        {
+            sx_ctx_set_error_internal(s->ctx, "sx_sim_set_comm: a stirred sim (sx_sim_set_turbulence) runs on one rank");
+            return SX_ERR_ARG;
+        }
         sx::Transport* T = sx_comm_transport_internal(c);
         if (T && T->size() > 1)
         {
@@ -2936,6 +3051,11 @@ extern "C"
         }
         SIM_HIP(hipEventRecord(s->kev[13], st));
         SIM_HIP(hipEventRecord(s->ev[ev++], st));
+        // ---- turbulence stirring (TurbVeProp::computeForces, turb_ve.hpp:114-119)
+        if (s->turb)
+        {
+            if (int e = turbStep(s, st)) return e;
+        }
         // ---- integrate: global time-step, positions, h
         dtCandidateKernel<<<1, 1, 0, st>>>(s->sc, s->p.Krho, s->p.maxDtIncrease, s->p.g, s->p.eps, s->p.etaAcc,
                                            s->p.propagator != 1);
@@ -2981,6 +3101,9 @@ extern "C"
             (void)hipEventElapsedTime(&s->stageMs[k], s->ev[k], s->ev[k + 1]);
         for (size_t k = 0; k < s->kernelMs.size(); ++k)
             (void)hipEventElapsedTime(&s->kernelMs[k], s->kev[2 * k], s->kev[2 * k + 1]);
+        if (s->turb)
+            for (int k = 0; k < 2; ++k)
+                (void)hipEventElapsedTime(&s->turb->ms[k], s->turb->ev[k], s->turb->ev[k + 1]);
         s->lastStats.numFailed     = s->statsHost[1];
         s->lastStats.maxNeighbors  = s->statsHost[2];
         s->lastStats.sumNeighbors  = *reinterpret_cast<uint64_t*>(s->statsHost + 4);
@@ -3070,6 +3193,97 @@ extern "C"
     int sx_sim_last_stats(sx_sim* s, sx_nbstats* st)
     {
         *st = s->lastStats;
+        return SX_OK;
+    }
+
+    // ---- turbulence stirring ----------------------------------------------------------------------------------------
+
+    int sx_sim_set_turbulence(sx_sim* s, const sx_turb_settings* set)
+    {
+        if (!s) return SX_ERR_ARG;
+        const char* why = nullptr;
+        if (!set) why = "sx_sim_set_turbulence: no settings";
+        else if (s->p.propagator == 1) why = "sx_sim_set_turbulence: the std propagator has no stirred counterpart "
+                                             "(the reference stirs the VE propagators, turb_ve.hpp)";
+        else if (s->p.propagator == 2) why = "sx_sim_set_turbulence: stirring with block time-steps (ve-bdt) is not "
+                                             "supported by sx_sim; sx_stir takes the active-rung views";
+        else if (s->comm) why = "sx_sim_set_turbulence: a stirred sim runs on one rank (a communicator is set)";
+        if (why)
+        {
+            sx_ctx_set_error_internal(s->ctx, why);
+            return SX_ERR_ARG;
+        }
+        sx_turb* host = nullptr;
+        if (sx_turb_create(&host, set) != SX_OK)
+        {
+            sx_ctx_set_error_internal(s->ctx, "sx_sim_set_turbulence: invalid settings (sx_turb_create)");
+            return SX_ERR_ARG;
+        }
+        if (!s->turb)
+        {
+            auto* T  = new sx::turb::SimTurb;
+            T->host  = host;
+            bool made = true;
+            for (auto& e : T->ringEv)
+                made = made && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+            for (auto& e : T->ev)
+                made = made && hipEventCreate(&e) == hipSuccess;
+            if (!made)
+            {
+                turbDestroy(T); // with the host state
+                return SX_ERR_HIP;
+            }
+            s->turb = T;
+        }
+        else
+        {
+            if (hipStreamSynchronize((hipStream_t)sx_ctx_stream_internal(s->ctx)) != hipSuccess)
+            {
+                sx_turb_destroy(host);
+                return SX_ERR_HIP;
+            }
+            sx_turb_destroy(s->turb->host);
+            s->turb->host = host;
+        }
+        return turbUpload(s);
+    }
+
+    int sx_sim_turbulence(sx_sim* s, sx_turb** out)
+    {
+        if (!s || !out) return SX_ERR_ARG;
+        if (!s->turb)
+        {
+            sx_ctx_set_error_internal(s->ctx, "sx_sim_turbulence: sx_sim_set_turbulence was not called");
+            return SX_ERR_ARG;
+        }
+        sx_turb& h = *s->turb->host;
+        SIM_HIP(hipStreamSynchronize((hipStream_t)sx_ctx_stream_internal(s->ctx)));
+        if (h.numModes) SIM_HIP(hipMemcpy(h.phases.data(), s->turb->phases, h.phases.size() * 8, hipMemcpyDeviceToHost));
+        *out = &h;
+        return SX_OK;
+    }
+
+    int sx_sim_set_turbulence_state(sx_sim* s, const double scalars[4], uint64_t numModes, const double* modes,
+                                    const double* amplitudes, const double* phases, const char* rng)
+    {
+        if (!s) return SX_ERR_ARG;
+        if (!s->turb)
+        {
+            sx_ctx_set_error_internal(s->ctx, "sx_sim_set_turbulence_state: sx_sim_set_turbulence was not called");
+            return SX_ERR_ARG;
+        }
+        if (sx_turb_set_state(s->turb->host, scalars, numModes, modes, amplitudes, phases, rng) != SX_OK)
+        {
+            sx_ctx_set_error_internal(s->ctx, "sx_sim_set_turbulence_state: bad arrays or generator text");
+            return SX_ERR_ARG;
+        }
+        return turbUpload(s);
+    }
+
+    int sx_sim_turbulence_times(sx_sim* s, float out[2])
+    {
+        if (!s || !out || !s->turb) return SX_ERR_ARG;
+        out[0] = s->turb->ms[0], out[1] = s->turb->ms[1];
         return SX_OK;
     }
 

@@ -16,6 +16,11 @@
 #include "sx_hydro.hpp"
 #include "sx_tree.hpp"
 
+namespace sx::turb
+{
+struct SimTurb; // sx_turb.hpp
+}
+
 namespace sx::sim
 {
 
@@ -203,6 +208,7 @@ struct sx_sim
 
     sx::sim::BdtState bdt; // propagator 2 only
     sx::sim::SkinState skin;
+    sx::turb::SimTurb* turb{nullptr}; // turbulence stirring (sx_sim_set_turbulence), VE propagator on one rank
 
     Fields fields() const { return Fields{x, y, z, temp, h, m, vx, vy, vz, xm1, ym1, zm1, dum1, alpha, id, rung}; }
 };

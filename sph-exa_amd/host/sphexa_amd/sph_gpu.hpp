@@ -453,4 +453,37 @@ void updateSmoothingLengthGpu(const GroupView& grp, unsigned ng0, const unsigned
     sa::check(sx_update_h_groups(sa::context(), &g, ng0, nc, h), "updateSmoothingLengthGpu");
 }
 
+/*! hydro_turb/stirring.hpp:123-126 (stirring_gpu.cu), called by driveTurbulence (driver.hpp:116-119) of turb_ve.hpp.
+ *  stirring.hpp declares this template `extern` with a cstone::GroupView by value; where the cstone headers are on the
+ *  include path the definition below is that very template, so driveTurbulence's call resolves to it.  Elsewhere the
+ *  group view is duck-typed like the rest of this header. */
+#if __has_include("cstone/traversal/groups.hpp")
+} // namespace sph
+#include "cstone/traversal/groups.hpp"
+namespace sph
+{
+template<class Tc, class Ta, class T>
+void computeStirringGpu(cstone::GroupView grp, size_t numDim, const Tc* x, const Tc* y, const Tc* z, Ta* ax, Ta* ay,
+                        Ta* az, size_t numModes, const T* modes, const T* phaseReal, const T* phaseImag,
+                        const T* amplitudes, T solWeightNorm)
+#else
+template<class Tc, class Ta, class T, class GroupView>
+void computeStirringGpu(const GroupView& grp, size_t numDim, const Tc* x, const Tc* y, const Tc* z, Ta* ax, Ta* ay,
+                        Ta* az, size_t numModes, const T* modes, const T* phaseReal, const T* phaseImag,
+                        const T* amplitudes, T solWeightNorm)
+#endif
+{
+    static_assert(std::is_same_v<Tc, double> && std::is_same_v<Ta, float> && std::is_same_v<T, double>,
+                  "computeStirringGpu: double coordinates and modes, float accelerations (SphTypes)");
+    namespace sa = sphexa_amd;
+    if (numDim != 3) throw std::runtime_error("computeStirringGpu: numDim must be 3");
+    const sx_groups g = sa::toGroups(grp);
+    sx_fields       f{};
+    f.n = g.groupStart ? 0 : g.lastBody; // the view carries no array length; explicit groups are taken as given
+    f.x = const_cast<Tc*>(x), f.y = const_cast<Tc*>(y), f.z = const_cast<Tc*>(z);
+    f.ax = ax, f.ay = ay, f.az = az;
+    sa::check(sx_stir_device(sa::context(), &g, &f, numModes, modes, phaseReal, phaseImag, amplitudes, solWeightNorm),
+              "computeStirringGpu");
+}
+
 } // namespace sph

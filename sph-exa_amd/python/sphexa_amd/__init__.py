@@ -76,6 +76,23 @@ class SxTimestep(C.Structure):
                 ("dt_drift", C.c_float * 4)]
 
 
+class SxTurbSettings(C.Structure):
+    """sx_turb_settings: the entries of TurbulenceConstants() (main/src/init/turbulence_init.hpp:48-71) that
+    TurbulenceData::initModes reads; the defaults are the reference's"""
+    _fields_ = [("solWeight", C.c_double), ("stMaxModes", C.c_uint64), ("Lbox", C.c_double),
+                ("stEnergyPrefac", C.c_double), ("stMachVelocity", C.c_double), ("epsilon", C.c_double),
+                ("rngSeed", C.c_uint64), ("stSpectForm", C.c_uint32), ("powerLawExp", C.c_double),
+                ("anglesExp", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().sx_turb_default_settings(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError(f"unknown turbulence setting {k!r}")
+            setattr(self, k, v)
+
+
 class SxOctree(C.Structure):
     _fields_ = [("prefixes", _P), ("childOffsets", _P), ("parents", _P), ("levelRange", _P),
                 ("internalToLeaf", _P), ("leafToInternal", _P)]
@@ -229,6 +246,25 @@ def lib():
         "sx_gravity_ewald": (C.c_int, [vp, C.POINTER(SxGroups), C.POINTER(SxFields), C.POINTER(SxBox), vp, vp,
                                        C.c_float, C.POINTER(SxEwaldSettings), C.POINTER(C.c_double)]),
         "sx_domain_halo_layout": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, vp, vp]),
+        "sx_turb_default_settings": (C.c_int, [C.POINTER(SxTurbSettings)]),
+        "sx_turb_create": (C.c_int, [C.POINTER(vp), C.POINTER(SxTurbSettings)]),
+        "sx_turb_destroy": (None, [vp]),
+        "sx_turb_num_modes": (C.c_uint64, [vp]),
+        "sx_turb_get_scalars": (C.c_int, [vp, C.POINTER(C.c_double)]),
+        "sx_turb_get_arrays": (C.c_int, [vp, vp, vp, vp]),
+        "sx_turb_get_rng": (C.c_int64, [vp, C.c_char_p, sz]),
+        "sx_turb_set_state": (C.c_int, [vp, C.POINTER(C.c_double), C.c_uint64, vp, vp, vp, C.c_char_p]),
+        "sx_turb_max_index": (C.c_int, [vp]),
+        "sx_turb_fast_limit": (C.c_int, []),
+        "sx_turb_update_noise": (C.c_int, [vp, C.c_double]),
+        "sx_turb_compute_phases": (C.c_int, [vp, vp, vp]),
+        "sx_stir": (C.c_int, [vp, C.POINTER(SxGroups), C.POINTER(SxFields), vp]),
+        "sx_stir_device": (C.c_int, [vp, C.POINTER(SxGroups), C.POINTER(SxFields), C.c_uint64, vp, vp, vp, vp,
+                                     C.c_double]),
+        "sx_sim_set_turbulence": (C.c_int, [vp, C.POINTER(SxTurbSettings)]),
+        "sx_sim_turbulence": (C.c_int, [vp, C.POINTER(vp)]),
+        "sx_sim_set_turbulence_state": (C.c_int, [vp, C.POINTER(C.c_double), C.c_uint64, vp, vp, vp, C.c_char_p]),
+        "sx_sim_turbulence_times": (C.c_int, [vp, C.POINTER(C.c_float)]),
     }
     for name, (res, args) in sig.items():
         # a measurement build named by SPHEXA_AMD_LIB (an A/B against an older library) may predate an entry
@@ -315,6 +351,114 @@ def reference_attributes(params, box, scalars, iteration, num_particles_global):
 
 class SxError(RuntimeError):
     pass
+
+
+# the step attributes TurbulenceData::loadOrStore writes (turbulence_data.hpp:92-115), in its order
+TURBULENCE_ATTRIBUTES = ["turbulence::variance", "turbulence::decayTime", "turbulence::solWeight",
+                         "turbulence::solWeightNorm", "turbulence::numModes", "turbulence::modes",
+                         "turbulence::amplitudes", "turbulence::phases", "rngEngineState"]
+
+
+class Turbulence:
+    """the host state of the turbulence stirring (sx_turb_*): sph::TurbulenceData (turbulence_data.hpp:46-184) with
+    createStirringModes, updateNoise (driver.hpp:80-92) and computePhases (phases.hpp:47-72).  Needs no GPU.
+    Turbulence(solWeight=..., rngSeed=..., ...) takes the fields of SxTurbSettings; a Sim hands out a borrowed one."""
+
+    def __init__(self, settings=None, _borrowed=None, **kw):
+        self.L = lib()
+        self.owned = _borrowed is None
+        if _borrowed is not None:
+            self.h = C.c_void_p(_borrowed)
+            return
+        self.settings = settings if settings is not None else SxTurbSettings(**kw)
+        self.h = C.c_void_p()
+        rc = self.L.sx_turb_create(C.byref(self.h), C.byref(self.settings))
+        if rc != SX_OK:
+            raise SxError(f"sx_turb_create: code {rc}: invalid settings")
+
+    def close(self):
+        if self.h and self.owned:
+            self.L.sx_turb_destroy(self.h)
+        self.h = None
+
+    @property
+    def num_modes(self):
+        return int(self.L.sx_turb_num_modes(self.h))
+
+    def scalars(self):
+        out = (C.c_double * 4)()
+        self.L.sx_turb_get_scalars(self.h, out)
+        return dict(zip(["variance", "decayTime", "solWeight", "solWeightNorm"], list(out)))
+
+    def arrays(self):
+        m = self.num_modes
+        modes, amp, ph = np.empty(3 * m), np.empty(m), np.empty(6 * m)
+        self.L.sx_turb_get_arrays(self.h, modes.ctypes.data, amp.ctypes.data, ph.ctypes.data)
+        return dict(modes=modes, amplitudes=amp, phases=ph)
+
+    def rng_state(self):
+        """the generator as operator<< on std::mt19937 writes it (the reference's rngEngineState)"""
+        n = self.L.sx_turb_get_rng(self.h, None, 0)
+        buf = C.create_string_buffer(n + 1)
+        self.L.sx_turb_get_rng(self.h, buf, n + 1)
+        return buf.value.decode()
+
+    def state(self):
+        """everything TurbulenceData::loadOrStore saves, under its attribute names"""
+        sc, ar = self.scalars(), self.arrays()
+        d = {"turbulence::" + k: np.float64(v) for k, v in sc.items()}
+        d["turbulence::numModes"] = np.uint64(self.num_modes)
+        d.update({"turbulence::" + k: v for k, v in ar.items()})
+        d["rngEngineState"] = np.frombuffer(self.rng_state().encode(), dtype=np.uint8).copy()
+        return {k: d[k] for k in TURBULENCE_ATTRIBUTES}
+
+    @staticmethod
+    def _state_args(state):
+        sc = (C.c_double * 4)(*[float(np.asarray(state["turbulence::" + k]).ravel()[0])
+                                for k in ("variance", "decayTime", "solWeight", "solWeightNorm")])
+        m = int(np.asarray(state["turbulence::numModes"]).ravel()[0])
+        arr = [np.ascontiguousarray(np.atleast_1d(state["turbulence::" + k]), dtype=np.float64)
+               for k in ("modes", "amplitudes", "phases")]
+        if [a.size for a in arr] != [3 * m, m, 6 * m]:
+            raise ValueError("turbulence state: array sizes do not match numModes")
+        rng = state.get("rngEngineState")
+        if rng is not None and not isinstance(rng, (bytes, str)):
+            rng = np.atleast_1d(rng).astype(np.uint8).tobytes()
+        if isinstance(rng, str):
+            rng = rng.encode()
+        if rng is not None:
+            rng = rng.split(b"\0")[0]
+        return sc, m, arr, rng
+
+    def _own(self, what):
+        if not self.owned:
+            raise SxError(f"Turbulence.{what}: this is a Sim's state, a host copy of what the device holds; "
+                          "change it with Sim.set_turbulence_state")
+
+    def set_state(self, state):
+        self._own("set_state")
+        sc, m, arr, rng = self._state_args(state)
+        rc = self.L.sx_turb_set_state(self.h, sc, m, *[a.ctypes.data for a in arr], rng)
+        if rc != SX_OK:
+            raise SxError(f"sx_turb_set_state: code {rc}")
+
+    def max_index(self):
+        return int(self.L.sx_turb_max_index(self.h))
+
+    def update_noise(self, dt):
+        self._own("update_noise")
+        self.L.sx_turb_update_noise(self.h, float(dt))
+
+    def compute_phases(self):
+        m = self.num_modes
+        re, im = np.empty(3 * m), np.empty(3 * m)
+        self.L.sx_turb_compute_phases(self.h, re.ctypes.data, im.ctypes.data)
+        return re, im
+
+
+def stir(ctx, groups, fields, turb):
+    """sx_stir: the stirring accelerations of turb's current phases onto fields.ax, ay, az over the group view"""
+    ctx.check(ctx.L.sx_stir(ctx.h, C.byref(groups), C.byref(fields), turb.h), "sx_stir")
 
 
 class Context:
@@ -512,6 +656,7 @@ class Sim:
         self.params = params or default_params()
         self.box = box
         self.iteration = 0  # completed steps (the reference's "iteration" attribute)
+        self.stirred = False  # set_turbulence was called: checkpoints carry the turbulence state
         self.h = C.c_void_p()
         ctx.check(self.L.sx_sim_create(C.byref(self.h), ctx.h, int(capacity), C.byref(self.params), C.byref(box),
                                        bucket), "sx_sim_create")
@@ -522,6 +667,36 @@ class Sim:
     def set_comm(self, comm):
         self.comm = comm
         self.ctx.check(self.L.sx_sim_set_comm(self.h, comm.h), "set_comm")
+
+    def set_turbulence(self, settings=None, **kw):
+        """stir every following step (sx_sim_set_turbulence: TurbVeProp, VE propagator on one rank); settings: an
+        SxTurbSettings, or its fields as keywords"""
+        self.turb_settings = settings if settings is not None else SxTurbSettings(**kw)
+        self.ctx.check(self.L.sx_sim_set_turbulence(self.h, C.byref(self.turb_settings)), "set_turbulence")
+        self.stirred = True
+
+    def turbulence(self):
+        """the sim's turbulence state as a borrowed Turbulence (sx_sim_turbulence: synchronises, brings the device
+        phases back); valid until the sim is closed"""
+        p = C.c_void_p()
+        self.ctx.check(self.L.sx_sim_turbulence(self.h, C.byref(p)), "turbulence")
+        return Turbulence(_borrowed=p.value)
+
+    def turbulence_state(self):
+        """what TurbulenceData::loadOrStore saves (Turbulence.state) of the running sim"""
+        return self.turbulence().state()
+
+    def set_turbulence_state(self, state):
+        """restart: restore Turbulence.state and upload it (sx_sim_set_turbulence_state)"""
+        sc, m, arr, rng = Turbulence._state_args(state)
+        self.ctx.check(self.L.sx_sim_set_turbulence_state(self.h, sc, m, *[a.ctypes.data for a in arr], rng),
+                       "set_turbulence_state")
+
+    def turbulence_times(self):
+        """device ms of the last step's noise advance and stirring kernel (sx_sim_turbulence_times)"""
+        out = (C.c_float * 2)()
+        self.ctx.check(self.L.sx_sim_turbulence_times(self.h, out), "turbulence_times")
+        return dict(noise=out[0], stirring=out[1])
 
     def set_overlap(self, on):
         self.ctx.check(self.L.sx_sim_set_overlap(self.h, int(bool(on))), "set_overlap")
@@ -581,6 +756,8 @@ class Sim:
         if bdt:  # Timestep::loadOrStore(writer, "ts::") (sph/timestep.h:29-33, HydroVeBdtProp::save)
             attrs["ts::numRungs"] = np.int32(ts["numRungs"])
             attrs["ts::dt_m1"] = np.array(ts["dt_m1"], dtype=np.float32)
+        if self.stirred:  # TurbVeProp::save (turb_ve.hpp:121): TurbulenceData::loadOrStore
+            attrs.update(self.turbulence_state())
         if str(path).endswith(".h5"):
             from . import h5part
 
@@ -611,6 +788,8 @@ class Sim:
                 fields = {k: f.read_field(k, DTYPES.get(k, np.uint64)) for k in names if f.field_info(k) is not None}
             types = {k: np.asarray(v).dtype for k, v in mine.items()}
             types.update({"ts::numRungs": np.int32, "ts::dt_m1": np.float32, "ttot": np.float64})
+            types.update({k: np.float64 for k in TURBULENCE_ATTRIBUTES})
+            types.update({"turbulence::numModes": np.uint64, "rngEngineState": np.uint8})
             _, attrs = h5part.read_step(path, {}, {k: t for k, t in types.items() if k in present}, step)
             return {**fields, **attrs}
         with np.load(path, allow_pickle=False) as d:
@@ -643,6 +822,13 @@ class Sim:
                 ts.dt_m1[k] = float(v)
             self._keep_rung = rung
             self.ctx.check(self.L.sx_sim_set_timestep(self.h, C.byref(ts), rung.ctypes.data), "set_timestep")
+        if "turbulence::numModes" in d:
+            if not self.stirred:
+                raise ValueError("restart file carries a turbulence state (turbulence::*) but this Sim is not stirred: "
+                                 "call set_turbulence before load_checkpoint")
+            # TurbVeProp::load (turb_ve.hpp:123-135); a file without the attributes keeps the state of set_turbulence,
+            # as the reference's optional attributes do
+            self.set_turbulence_state(d)
         self.iteration = int(d["iteration"]) if "iteration" in d else 0
         t = float(d["time"] if "time" in d else d["ttot"])
         self.ctx.check(self.L.sx_sim_set_time(self.h, t), "set_time")

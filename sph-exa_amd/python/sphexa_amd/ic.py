@@ -56,6 +56,36 @@ def noh(side):
     return f, [lo, hi, lo, hi, lo, hi], [0, 0, 0], 1e-4
 
 
+#: TurbulenceConstants() (main/src/init/turbulence_init.hpp:48-71): the entries that are parameters of a Sim
+TURBULENCE_CONSTANTS = dict(gamma=1.001, muiConst=0.62, Kcour=0.4, ng0=100, ngmax=150)
+
+
+def turbulence_params(params):
+    """`params` (an SxParams) with TURBULENCE_CONSTANTS applied, as the reference's settings set the ParticlesData
+    attributes of a turbulence run"""
+    for k, v in TURBULENCE_CONSTANTS.items():
+        setattr(params, k, v)
+    return params
+
+
+def turbulence(side, Lbox=1.0, mTotal=1.0, u0=1000.0):
+    """Subsonic driven turbulence (turbulence_init.hpp:75-97 field values, initTurbulenceHydroFields): side^3 particles
+    at rest in the periodic cube [-L/2, L/2)^3, m = mTotal/N, T = u0/cv with gamma = 1.001 and mui = 0.62, alpha =
+    alphamin, h from ng0 = 100, dt0 = 1e-4.  The reference replicates a glass block (TurbulenceGlass, --glass) that is
+    not available offline; a cell-centred lattice stands in for it.  Run with turbulence_params(default_params()) and
+    Sim.set_turbulence(Lbox=Lbox).  Returns (arrays, box limits, boundary, dt0)."""
+    r = 0.5 * Lbox
+    x, y, z = _lattice(side, r)
+    n = x.size
+    f = _fields(n)
+    f["x"], f["y"], f["z"] = x, y, z
+    f["m"][:] = np.float32(mTotal / n)
+    f["h"][:] = np.float32(np.cbrt(3.0 / (4.0 * math.pi) * TURBULENCE_CONSTANTS["ng0"] * Lbox ** 3 / n) * 0.5)
+    cv = ideal_gas_cv(np.float32(TURBULENCE_CONSTANTS["muiConst"]), TURBULENCE_CONSTANTS["gamma"])
+    f["temp"] = np.full(n, u0 / np.float64(cv))
+    return f, [-r, r, -r, r, -r, r], [1, 1, 1], 1e-4
+
+
 def evrard(side):
     """Evrard collapse (evrard_init.hpp:50-108 field values): lattice in [-1,1]^3 cut to 0 < r <= 1 and contracted by
     sqrt(r) to a 1/r density profile; m = 1/N, u0 = 0.05, h from the 1/r concentration, G = 1, dt0 = 1e-4; open box
