@@ -198,6 +198,18 @@ double sx_kernel_constant(void); /* K of the sinc^6 kernel, particles_data.hpp:3
 /*! host evaluation of the register-resident kernel W(v), dW/dv of the fast pair kernels (sx_kernel_poly.hpp), for
  *  checking it against the reference tables */
 int    sx_kernel_poly(const float* v, size_t n, float* w, float* dw);
+/*! packed12 cluster neighbor lists (sx_pack12.hpp): 12-bit union positions, eight per three words.  A cluster's lists
+ *  are packed12 when its union holds at most maxUnion entries, else u16 pairs.  Default: 4095, the largest value; 0
+ *  (every list u16) for a context with sx_set_exact(1), whose gather kernels decode one entry at a time.  Tests set it
+ *  to reach both formats with either variant (0xffffffff: back to the default).  It takes effect with the context's next search; an sx_sim reads it when
+ *  it is created. */
+int      sx_set_pack12_max(sx_ctx* ctx, uint32_t maxUnion);
+/*! host side of the format, for checking it: words per target of a row with up to ngmax entries; the cnt positions
+ *  pos[] (each < 4096) packed into 3 * ceil(cnt / 8) words (the last group's tail repeats the last position); the
+ *  first n entries of such a list */
+uint32_t sx_pack12_row_words(uint32_t ngmax);
+int      sx_pack12_pack(const uint32_t* pos, uint32_t cnt, uint32_t* words);
+int      sx_pack12_unpack(const uint32_t* words, uint32_t n, uint32_t* pos);
 int    sx_copy_tables(sx_ctx* ctx, float* wh_host, float* whd_host); /* 20000-entry f32 tables */
 int    sx_synchronize(sx_ctx* ctx);
 

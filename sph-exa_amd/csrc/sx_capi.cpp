@@ -116,6 +116,7 @@ struct sx_ctx
     hipStream_t own{nullptr};
     hipStream_t stream{nullptr};
     bool        exact{false};
+    int         packMaxSet{-1}; // sx_set_pack12_max's value; -1: the default (packMax())
     Arena       arena;
     float2*     wh{nullptr};
     float2*     whd{nullptr};
@@ -138,6 +139,10 @@ struct sx_ctx
     uint32_t powTabNg0{0};
 
     const HydroLaunch& hydro() const { return exact ? hydro_exact() : hydro_fast(); }
+    //! largest union count whose lists the next search packs (sx_pack12.hpp).  The exact variant's gather kernels
+    //! decode one entry at a time, and two-word packed12 entries cost them 3 % (Sedov 64M --exact, A/B): an exact
+    //! context keeps u16 lists unless sx_set_pack12_max says otherwise
+    uint32_t packMax() const { return packMaxSet >= 0 ? (uint32_t)packMaxSet : (exact ? 0u : p12::kPack12Max); }
 };
 
 //! updateH's pow factor for every nc < kPowTable, computed with the host libm powf the reference calls
@@ -179,6 +184,31 @@ extern "C"
     const float2* sx_ctx_table_internal(sx_ctx* c, int which) { return which ? c->whd : c->wh; }
     const float*  sx_ctx_powtab_internal(sx_ctx* c, uint32_t ng0) { return ensurePowTab(c, ng0); }
     void          sx_ctx_set_error_internal(sx_ctx* c, const char* msg) { fail(c, SX_ERR_ARG, msg); }
+    uint32_t      sx_ctx_pack12_max_internal(sx_ctx* c) { return c->packMax(); }
+
+    int sx_set_pack12_max(sx_ctx* c, uint32_t maxUnion)
+    {
+        if (maxUnion > p12::kPack12Max && maxUnion != 0xffffffffu)
+            return fail(c, SX_ERR_ARG, "sx_set_pack12_max: at most 4095 (or 0xffffffff: the default)");
+        c->packMaxSet = maxUnion == 0xffffffffu ? -1 : (int)maxUnion; // read by the next search (its lists carry the value they were written with)
+        return SX_OK;
+    }
+
+    uint32_t sx_pack12_row_words(uint32_t ngmax) { return p12::rowWords(ngmax); }
+
+    int sx_pack12_pack(const uint32_t* pos, uint32_t cnt, uint32_t* words)
+    {
+        for (uint32_t g = 0; g < p12::groups(cnt); ++g)
+            p12::packGroup(pos + p12::kGroup * g, std::min(p12::kGroup, cnt - p12::kGroup * g), words + p12::kWords * g);
+        return SX_OK;
+    }
+
+    int sx_pack12_unpack(const uint32_t* words, uint32_t n, uint32_t* pos)
+    {
+        for (uint32_t k = 0; k < n; ++k)
+            pos[k] = p12::get(words + p12::kWords * (k / p12::kGroup), k % p12::kGroup);
+        return SX_OK;
+    }
 
     int sx_kernel_poly(const float* v, size_t n, float* w, float* dw)
     {
@@ -439,6 +469,7 @@ extern "C"
         a.hitMasks       = c->arena.get<uint64_t>("ns.masks", searchScratchBytes() / sizeof(uint64_t));
         if (!c->nb.reserve(c->arena, first, last, p->ngmax, true) || !a.powTab || !a.clStats || !a.work || !a.hitMasks)
             return fail(c, SX_ERR_NOMEM, "neighbor list allocation failed");
+        c->nb.packMax = c->packMax();
         a.setLists(c->nb);
         SX_HIP(c, hipMemsetAsync(c->stats, 0, kStatsWords * 4, c->stream));
         SX_HIP(c, findNeighbors(a, c->stream));
@@ -563,6 +594,7 @@ PairArgs pairArgs(sx_ctx* c, const sx_groups* g, const sx_fields* f, const sx_pa
     a.uni            = c->nb.uni;
     a.ucount         = c->nb.ucount;
     a.ucap           = c->nb.ucap;
+    a.packMax        = c->nb.packMax;
     a.nc             = f->nc;
     a.rx             = r.rx;
     a.rv             = r.rv;

@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sx_pack12.hpp"
+
 namespace sx
 {
 
@@ -22,8 +24,12 @@ constexpr int kGroupSize  = 64;    // particles per neighbor-list block = one wa
 constexpr int kClusterWaves = 4;   // groups per cluster = waves per cluster workgroup
 constexpr int kCluster      = kGroupSize * kClusterWaves; // particles sharing one neighbor union
 
-//! words of u16 cluster-local neighbor positions per target (two per word)
-__host__ __device__ constexpr uint32_t nlocWords(uint32_t ngmax) { return (ngmax + 1) / 2; }
+//! words of cluster-local neighbor positions per target: u16 pairs (two per word) or packed12 groups (sx_pack12.hpp:
+//! eight per three words), whichever needs more (the u16 pairs from ngmax = 11 on)
+__host__ __device__ constexpr uint32_t nlocWords(uint32_t ngmax)
+{
+    return (ngmax + 1) / 2 > 3 * ((ngmax + 7) / 8) ? (ngmax + 1) / 2 : 3 * ((ngmax + 7) / 8);
+}
 //! union capacity per cluster: every union entry is a stored neighbor of at least one of its targets
 __host__ __device__ constexpr uint32_t unionCap(uint32_t ngmax) { return kCluster * ngmax; }
 

@@ -46,8 +46,17 @@ constexpr bool kFastClusters = SX_STR(SX_VARIANT)[0] == 'f';
                                       : a.nidx + (size_t)gw * a.ngmax * kWave + lane;                                 \
     const uint32_t* un = a.localLists ? a.uni + (size_t)(gw / kClusterWaves) * a.ucap + (lB ? a.lb.uoff : 0u)        \
                                       : nullptr;                                                                       \
+    const bool p12l = a.localLists && gw < a.numGroups &&                                                             \
+                      (lB ? a.lb.ucount : a.ucount)[gw / kClusterWaves] <= a.packMax; /* packed12 (sx_pack12.hpp) */   \
     auto nbj = [&](unsigned k) -> uint32_t {                                                                           \
         if (!a.localLists) return nb[(size_t)k * kWave];                                                               \
+        if (p12l)                                                                                                      \
+        {                                                                                                              \
+            const uint32_t  b = p12::kBits * (k & 7u), t = b >> 5; /* the entry's bits start in word t */             \
+            const uint32_t* q = nb + (size_t)(k >> 3) * (p12::kWords * kWave) + (p12::kWords - 1) * lane + t;          \
+            const uint64_t  v = (uint64_t)q[0] | ((uint64_t)q[t < 2 ? 1 : 0] << 32);                                   \
+            return un[(uint32_t)(v >> (b & 31u)) & 0xfffu];                                                            \
+        }                                                                                                              \
         uint32_t w = nb[(size_t)(k >> 1) * kWave];                                                                     \
         return un[(k & 1) ? (w >> 16) : (w & 0xffffu)];                                                                \
     };

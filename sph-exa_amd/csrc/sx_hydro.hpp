@@ -29,7 +29,8 @@ struct PairArgs
 {
     uint32_t first, last, numGroups, ngmax;
     // neighbor lists (NbLists, sx_tree.hpp): global nidx[group][k][lane], or, with localLists, the cluster unions
-    // uni[cluster*ucap + u] (ucount[cluster] entries) and u16 positions nloc[group][k/2][lane]
+    // uni[cluster*ucap + u] (ucount[cluster] entries) and positions into it in the group's row of nloc: packed12
+    // (sx_pack12.hpp) where ucount[cluster] <= packMax, else u16 pairs [k/2][lane]
     int             localLists;
     const uint32_t* nidx;
     const uint32_t* nloc;
@@ -37,6 +38,7 @@ struct PairArgs
     const uint32_t* ucount;
     uint32_t        ucap;
     ListsB          lb;   // the second set of cluster lists (sx_device.hpp); lb.sel == nullptr: none
+    uint32_t        packMax; // cluster lists whose union count is at most this are packed12 (sx_pack12.hpp), else u16
     const uint32_t* nc;   // includes self
     const RecX*     rx;
     const RecV*     rv;

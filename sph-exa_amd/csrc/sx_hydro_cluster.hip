@@ -4,18 +4,19 @@
  *
  * One 256-thread workgroup per 256-particle SFC cluster (four wave64 groups, one lane per target).  The neighbor
  * search (sx_neighbors.hip) leaves, per cluster, the UNION of its targets' neighbors (uni[], typically 6-7 entries
- * per target instead of ~120 per target) and, per target, u16 positions into it, two per word, lane-interleaved.
+ * per target instead of ~120 per target) and, per target, its neighbors as positions into it: packed12 (12 bits each,
+ * eight per three words, sx_pack12.hpp) where the union holds at most PairArgs::packMax entries, else u16 pairs.
  *
  *   1. stage: the workgroup gathers the union's packed records (coalesced runs: the union is in leaf order) and
  *      writes one compact LDS record per union entry: positions relative to the cluster origin (minimum image,
  *      folded in double, rounded to float) plus the per-kernel neighbor fields, derived quantities precomputed
  *      (vol = xm/kx, rho = kx*m/xm, 1/h, m/rho);
- *   2. each lane walks its position list (one coalesced 256-B word load per two neighbors, prefetched four words
- *      ahead) and reads its neighbors' records from LDS (ds_read_b128); the SPH kernel W(v) = sinc(pi v/2)^6 and
+ *   2. each lane walks its position list (one 12-byte group load per eight neighbors, 768 contiguous bytes per wave,
+ *      prefetched a group ahead) and reads its neighbors' records from LDS (ds_read_b128); the SPH kernel W(v) = sinc(pi v/2)^6 and
  *      dW/dv are evaluated in registers with a degree-6 polynomial in v^2 (|error| < 2e-7 over [0,2), the same
  *      order as the reference's 20000-point table interpolation), so the inner loop touches no global memory;
- *   3. unions larger than the LDS capacity CH are processed in CH-sized chunks, every lane advancing through its
- *      sorted position list chunk by chunk.
+ *   3. unions larger than the LDS capacity CH, and unions whose lists are u16, are processed in CH-sized chunks, every
+ *      lane advancing through its sorted position list (either format) chunk by chunk.
  *
  * The per-pair arithmetic follows the reference kernels (citations per kernel) in float with FMA contraction and
  * reciprocal multiplies; results agree with the CPU reference to float rounding (tests/test_gpu_parity.py states
@@ -23,6 +24,7 @@
  */
 #include "sx_hydro.hpp"
 #include "sx_kernel_poly.hpp"
+#include "sx_pack12.hpp"
 #include "sx_traverse.hpp"
 
 namespace sx
@@ -45,11 +47,12 @@ struct Clu
     uint32_t        c, gw, i, iSafe, U;
     bool            valid;
     unsigned        cnt;        // this target's stored neighbors
-    uint32_t        wBeg, wEnd; // this wave's share of the target's list words (split-K over the wave's part)
+    uint32_t        gBeg, gEnd; // this wave's share of the target's list, in groups of 8 entries (split-K)
+    bool            packed;     // the cluster's lists are packed12 (sx_pack12.hpp), else u16 pairs
     int             part;       // which share: 0 .. SPLIT-1
     int             tid;        // target slot within the cluster: 0 .. 255
     const uint32_t* un;         // union of this cluster
-    const uint32_t* nl;         // this lane's position words, stride 64
+    const uint32_t* nl;         // this lane's list: packed12 groups (3 words, stride 192) or u16 words (stride 64)
     double          ox, oy, oz;
     bool            pbc; // positions need the applyPBC rule after folding (tiny periodic boxes)
 };
@@ -73,7 +76,7 @@ __device__ __forceinline__ float relc(double x, double o, const DevBox& b, int k
 
 //! sets up the cluster and decides (workgroup-uniformly) whether folded coordinates are minimum-image for every
 //! neighbor pair: |x_i - o| + 2 h_i < L/2 on every periodic axis.  With SPLIT > 1 the workgroup has SPLIT waves per
-//! group: wave w serves group w % 4 and takes the words [wBeg, wEnd) of share w / 4 of every lane's list.
+//! group: wave w serves group w % 4 and takes the groups [gBeg, gEnd) of share w / 4 of every lane's list.
 template<int SPLIT>
 __device__ __forceinline__ Clu setup(const PairArgs& a, float* s_red)
 {
@@ -95,13 +98,15 @@ __device__ __forceinline__ Clu setup(const PairArgs& a, float* s_red)
         unsigned c1 = a.nc[cu.i] - 1;
         cu.cnt      = c1 < a.ngmax ? c1 : a.ngmax;
     }
-    const uint32_t nw = (cu.cnt + 1) >> 1;
-    cu.wBeg           = nw * cu.part / SPLIT;
-    cu.wEnd           = nw * (cu.part + 1) / SPLIT;
+    const uint32_t ng = p12::groups(cu.cnt);
+    cu.gBeg           = ng * cu.part / SPLIT;
+    cu.gEnd           = ng * (cu.part + 1) / SPLIT;
     const bool lB     = listsB(a.lb, cu.c); // the cluster's current set of lists
     cu.U              = lB ? a.lb.ucount[cu.c] : a.ucount[cu.c];
+    cu.packed         = cu.U <= a.packMax;
     cu.un             = a.uni + (size_t)cu.c * a.ucap + (lB ? a.lb.uoff : 0u);
-    cu.nl             = (lB ? a.lb.nloc : a.nloc) + (size_t)cu.gw * nlocWords(a.ngmax) * kWave + lane;
+    cu.nl             = (lB ? a.lb.nloc : a.nloc) + (size_t)cu.gw * nlocWords(a.ngmax) * kWave +
+            (cu.packed ? p12::kWords * lane : lane);
     const RecX o      = a.rx[c0];
     cu.ox = o.x, cu.oy = o.y, cu.oz = o.z;
 
@@ -151,8 +156,8 @@ __device__ __forceinline__ void combineShares(const Clu& cu, float (&v)[NV], flo
 
 /*! Run compute(load(p)) over this lane's share of its neighbors, p = LDS slot.  stage(j, slot) writes the record
  *  of particle j.  `resident` carries "the whole union is already in LDS" from a previous pass over the same records.
- *  With the union resident the loop is software-pipelined: the LDS records of the next two neighbors (one list
- *  word) are read while the current two are computed, and list words are prefetched four ahead. */
+ *  With the union resident (and the lists packed12) the loop is software-pipelined: the LDS records of the next
+ *  neighbors are read while the current ones are computed, and list groups are prefetched one ahead. */
 template<int CH, int SPLIT, bool PF = true, bool LEAN = false, class Stage, class Load, class Compute>
 __device__ __forceinline__ void neighborLoop(const Clu& cu, Stage&& stage, Load&& load, Compute&& compute,
                                              bool& resident)
@@ -175,7 +180,7 @@ __device__ __forceinline__ void neighborLoop(const Clu& cu, Stage&& stage, Load&
         }
     };
 
-    if (cu.U <= (uint32_t)CH)
+    if (cu.U <= (uint32_t)CH && cu.packed)
     {
         if (!resident)
         {
@@ -183,88 +188,114 @@ __device__ __forceinline__ void neighborLoop(const Clu& cu, Stage&& stage, Load&
             __syncthreads();
             resident = true;
         }
-        const uint32_t wBeg = cu.wBeg, wEnd = cu.wEnd;
-        if (wBeg >= wEnd) return;
-        const uint32_t* nl = cu.nl;
-        if constexpr (LEAN)
+        const uint32_t gBeg = cu.gBeg, gEnd = cu.gEnd;
+        if (gBeg >= gEnd) return;
+        // One iteration per packed12 group: eight entries decoded with immediate bit offsets.  Groups beyond the share
+        // re-read its last group (always in bounds), and the tail entries of a list's last group repeat its last
+        // position: their records are read, never computed.  The next group's three words load one group ahead.
+        const uint32_t gLast = gEnd - 1;
+        struct Grp
+        {
+            uint32_t a, b, c;
+        };
+        auto ldg = [&](uint32_t g) {
+            const uint32_t* p = cu.nl + (size_t)min(g, gLast) * (p12::kWords * kWave);
+            return Grp{p[0], p[1], p[2]};
+        };
+#define SX_P12(E, G) p12::get<E>((G).a, (G).b, (G).c)
+        uint32_t g = gBeg;
+        if constexpr (LEAN || !PF)
         {
             // one record in flight while the other is computed: the LDS read latency (~100 cycles) is far below a
             // heavy pair's compute, and half the record registers let one more wave per SIMD in (momentum 152 -> 128
-            // VGPRs).  List words beyond the share re-read its last word; their records are read, never computed.
-            const uint32_t wLast = wEnd - 1;
-            auto           ld    = [&](uint32_t w) { return nl[(size_t)min(w, wLast) * kWave]; };
-            // list words prefetched SX_LEAN_DEPTH ahead (the list streams from HBM: a load's latency under load
-            // spans several heavy pairs)
-            constexpr int  D = SX_LEAN_DEPTH;
-            uint32_t       q[D];
-#pragma unroll
-            for (int d = 0; d < D; ++d)
-                q[d] = ld(wBeg + 1 + d);
-            uint32_t       wd = nl[(size_t)wBeg * kWave];
-            auto           ra = load(wd & 0xffffu);
-            for (uint32_t w = wBeg;;)
+            // VGPRs).  Each word of the next group loads into the register of the word just used up (five entries or
+            // more ahead of its first use), so the list holds three registers.
+            // rem: the share's entries from the current group on (its last group may be the list's partly filled one)
+            const uint32_t* pc  = cu.nl + (size_t)gBeg * (p12::kWords * kWave);
+            uint32_t        rem = min(cu.cnt, p12::kGroup * gEnd) - p12::kGroup * gBeg;
+            uint32_t        w0 = pc[0], w1 = pc[1], w2 = pc[2];
+            auto            r0 = load(p12::get<0>(w0, w1, w2));
+            while (true)
             {
-                const auto rb = load(wd >> 16);
-                compute(ra);
-                const bool odd = 2 * w + 1 < cu.cnt;
-                wd             = q[0];
-#pragma unroll
-                for (int d = 0; d + 1 < D; ++d)
-                    q[d] = q[d + 1];
-                q[D - 1] = ld(w + 1 + D);
-                ra             = load(wd & 0xffffu);
-                if (odd) compute(rb);
-                if (++w >= wEnd) break;
+                pc += rem > p12::kGroup ? p12::kWords * kWave : 0; // the next group; the share's last one again
+                auto r1 = load(p12::get<1>(w0, w1, w2));
+                compute(r0);
+                const uint32_t p2 = p12::get<2>(w0, w1, w2);
+                w0                = pc[0];
+                r0                = load(p2);
+                if (1 < rem) compute(r1);
+                r1 = load(p12::get<3>(w0, w1, w2));
+                if (2 < rem) compute(r0);
+                r0 = load(p12::get<4>(w0, w1, w2));
+                if (3 < rem) compute(r1);
+                const uint32_t p5 = p12::get<5>(w0, w1, w2);
+                w1                = pc[1];
+                r1                = load(p5);
+                if (4 < rem) compute(r0);
+                r0 = load(p12::get<6>(w0, w1, w2));
+                if (5 < rem) compute(r1);
+                const uint32_t p7 = p12::get<7>(w0, w1, w2);
+                w2                = pc[2];
+                r1                = load(p7);
+                if (6 < rem) compute(r0);
+                r0 = load(p12::get<0>(w0, w1, w2));
+                if (7 < rem) compute(r1);
+                if (rem <= p12::kGroup) break;
+                rem -= p12::kGroup;
             }
             return;
         }
-        // PF: list words beyond the share read the share's last word again (always in bounds) and every prefetch
-        // below is unconditional, so the LDS reads of the next pair are issued on one path and the wait before a
-        // computation covers only the records it consumes (a masked prefetch leaves a path on which the previous
-        // pair's reads may still be outstanding, and the merged wait then also waits for the new reads).  Measured
-        // (Sedov 64M): IAD -0.4 ms, AV -0.3 ms; momentum +0.3..0.7 ms (its records are 80 B: the extra registers of
-        // the unmasked form cost more than the wait), so momentum takes the LEAN form above (22.5 -> 21.5 ms).
-        const uint32_t  wLast = wEnd - 1;
-        auto            ld    = [&](uint32_t w) {
-            if constexpr (PF) return nl[(size_t)min(w, wLast) * kWave];
-            else return w < wEnd ? nl[(size_t)w * kWave] : 0u;
-        };
-        // two record buffers used alternately (2x unrolled, no register copies); list words prefetched ahead
-        uint32_t        q0 = ld(wBeg + 1), q1 = ld(wBeg + 2), q2 = ld(wBeg + 3);
-        const uint32_t  w0 = nl[(size_t)wBeg * kWave];
-        auto            a0 = load(w0 & 0xffffu); // slot 0 for a missing odd partner: valid, never computed
-        auto            b0 = load(w0 >> 16);
-        decltype(a0)    a1, b1;
-        uint32_t        w = wBeg;
+        Grp cur = ldg(gBeg), nx = ldg(gBeg + 1);
+        // PF: every prefetch is unconditional, so the LDS reads of the next pair are issued on one path and the wait
+        // before a computation covers only the records it consumes (a masked prefetch leaves a path on which the
+        // previous pair's reads may still be outstanding, and the merged wait then also waits for the new reads).
+        // Measured (Sedov 64M): IAD -0.4 ms, AV -0.3 ms; momentum +0.3..0.7 ms (its records are 80 B: the extra
+        // registers of the unmasked form cost more than the wait), so momentum takes the LEAN form above.
+        // Two pairs of record buffers used alternately (no register copies).
+        auto         a0 = load(SX_P12(0, cur));
+        auto         b0 = load(SX_P12(1, cur));
+        decltype(a0) a1, b1;
         while (true)
         {
-            if (PF || w + 1 < wEnd) // past the share's end (PF): a valid slot that is never computed
-            {
-                a1 = load(q0 & 0xffffu);
-                b1 = load(q0 >> 16);
-                q0 = ld(w + 4);
-            }
+            const uint32_t rem = cu.cnt - p12::kGroup * g;
+            a1 = load(SX_P12(2, cur));
+            b1 = load(SX_P12(3, cur));
             compute(a0);
-            if (2 * w + 1 < cu.cnt) compute(b0);
-            if (++w >= wEnd) break;
-            if (PF || w + 1 < wEnd)
-            {
-                a0 = load(q1 & 0xffffu);
-                b0 = load(q1 >> 16);
-                q1 = ld(w + 4);
-            }
-            compute(a1);
-            if (2 * w + 1 < cu.cnt) compute(b1);
-            if (++w >= wEnd) break;
-            const uint32_t t = q0;
-            q0 = q2, q2 = q1, q1 = t;
+            if (1 < rem) compute(b0);
+            a0 = load(SX_P12(4, cur));
+            b0 = load(SX_P12(5, cur));
+            if (2 < rem) compute(a1);
+            if (3 < rem) compute(b1);
+            a1 = load(SX_P12(6, cur));
+            b1 = load(SX_P12(7, cur));
+            if (4 < rem) compute(a0);
+            if (5 < rem) compute(b0);
+            a0 = load(SX_P12(0, nx));
+            b0 = load(SX_P12(1, nx));
+            if (6 < rem) compute(a1);
+            if (7 < rem) compute(b1);
+            cur = nx;
+            nx  = ldg(g + 2);
+            if (++g >= gEnd) break;
         }
+#undef SX_P12
     }
     else
     {
-        resident         = false;
-        uint32_t       k    = 2 * cu.wBeg;
-        const uint32_t kEnd = min(cu.cnt, 2 * cu.wEnd);
+        // unions beyond the LDS capacity, and u16 lists (unions beyond the packed12 threshold): chunk by chunk
+        resident            = false;
+        uint32_t       k    = p12::kGroup * cu.gBeg;
+        const uint32_t kEnd = min(cu.cnt, p12::kGroup * cu.gEnd);
+        auto           pos  = [&](uint32_t k) -> uint32_t {
+            if (cu.packed)
+            {
+                const uint32_t* p    = cu.nl + (size_t)(k >> 3) * (p12::kWords * kWave);
+                const uint32_t  w[3] = {p[0], p[1], p[2]};
+                return p12::get(w, k & 7u);
+            }
+            const uint32_t w = cu.nl[(size_t)(k >> 1) * kWave];
+            return (k & 1) ? (w >> 16) : (w & 0xffffu);
+        };
         for (uint32_t b0 = 0; b0 < cu.U; b0 += CH)
         {
             const uint32_t b1 = min(cu.U, b0 + (uint32_t)CH);
@@ -273,8 +304,7 @@ __device__ __forceinline__ void neighborLoop(const Clu& cu, Stage&& stage, Load&
             __syncthreads();
             while (k < kEnd)
             {
-                const uint32_t w = cu.nl[(size_t)(k >> 1) * kWave];
-                const uint32_t p = (k & 1) ? (w >> 16) : (w & 0xffffu);
+                const uint32_t p = pos(k);
                 if (p >= b1) break;
                 compute(load(p - b0));
                 ++k;
@@ -830,7 +860,8 @@ __global__ __launch_bounds__(kB * SPLIT) void momentumEnergyKernel(PairArgs a, u
     __shared__ float  s_red[kClusterWaves * SPLIT];
     using Pre                  = MePre<CH, SPLIT, AVC>;
     constexpr int  NT          = Pre::NT, S = Pre::S, SP = Pre::SP;
-    const int      wave        = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // (the wave index as a scalar: it and what follows from it hold no vector register over the kernel's lifetime)
+    const int      wave        = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int      sub         = wave & (kClusterWaves - 1);
     const int      part        = wave / kClusterWaves;
     const int      tid         = sub * kWave + lane;
@@ -912,12 +943,14 @@ __global__ __launch_bounds__(kB * SPLIT) void momentumEnergyKernel(PairArgs a, u
             const unsigned c1 = cur.nc - 1;
             cu.cnt            = c1 < a.ngmax ? c1 : a.ngmax;
         }
-        const uint32_t nw = (cu.cnt + 1) >> 1;
-        cu.wBeg           = nw * cu.part / SPLIT;
-        cu.wEnd           = nw * (cu.part + 1) / SPLIT;
+        const uint32_t ng = p12::groups(cu.cnt);
+        cu.gBeg           = ng * cu.part / SPLIT;
+        cu.gEnd           = ng * (cu.part + 1) / SPLIT;
         cu.U              = cur.U;
+        cu.packed         = cu.U <= a.packMax;
         cu.un             = a.uni + (size_t)cu.c * a.ucap + (cur.lB ? a.lb.uoff : 0u);
-        cu.nl             = (cur.lB ? a.lb.nloc : a.nloc) + (size_t)cu.gw * nlocWords(a.ngmax) * kWave + lane;
+        cu.nl             = (cur.lB ? a.lb.nloc : a.nloc) + (size_t)cu.gw * nlocWords(a.ngmax) * kWave +
+                (cu.packed ? p12::kWords * lane : lane);
         const RecX o      = cur.o;
         cu.ox = o.x, cu.oy = o.y, cu.oz = o.z;
         // lanes outside the view read the cluster's first particle, as setup<SPLIT> does

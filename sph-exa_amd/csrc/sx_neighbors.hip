@@ -24,7 +24,8 @@
  *   5. cluster lists: the union bitmap over the candidate space (OR-ed per chunk) is numbered by a prefix popcount:
  *      the UNION of the cluster's neighbors (uni[], candidate order = leaf runs); the chunk tables are translated to
  *      union positions and every lane expands its hit masks into its u16 list (ascending, which the chunked LDS
- *      staging of sx_hydro_cluster.hip relies on).
+ *      staging of sx_hydro_cluster.hip relies on); where the union holds at most NsArgs::packMax entries each wave
+ *      then converts its row to packed12 in place (sx_pack12.hpp: 12 bits per position, eight per three words).
  *
  * Deferred list expansion (step 5).  Appending a chunk's hits right after its test walks the chunk's hit masks in a
  * divergent loop whose trip count is the MAX over the wave's lanes of the hits in that chunk; a chunk is a compact
@@ -1044,6 +1045,42 @@ findNeighborsKernel(NsArgs a)
         // the last batch: union positions straight into the lists (the early entries' last pending half included)
         expandFinal();
         if (stored & 1u) ll[(size_t)(stored >> 1) * kWave] = pend;
+        // packed12 lists (sx_pack12.hpp) where the union allows: each wave converts its row in place, four groups a
+        // step.  Groups [g, g + 4) take the row's words [192 g, 192 g + 768) and come from the u16 words 4 g .. 4 g + 15
+        // of every lane (row words [256 g, 256 g + 1024)): a step's loads (each lane its own words) complete before
+        // any lane's stores, and its stores end below the next step's loads.
+        if (ucnt <= a.packMax)
+        {
+            constexpr uint32_t G     = 4;
+            uint32_t* const    row   = ll - lane;
+            const uint32_t     ngr   = p12::groups(stored);
+            const uint32_t     lastW = stored ? (stored - 1u) >> 1 : 0u;
+            __builtin_amdgcn_s_waitcnt(0); // the expansion's stores precede these loads
+            for (uint32_t g = 0; g < ngr; g += G)
+            {
+                uint32_t v[4 * G];
+#pragma unroll
+                for (uint32_t t = 0; t < 4 * G; ++t)
+                    v[t] = ll[(size_t)min(4 * g + t, lastW) * kWave];
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                __builtin_amdgcn_s_waitcnt(0);
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (uint32_t q = 0; q < G; ++q)
+                {
+                    if (g + q < ngr)
+                    {
+                        uint32_t p[8], w[3];
+#pragma unroll
+                        for (uint32_t t = 0; t < 4; ++t)
+                            p[2 * t] = v[4 * q + t] & 0xffffu, p[2 * t + 1] = v[4 * q + t] >> 16;
+                        p12::packGroup(p, min(8u, stored - 8 * (g + q)), w);
+                        uint32_t* const o = row + ((size_t)(g + q) * kWave + lane) * p12::kWords;
+                        storeList(o, w[0]), storeList(o + 1, w[1]), storeList(o + 2, w[2]);
+                    }
+                }
+            }
+        }
     }
 
     if (valid && !abandoned)
@@ -1098,9 +1135,21 @@ __global__ void exportKernel(NsArgs a, uint32_t* out)
         {
             if (a.localLists)
             {
-                const bool lB = listsB(a.lb, c);
-                uint32_t   w  = (lB ? a.lb.nloc : a.nloc)[((size_t)g * W + k / 2) * kWave + lane];
-                j = a.uni[(size_t)c * a.ucap + (lB ? a.lb.uoff : 0u) + ((k & 1) ? (w >> 16) : (w & 0xffffu))];
+                const bool      lB  = listsB(a.lb, c);
+                const uint32_t* row = (lB ? a.lb.nloc : a.nloc) + (size_t)g * W * kWave;
+                uint32_t        p;
+                if ((lB ? a.lb.ucount[c] : a.ucount[c]) <= a.packMax)
+                {
+                    const uint32_t* q    = row + ((size_t)(k >> 3) * kWave + lane) * p12::kWords;
+                    const uint32_t  w[3] = {q[0], q[1], q[2]};
+                    p                    = p12::get(w, k & 7u);
+                }
+                else
+                {
+                    const uint32_t w = row[(size_t)(k / 2) * kWave + lane];
+                    p                = (k & 1) ? (w >> 16) : (w & 0xffffu);
+                }
+                j = a.uni[(size_t)c * a.ucap + (lB ? a.lb.uoff : 0u) + p];
             }
             else { j = a.nidx[((size_t)g * a.ngmax + k) * kWave + lane]; }
         }

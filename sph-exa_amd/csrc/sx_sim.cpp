@@ -49,6 +49,7 @@ using namespace sx::sim;
 
 extern "C" void*          sx_ctx_stream_internal(sx_ctx* c);
 extern "C" int            sx_ctx_exact_internal(sx_ctx* c);
+extern "C" uint32_t       sx_ctx_pack12_max_internal(sx_ctx* c);
 extern "C" const float2*  sx_ctx_table_internal(sx_ctx* c, int which);
 extern "C" const float*   sx_ctx_powtab_internal(sx_ctx* c, uint32_t ng0);
 extern "C" sx::Transport* sx_comm_transport_internal(sx_comm* c);
@@ -711,6 +712,7 @@ PairArgs simPairArgs(sx_sim* s)
     a.uni            = s->nb.uni;
     a.ucount         = s->nb.ucount;
     a.ucap           = s->nb.ucap;
+    a.packMax        = s->nb.packMax;
     a.nc             = s->nc;
     a.rx             = s->rx;
     a.rv             = s->rv;
@@ -1836,6 +1838,7 @@ int skinSearch(sx_sim* s, const NsArgs& na, bool reuse, hipStream_t st, float* x
     // start
     const uint32_t uoff = na.ucap / 2;
     fa.nloc = na.nloc, fa.uni = na.uni, fa.ucount = na.ucount, fa.ucap = na.ucap, fa.uoff = uoff, fa.ucountS = ucS;
+    fa.packMax = na.packMax;
     fa.sloc = sloc, fa.scnt = scnt, fa.hb = hb, fa.rel = rel, fa.acc = acc, fa.cells = cells, fa.grid = g;
     fa.dispX = dx, fa.dispY = dy, fa.dispZ = dz;
     fa.xmOut = xmOut, fa.rtXm = rtXm, fa.K = s->p.K;
@@ -1857,6 +1860,7 @@ int skinSearch(sx_sim* s, const NsArgs& na, bool reuse, hipStream_t st, float* x
     b.skin1    = 1.0f + K.built;
     b.iterateH = 0;
     b.nloc     = sloc;
+    b.packMax  = 0; // the skin lists stay u16
     b.ngmax    = K.ngmaxS;
     b.nc       = scnt;
     b.rxOut    = nullptr;
@@ -2219,6 +2223,7 @@ extern "C"
         s->dbox   = toDevBox(box);
         s->bucket = bucketSize;
         s->cap    = capacity;
+        s->nb.packMax = sx_ctx_pack12_max_internal(ctx); // (sx_set_pack12_max: before the sim is created)
         allocFields(s, capacity);
         if (s->p.propagator == 2) allocBdt(s);
         if (s->mem.failed())

@@ -14,8 +14,9 @@
  *      bit-identical to findNeighbors; j != i by global index;
  *   4. lanes with nc outside [ng0/4, ngmax+1] update h and walk again (at most 10 updates, the CPU loop's bound); an
  *      updated h must stay within the skin, else the cluster is stale;
- *   5. h, nc, the targets' RecX and the exact lists (ascending positions into U_s, first ngmax in stream order) are
- *      written only by a cluster that completes;
+ *   5. h, nc, the targets' RecX and the exact lists (ascending ranks in the exact union, first ngmax in stream order;
+ *      packed12, sx_pack12.hpp, where that union holds at most SkinArgs::packMax entries, else u16 pairs) are written
+ *      only by a cluster that completes;
  *   4b. (round 6) a walk whose hit bits equal one of the cluster's two recorded list sets keeps that set (no 5), and a
  *      cluster whose freeze reference proves its hits unchanged is not walked (1b: the XMass over its exact lists).
  * This file is compiled with -ffp-contract=off (the double criterion must round like the reference).
@@ -391,7 +392,49 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4))) void sk
         (void)stage(setUnion(lcur), ue);
         count  = valid ? a.nc[i] - 1u : 0u;
         stored = min(count, a.ngmax);
-        if (a.xmOut && valid)
+        if (a.xmOut && valid && ue <= a.packMax)
+        {
+            // packed12 lists (sx_pack12.hpp): two groups (six words, 16 entries) per iteration, the next two loaded a
+            // block ahead, every load unconditional (clamped to the list's last group)
+            const float     hInv = 1.0f / hi, hInv2 = hInv * hInv;
+            const uint32_t  ngr = p12::groups(stored), lastG = ngr ? ngr - 1 : 0u;
+            const uint32_t* lp  = ll + (p12::kWords - 1) * lane;
+            constexpr int   PW  = 2 * p12::kWords;
+            auto            lw  = [&](uint32_t g0, int u) {
+                return lp[(size_t)min(g0 + u / p12::kWords, lastG) * (p12::kWords * kWave) + u % p12::kWords];
+            };
+            uint32_t nx[PW];
+#pragma unroll
+            for (int u = 0; u < PW; ++u)
+                nx[u] = lw(0, u);
+            for (uint32_t g0 = 0; g0 < ngr; g0 += 2)
+            {
+                uint32_t cw[PW];
+#pragma unroll
+                for (int u = 0; u < PW; ++u)
+                {
+                    cw[u] = nx[u];
+                    nx[u] = lw(g0 + 2, u);
+                }
+#pragma unroll
+                for (int h2 = 0; h2 < 2; ++h2)
+                {
+                    const uint32_t w0 = cw[3 * h2], w1 = cw[3 * h2 + 1], w2 = cw[3 * h2 + 2];
+                    const uint32_t pos[8] = {p12::get<0>(w0, w1, w2), p12::get<1>(w0, w1, w2), p12::get<2>(w0, w1, w2),
+                                             p12::get<3>(w0, w1, w2), p12::get<4>(w0, w1, w2), p12::get<5>(w0, w1, w2),
+                                             p12::get<6>(w0, w1, w2), p12::get<7>(w0, w1, w2)};
+#pragma unroll
+                    for (uint32_t e = 0; e < 8; ++e)
+                    {
+                        const float4 q  = s_rec[min(pos[e], (uint32_t)kSkinCap - 1u)];
+                        const float  dx = q.x - xr, dy = q.y - yr, dz = q.z - zr;
+                        const float  r2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+                        rho0 += keepOrZero(kernelWt(r2 * hInv2) * q.w, 8 * (g0 + h2) + e < stored);
+                    }
+                }
+            }
+        }
+        else if (a.xmOut && valid)
         {
             const float    hInv = 1.0f / hi, hInv2 = hInv * hInv;
             const uint32_t nw = (stored + 1) >> 1, last = nw ? nw - 1 : 0u;
@@ -667,8 +710,42 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4))) void sk
         }
         __syncthreads();
     }
-    // pass B: the same walk, the first ngmax hits written as exact-union ranks (two per word); the hit bits recorded
-    if (!kept)
+    // pass B: the same walk, the first ngmax hits written as exact-union ranks (packed12 where the exact union allows,
+    // sx_pack12.hpp, else two per word); the hit bits recorded
+    if (!kept && ue <= a.packMax)
+    {
+        // the ranks stream through the word being filled, 12 bits each (nb: its bits in use); a full word goes to the
+        // next of the group's three words and the rank's bits that did not fit start the next word (8 entries = 96
+        // bits: the word is empty at every group boundary)
+        uint32_t* lw = setLists(ltgt) + (p12::kWords - 1) * lane; // word 0 of this lane's group 0
+        uint32_t  acc = 0, nb = 0, t = 0, n = 0, lastR = 0, bits = 0;
+        auto      push = [&](uint32_t r, bool keep) { // (one branch per entry, around the store)
+            acc |= keep ? r << nb : 0u;
+            nb += keep ? p12::kBits : 0u;
+            n += keep ? 1u : 0u;
+            if (nb >= 32u)
+            {
+                lw[t] = acc;
+                nb -= 32u;
+                acc = r >> (p12::kBits - nb);
+                if (++t == p12::kWords) t = 0, lw += p12::kWords * kWave;
+            }
+        };
+        walk([&](uint32_t b) { bits = s_bm[b][threadIdx.x]; },
+             [&](uint32_t p, int e, bool) {
+                 const bool keep = ((bits >> e) & 1u) != 0;
+                 lastR           = keep ? s_rank[p] : lastR;
+                 push(lastR, keep);
+             },
+             [](uint32_t) {});
+        while (n & (p12::kGroup - 1u)) // the last group's tail repeats the last rank
+            push(lastR, true);
+        if (uint32_t* const hm = setMask(ltgt))
+            for (uint32_t k = 0; 2 * k < nbl; ++k)
+                hm[(size_t)k * kWave] = maskWord(k);
+        if (threadIdx.x == 0) *setCount(ltgt) = ue;
+    }
+    else if (!kept)
     {
         uint32_t* const lw = setLists(ltgt);
         unsigned st = 0;

@@ -67,6 +67,7 @@ struct SkinArgs
     // exact lists and unions (output, the pair kernels' nloc / uni[c*ucap ...] / ucount) and the skin unions (input,
     // uni[c*ucap + uoff ...], ucountS[c] entries)
     uint32_t*       nloc;
+    uint32_t        packMax; // exact lists (nloc / nlocB) of a union of at most packMax entries are packed12 (sx_pack12.hpp)
     uint32_t*       uni;
     uint32_t*       ucount;
     uint32_t        ucap;

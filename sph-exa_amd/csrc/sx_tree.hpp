@@ -115,7 +115,7 @@ struct DevTree
     }
 };
 
-//! the neighbor lists of one search over [first, last): global u32 lists or cluster unions + u16 positions
+//! the neighbor lists of one search over [first, last): global u32 lists or cluster unions + positions into them
 struct NbLists
 {
     int       local{0};
@@ -124,6 +124,8 @@ struct NbLists
     uint32_t* nloc{nullptr};
     uint32_t* uni{nullptr};
     uint32_t* ucount{nullptr};
+    //! clusters whose union count is at most this hold packed12 lists (sx_pack12.hpp), the others u16 pairs
+    uint32_t  packMax{4095};
 
     size_t groups() const { return (size_t(last - first) + kGroupSize - 1) / kGroupSize; }
     size_t clusters() const { return (size_t(last - first) + kCluster - 1) / kCluster; }
@@ -201,14 +203,16 @@ struct NsArgs
     uint32_t*       nc;
     uint32_t*       nidx; // global lists [group][k][lane] (localLists == 0)
     // cluster lists (localLists == 1): per 256-particle cluster c, the union of its targets' neighbors
-    // uni[c*ucap + u] (global indices, stream order), ucount[c] = U, and per target the u16 positions into that
-    // union, two per word: nloc[(group*nlocWords + k/2)*64 + lane]
+    // uni[c*ucap + u] (global indices, stream order), ucount[c] = U, and per target the positions into that union in
+    // the group's row nloc + group*nlocWords*64: packed12 (sx_pack12.hpp) where U <= packMax, else u16, two per word,
+    // word k/2 at [(k/2)*64 + lane]
     int             localLists;
     ListsB          lb; // exportNeighbors only: the second set of cluster lists (sx_device.hpp)
     uint32_t*       nloc;
     uint32_t*       uni;
     uint32_t*       ucount;
     uint32_t        ucap;
+    uint32_t        packMax; // 0: every list u16 (the skin lists)
     // tree (OctreeNsView)
     const int32_t*  childOffsets;
     const int32_t*  internalToLeaf;
@@ -265,6 +269,7 @@ struct NsArgs
         uni        = L.uni;
         ucount     = L.ucount;
         ucap       = L.ucap;
+        packMax    = L.packMax;
     }
 };
 

@@ -142,6 +142,10 @@ def lib():
         "sx_kernel_constant": (C.c_double, []),
         "sx_copy_tables": (C.c_int, [vp, vp, vp]),
         "sx_kernel_poly": (C.c_int, [vp, C.c_size_t, vp, vp]),
+        "sx_set_pack12_max": (C.c_int, [vp, u32]),
+        "sx_pack12_row_words": (u32, [u32]),
+        "sx_pack12_pack": (C.c_int, [vp, u32, vp]),
+        "sx_pack12_unpack": (C.c_int, [vp, u32, vp]),
         "sx_synchronize": (C.c_int, [vp]),
         "sx_device_alloc": (vp, [vp, sz]),
         "sx_device_free": (C.c_int, [vp, vp]),
@@ -477,6 +481,12 @@ class Context:
 
     def set_exact(self, exact):
         self.L.sx_set_exact(self.h, 1 if exact else 0)
+
+    def set_pack12_max(self, max_union=None):
+        """cluster lists of unions up to max_union entries are packed12, larger ones u16 (None: the default, 4095, or
+        0 for an exact context; tests set it).  Takes effect with the next search; a Sim reads it when it is created."""
+        v = 0xffffffff if max_union is None else int(max_union)
+        self.check(self.L.sx_set_pack12_max(self.h, v), "sx_set_pack12_max")
 
     # ---- device arrays --------------------------------------------------------------------------------------
     def alloc(self, n, dtype):
