@@ -43,6 +43,9 @@
  *                                                               driver.hpp:80-92, phases.hpp:47-72, create_modes.hpp:59-244
  *   sx_stir                sph::computeStirringGpu              hydro_turb/stirring.hpp:123-126 (stirParticle :44-79)
  *   sx_sim_set_turbulence  TurbVeProp::computeForces            main/src/propagator/turb_ve.hpp:114-119
+ *   sx_observables         sphexa::gpuGrowthRate, machSquareSumGpu, survivorsGpu  main/src/observables/gpu_reductions.cu:69-168;
+ *                                                               d2QuadpoleMomentum grav_waves_calculations.hpp:87-121
+ *   sx_sim_observe         IObservables::computeAndWrite        main/src/observables/factory.hpp:46-69
  *   sx_sim_*               one HydroVeProp step (sync + computeForces + integrate), main/src/propagator/ve_hydro.hpp:132-218
  *
  * Conventions (reference semantics preserved):
@@ -341,6 +344,59 @@ int sx_max_divv(sx_ctx* ctx, uint32_t first, uint32_t last, const float* divv, f
 int sx_conserved_quantities(sx_ctx* ctx, const sx_fields* f, uint32_t first, uint32_t last, float muiConst,
                             double gamma, double out[9]);
 
+/*! the observables of observablesFactory (main/src/observables/factory.hpp:46-69) */
+#define SX_OBS_TIME_ENERGY 0 /* TimeAndEnergy, time_energies.hpp */
+#define SX_OBS_MACH_RMS 1    /* TurbulenceMachRMS, turbulence_mach_rms.hpp */
+#define SX_OBS_KH_GROWTH 2   /* TimeEnergyGrowth, time_energy_growth.hpp */
+#define SX_OBS_WIND_BUBBLE 3 /* WindBubble, wind_bubble_fraction.hpp */
+#define SX_OBS_GRAV_WAVES 4  /* GravWaves, gravitational_waves.hpp */
+#define SX_OBS_MAX_SUMS 15   /* the nine conserved sums + at most six of the kind */
+#define SX_OBS_MAX_COLUMNS 16 /* longest row of sx_sim_observe */
+/*! what the observables read besides the fields (the constructor arguments of factory.hpp:48-66) */
+typedef struct sx_obs_settings
+{
+    double rhoBubble;     /* wind bubble: initial density inside the cloud (rhoInt) */
+    double tempWind;      /* wind bubble: temperature of the wind, uExt * idealGasCv(muiConst, gamma) */
+    double initialMass;   /* wind bubble: initial mass of the cloud, 4/3 pi rSphere^3 rhoInt */
+    double particleMass;  /* wind bubble: the reference's m[0] (equal masses, wind_bubble_fraction.hpp:96) */
+    double gravWaveTheta; /* viewing angles of the gravitational-wave polarisations */
+    double gravWavePhi;
+} sx_obs_settings;
+/*! zeros, and 1 for the masses (a fraction that is a particle count until the caller sets them) */
+int sx_obs_default_settings(sx_obs_settings* s);
+/*! extra sums of a kind: 0, 1, 3, 1, 6; -1 for an unknown kind */
+int sx_obs_num_sums(int kind);
+/*! one fused, deterministic pass over [first, last) of f (replaces gpuGrowthRate, machSquareSumGpu and survivorsGpu,
+ *  main/src/observables/gpu_reductions.cu:69-168, each together with conservedQuantitiesGpu, conserved_gpu.cu:71-94;
+ *  and d2QuadpoleMomentum, grav_waves_calculations.hpp:87-121, which the reference runs on host vectors,
+ *  gravitational_waves.hpp:114).  out receives this rank's sums, all double: the nine of sx_conserved_quantities,
+ *  then
+ *    SX_OBS_MACH_RMS     sum |v|^2 / c^2 (float per term, as MachSquareSum)
+ *    SX_OBS_KH_GROWTH    sum si, sum ci, sum di with ybox = box->lim[3] - box->lim[2] (localGrowthRate,
+ *                        time_energy_growth.hpp:57-63: xm / kx in float, the rest in double)
+ *    SX_OBS_WIND_BUBBLE  the number of particles with kx / xm * m >= 0.64 rhoBubble and temp <= 0.9 tempWind
+ *    SX_OBS_GRAV_WAVES   d2Q xx, yy, zz, xy, xz, yz (the diagonal times 2/3 after the sum, as :108)
+ *  SX_ERR_ARG with a message when cap < 9 + sx_obs_num_sums(kind) or a field of the kind is NULL: c for the Mach RMS,
+ *  kx, xm for the KH growth and the wind bubble (and temp for the latter), ax, ay, az for the gravitational waves.
+ *  A caller that holds only the kind's fields (the signatures of gpu_reductions.h) may leave fields of the conserved
+ *  sums NULL (x y z vx vy vz m, temp or u): the nine conserved sums are then zero and only the kind's fields are read
+ *  (SX_OBS_TIME_ENERGY needs them all).  settings may be NULL unless kind is SX_OBS_WIND_BUBBLE.  The result does not
+ *  depend on the device or the run: fixed grid, fixed order, no atomics.  Synchronises. */
+int sx_observables(sx_ctx* ctx, const sx_fields* f, const sx_box* box, uint32_t first, uint32_t last, int kind,
+                   const sx_obs_settings* settings, float muiConst, double gamma, double* out, int cap);
+/*! computeHtt (grav_waves_calculations.hpp:50-84): out = {h+, hx} of the quadrupole's second derivative q (xx, yy,
+ *  zz, xy, xz, yz) seen from (theta, phi), in the reference's units (10 kpc).  Host arithmetic, needs no GPU. */
+int sx_grav_wave_htt(const double q[6], double theta, double phi, double out[2]);
+/*! the observable from the sums of sx_observables added over the ranks (globalSums: nine conserved + the kind's) and
+ *  the global particle count.  Host arithmetic, needs no GPU.  out receives
+ *    SX_OBS_TIME_ENERGY  nothing
+ *    SX_OBS_MACH_RMS     sqrt(sum / N)                            (turbulence_mach_rms.hpp:84)
+ *    SX_OBS_KH_GROWTH    2 sqrt(s^2 + c^2) / d                    (time_energy_growth.hpp:109)
+ *    SX_OBS_WIND_BUBBLE  count * particleMass / initialMass       (wind_bubble_fraction.hpp:96)
+ *    SX_OBS_GRAV_WAVES   h+, hx at (gravWaveTheta, gravWavePhi)   (gravitational_waves.hpp:86) */
+int sx_obs_finalize(int kind, const sx_obs_settings* settings, const double* globalSums, uint64_t numParticlesGlobal,
+                    double* out);
+
 /* ---- self-gravity: ryoanji MultipoleHolder seam (multipole_holder.cuh:40-66, gravity_wrapper.hpp:104-174) ----- */
 /*! expansion centers (mass centers, {x,y,z,mac^2}, numNodes x 4 doubles; mac = 2 max(node size)/theta + |com-geo|,
  *  setMac, source_center.hpp:130-143) and Cartesian quadrupoles (numNodes x 8 floats, Cqi order,
@@ -501,6 +557,29 @@ int    sx_sim_gravity_interactions(sx_sim* sim, uint64_t out[2]);
  *  communicator: {ecin, eint, egrav, etot, |linmom|, |angmom|, totalNeighbors, linmom x y z, angmom x y z}
  *  (egrav of the last step; synchronises) */
 int    sx_sim_conserved(sx_sim* sim, double out[13]);
+/*! select the observable of sx_sim_observe (observablesFactory, factory.hpp:46-69; the default is
+ *  SX_OBS_TIME_ENERGY).  For SX_OBS_WIND_BUBBLE the settings carry the reference's three inputs and the driver forms
+ *  the derived ones as wind_bubble_fraction.hpp:114-131 and factory.hpp:59-63 do: rhoBubble = rhoInt, tempWind = uExt
+ *  (the driver stores uExt * idealGasCv(muiConst, gamma)), initialMass = rSphere (stored: 4/3 pi rSphere^3 rhoInt);
+ *  particleMass <= 0 takes the mass of the rank's first particle at each sx_sim_observe, the reference's m[0].
+ *  settings NULL: the defaults.  Every propagator and any number of ranks; SX_ERR_ARG for SX_OBS_KH_GROWTH and
+ *  SX_OBS_WIND_BUBBLE with the std propagator, which has no kx (the reference's reason, time_energy_growth.hpp:88-91,
+ *  wind_bubble_fraction.hpp:125-129). */
+int    sx_sim_set_observable(sx_sim* sim, int kind, const sx_obs_settings* settings);
+/*! the row IObservables::computeAndWrite writes to constants.txt for the current state (one fused pass over the local
+ *  particles, the last step's egrav and the local particle count added, ONE sum over the communicator, finalised on
+ *  the host; synchronises).  Columns, in the reference's order:
+ *    iteration ttot minDt etot ecin eint egrav |linmom| |angmom|          SX_OBS_TIME_ENERGY (time_energies.hpp)
+ *    ... machRms                                                         SX_OBS_MACH_RMS (turbulence_mach_rms.hpp:112)
+ *    ... khGrowthRate                                                    SX_OBS_KH_GROWTH (time_energy_growth.hpp:137)
+ *    ... bubbleFraction ttot/0.0937                                      SX_OBS_WIND_BUBBLE (wind_bubble_fraction.hpp:141)
+ *    iteration ttot minDt etot ecin eint egrav h+ hx d2xx d2yy d2zz d2xy d2xz d2yz   SX_OBS_GRAV_WAVES (no momenta,
+ *                                                                        gravitational_waves.hpp:122-123)
+ *  iteration counts the completed steps (sx_sim_set_iteration after a restart).  *ncols receives the number of columns;
+ *  SX_ERR_ARG when cap is smaller.  Nothing is computed on steps after which this is not called. */
+int    sx_sim_observe(sx_sim* sim, double* row, int cap, int* ncols);
+/*! the iteration a restarted run continues from (the restart file's "iteration" attribute) */
+int    sx_sim_set_iteration(sx_sim* sim, uint64_t iteration);
 /*! device time (ms) of each hot kernel alone in the last step (HIP events on the launch stream, bracketing just the
  *  launch): findNeighbors, xmass, veDefGradh, iadDivvCurlv, avSwitches, momentumEnergy */
 int    sx_sim_kernel_times(sx_sim* sim, float* ms, int cap, const char** names);

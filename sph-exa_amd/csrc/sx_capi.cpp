@@ -1240,6 +1240,115 @@ extern "C"
         return SX_OK;
     }
 
+    int sx_obs_default_settings(sx_obs_settings* s)
+    {
+        if (!s) return SX_ERR_ARG;
+        *s = sx_obs_settings{0.0, 0.0, 1.0, 1.0, 0.0, 0.0};
+        return SX_OK;
+    }
+
+    int sx_obs_num_sums(int kind) { return kind < 0 || kind >= kObsKinds ? -1 : obsExtraSums(kind); }
+
+    int sx_observables(sx_ctx* c, const sx_fields* f, const sx_box* box, uint32_t first, uint32_t last, int kind,
+                       const sx_obs_settings* set, float muiConst, double gamma, double* out, int cap)
+    {
+        if (!c) return SX_ERR_ARG;
+        if (kind < 0 || kind >= kObsKinds) return fail(c, SX_ERR_ARG, "sx_observables: unknown kind");
+        const int nq = kObsConserved + obsExtraSums(kind);
+        if (!f || !out || cap < nq)
+            return fail(c, SX_ERR_ARG, "sx_observables: out holds " + std::to_string(cap) + " sums, the kind has " +
+                                           std::to_string(nq));
+        if (last > f->n || first > last) return fail(c, SX_ERR_ARG, "sx_observables: [first, last) outside the fields");
+        const char* why = nullptr;
+        if (kind == kObsMachRms && !(f->c && f->vx && f->vy && f->vz))
+            why = "sx_observables: the Mach RMS needs c (and vx, vy, vz)";
+        else if (kind == kObsKhGrowth && !(f->kx && f->xm))
+            why = "sx_observables: kx or xm is missing. The KH growth rate is only supported with volume elements";
+        else if (kind == kObsKhGrowth && !(f->x && f->y && f->vy && box))
+            why = "sx_observables: the KH growth rate needs x, y, vy and the box";
+        else if (kind == kObsWindBubble && !(f->kx && f->xm))
+            why = "sx_observables: kx or xm is missing. The wind-shock surviving fraction is only supported with "
+                  "volume elements";
+        else if (kind == kObsWindBubble && !(f->temp && f->m && set))
+            why = "sx_observables: the wind bubble needs temp, m and the settings";
+        else if (kind == kObsGravWaves && !(f->ax && f->ay && f->az))
+            why = "sx_observables: the gravitational waves need ax, ay, az";
+        else if (kind == kObsGravWaves && !(f->x && f->y && f->z && f->vx && f->vy && f->vz && f->m))
+            why = "sx_observables: the gravitational waves need x, y, z, vx, vy, vz, m";
+        const bool cons = f->x && f->y && f->z && f->vx && f->vy && f->vz && f->m && (f->u || f->temp);
+        if (!why && kind == kObsTimeEnergy && !cons) why = "sx_observables: null field of the conserved sums";
+        if (why) return fail(c, SX_ERR_ARG, why);
+
+        ObsArgs a{};
+        a.c = ConservedArgs{first, last, f->x, f->y, f->z, f->vx, f->vy, f->vz, f->m, f->temp, f->u, f->nc,
+                            (double)idealGasCv(muiConst, gamma)};
+        a.conserved = cons;
+        a.cs = f->c, a.kx = f->kx, a.xm = f->xm, a.ax = f->ax, a.ay = f->ay, a.az = f->az;
+        a.ybox    = box ? box->lim[3] - box->lim[2] : 0.0;
+        a.rhoMin  = set ? 0.64 * set->rhoBubble : 0.0;
+        a.tempMax = set ? 0.9 * set->tempWind : 0.0;
+        double* scratch = c->arena.get<double>("obs.fused", observablesScratch());
+        double* dout    = c->arena.get<double>("obs.fusedOut", kObsMaxSums + 1);
+        double* hout    = c->arena.pinned<double>("obs.fusedHost", kObsMaxSums + 1);
+        SX_HIP(c, observables(kind, a, scratch, dout, c->stream));
+        SX_HIP(c, hipMemcpyAsync(hout, dout, nq * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        SX_HIP(c, hipStreamSynchronize(c->stream));
+        for (int k = 0; k < nq; ++k)
+            out[k] = hout[k];
+        return SX_OK;
+    }
+
+    int sx_grav_wave_htt(const double q[6], double theta, double phi, double out[2])
+    {
+        if (!q || !out) return SX_ERR_ARG;
+        // computeHtt (grav_waves_calculations.hpp:50-84) with T = double, statement by statement
+        const double g       = 6.6726e-8;
+        const double c       = 2.997924562e10;
+        const double gwunits = g / std::pow(c, 4) / 3.08568025e22;
+        const double sin2t   = std::sin(2.0 * theta);
+        const double sin2p   = std::sin(2.0 * phi);
+        const double cos2p   = std::cos(2.0 * phi);
+        const double sint    = std::sin(theta);
+        const double sinp    = std::sin(phi);
+        const double cost    = std::cos(theta);
+        const double cosp    = std::cos(phi);
+        const double sqsint  = sint * sint;
+        const double sqsinp  = sinp * sinp;
+        const double sqcost  = cost * cost;
+        const double sqcosp  = cosp * cosp;
+        enum { xx, yy, zz, xy, xz, yz };
+        const double tt = (q[xx] * sqcosp + q[yy] * sqsinp + q[xy] * sin2p) * sqcost + q[zz] * sqsint -
+                          (q[xz] * cosp + q[yz] * sinp) * sin2t;
+        const double pp = q[xx] * sqsinp + q[yy] * sqcosp - q[xy] * sin2p;
+        const double tp = 0.5 * (q[yy] - q[xx]) * cost * sin2p + q[xy] * cost * cos2p +
+                          (q[xz] * sinp - q[yz] * cosp) * sint;
+        out[0] = (tt - pp) * gwunits;
+        out[1] = 2.0 * tp * gwunits;
+        return SX_OK;
+    }
+
+    int sx_obs_finalize(int kind, const sx_obs_settings* set, const double* sums, uint64_t numParticlesGlobal,
+                        double* out)
+    {
+        if (kind < 0 || kind >= kObsKinds || !sums) return SX_ERR_ARG;
+        if (kind == kObsTimeEnergy) return SX_OK;
+        if (!out) return SX_ERR_ARG;
+        const double* x = sums + kObsConserved;
+        if (kind == kObsMachRms) out[0] = std::sqrt(x[0] / numParticlesGlobal);
+        else if (kind == kObsKhGrowth) out[0] = 2.0 * std::sqrt(x[0] * x[0] + x[1] * x[1]) / x[2];
+        else if (kind == kObsWindBubble)
+        {
+            if (!set) return SX_ERR_ARG;
+            out[0] = (double)(size_t)x[0] * set->particleMass / set->initialMass;
+        }
+        else
+        {
+            if (!set) return SX_ERR_ARG;
+            return sx_grav_wave_htt(x, set->gravWaveTheta, set->gravWavePhi, out);
+        }
+        return SX_OK;
+    }
+
     int sx_gravity_upsweep(sx_ctx* c, const sx_fields* f, const sx_tree* tree, float theta, double* centers,
                            float* multipoles)
     {

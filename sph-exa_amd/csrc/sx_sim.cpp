@@ -2562,7 +2562,114 @@ extern "C"
         return SX_OK;
     }
 
+    int sx_sim_set_observable(sx_sim* s, int kind, const sx_obs_settings* set)
+    {
+        if (!s) return SX_ERR_ARG;
+        const char* why = nullptr;
+        if (kind < 0 || kind >= kObsKinds) why = "sx_sim_set_observable: unknown kind";
+        else if (kind == kObsKhGrowth && s->p.propagator == 1)
+            why = "kx was empty. KHGrowthRate only supported with volume elements (--prop ve)";
+        else if (kind == kObsWindBubble && s->p.propagator == 1)
+            why = "kx was empty. Wind Shock surviving fraction is only supported with volume elements (--prop ve)";
+        if (why)
+        {
+            sx_ctx_set_error_internal(s->ctx, why);
+            return SX_ERR_ARG;
+        }
+        sx_obs_settings o;
+        sx_obs_default_settings(&o);
+        if (set) o = *set;
+        if (kind == kObsWindBubble && set)
+        {
+            // WindBubble's constructor and computeAndWrite (wind_bubble_fraction.hpp:114-131; factory.hpp:59-63)
+            const double rhoInt = set->rhoBubble, uExt = set->tempWind, rSphere = set->initialMass;
+            const double bubbleVolume = std::pow(rSphere, 3) * 4.0 / 3.0 * M_PI;
+            o.initialMass = bubbleVolume * rhoInt;
+            o.tempWind    = uExt * idealGasCv(s->p.muiConst, s->p.gamma);
+        }
+        s->obsKind = kind;
+        s->obsSet  = o;
+        return SX_OK;
+    }
+
+    int sx_sim_set_iteration(sx_sim* s, uint64_t iteration)
+    {
+        if (!s) return SX_ERR_ARG;
+        s->iteration = iteration;
+        return SX_OK;
+    }
+
+    int sx_sim_observe(sx_sim* s, double* row, int cap, int* ncols)
+    {
+        if (!s || !row) return SX_ERR_ARG;
+        const int kind = s->obsKind;
+        const int nx   = obsExtraSums(kind);
+        const int nq   = kObsConserved + nx;
+        const int nrow = kind == kObsGravWaves ? 15 : kind == kObsWindBubble ? 11 : kind == kObsTimeEnergy ? 9 : 10;
+        if (ncols) *ncols = nrow;
+        if (cap < nrow)
+        {
+            sx_ctx_set_error_internal(s->ctx, "sx_sim_observe: the row is longer than cap");
+            return SX_ERR_ARG;
+        }
+        hipStream_t st = (hipStream_t)sx_ctx_stream_internal(s->ctx);
+        ObsArgs     a{};
+        a.c = ConservedArgs{s->first, s->last, s->x, s->y, s->z, s->vx, s->vy, s->vz, s->m, s->temp, nullptr, s->nc,
+                            (double)idealGasCv(s->p.muiConst, s->p.gamma)};
+        a.conserved = true;
+        a.cs = s->c, a.kx = s->kx, a.xm = s->xm, a.ax = s->ax, a.ay = s->ay, a.az = s->az;
+        a.ybox    = s->box.lim[3] - s->box.lim[2];
+        a.rhoMin  = 0.64 * s->obsSet.rhoBubble;
+        a.tempMax = 0.9 * s->obsSet.tempWind;
+        double* scratch = s->work.get<double>("obs.fused", observablesScratch());
+        // [nq sums | particle count | egrav]: one reduction over the ranks for all of it
+        double* q = s->work.get<double>("obs.fusedQ", kObsMaxSums + 2);
+        SIM_HIP(observables(kind, a, scratch, q, st));
+        // egrav of the last step joins the sum (computeConservedQuantities, conserved_quantities.hpp:145-153)
+        SIM_HIP(hipMemcpyAsync(q + nq + 1, &s->sc->egrav, 8, hipMemcpyDeviceToDevice, st));
+        if (s->comm && s->comm->size() > 1) SIM_COMM(s->comm->allreduceSumF64(q, nq + 2, st));
+        double h[kObsMaxSums + 2];
+        float  m0 = 0.0f;
+        SIM_HIP(hipMemcpyAsync(h, q, (nq + 2) * sizeof(double), hipMemcpyDeviceToHost, st));
+        SIM_HIP(hipMemcpyAsync(s->scHost, s->sc, sizeof(Scalars), hipMemcpyDeviceToHost, st));
+        if (kind == kObsWindBubble && !(s->obsSet.particleMass > 0.0) && s->last > s->first)
+            SIM_HIP(hipMemcpyAsync(&m0, s->m + s->first, 4, hipMemcpyDeviceToHost, st));
+        SIM_HIP(hipStreamSynchronize(st));
+
+        const double   ecin = h[0], eint = h[1], egrav = h[nq + 1];
+        const uint64_t numGlobal = (uint64_t)h[nq];
+        int            k = 0;
+        row[k++] = (double)s->iteration;
+        row[k++] = s->scHost->ttot;
+        row[k++] = s->scHost->minDt;
+        row[k++] = ecin + eint + egrav;
+        row[k++] = ecin, row[k++] = eint, row[k++] = egrav;
+        if (kind != kObsGravWaves)
+        {
+            row[k++] = std::sqrt(h[2] * h[2] + h[3] * h[3] + h[4] * h[4]);
+            row[k++] = std::sqrt(h[5] * h[5] + h[6] * h[6] + h[7] * h[7]);
+        }
+        sx_obs_settings set = s->obsSet;
+        if (!(set.particleMass > 0.0)) set.particleMass = m0;
+        if (sx_obs_finalize(kind, &set, h, numGlobal, row + k) != SX_OK) return SX_ERR_ARG;
+        k += kind == kObsGravWaves ? 2 : kind == kObsTimeEnergy ? 0 : 1;
+        if (kind == kObsWindBubble) row[k++] = s->scHost->ttot / 0.0937; // normalizedTime, wind_bubble_fraction.hpp:138-139
+        if (kind == kObsGravWaves)
+            for (int j = 0; j < 6; ++j)
+                row[k++] = h[kObsConserved + j];
+        return SX_OK;
+    }
+
+    static int stepImpl(sx_sim* s);
+
     int sx_sim_step(sx_sim* s)
+    {
+        const int rc = stepImpl(s);
+        if (rc == SX_OK) ++s->iteration;
+        return rc;
+    }
+
+    static int stepImpl(sx_sim* s)
     {
         if (s->p.propagator == 2) return stepBdt(s);
         hipStream_t        st  = (hipStream_t)sx_ctx_stream_internal(s->ctx);

@@ -210,6 +210,11 @@ struct sx_sim
     sx::sim::SkinState skin;
     sx::turb::SimTurb* turb{nullptr}; // turbulence stirring (sx_sim_set_turbulence), VE propagator on one rank
 
+    // the observable of sx_sim_observe (observablesFactory, main/src/observables/factory.hpp:46-69)
+    int             obsKind{0};
+    sx_obs_settings obsSet{0.0, 0.0, 1.0, 1.0, 0.0, 0.0};
+    uint64_t        iteration{0}; // completed steps (ParticlesData::iteration of the row)
+
     Fields fields() const { return Fields{x, y, z, temp, h, m, vx, vy, vz, xm1, ym1, zm1, dum1, alpha, id, rung}; }
 };
 

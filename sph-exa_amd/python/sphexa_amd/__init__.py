@@ -93,6 +93,84 @@ class SxTurbSettings(C.Structure):
             setattr(self, k, v)
 
 
+class SxObsSettings(C.Structure):
+    """sx_obs_settings: what the observables read besides the fields (factory.hpp:48-66)"""
+    _fields_ = [("rhoBubble", C.c_double), ("tempWind", C.c_double), ("initialMass", C.c_double),
+                ("particleMass", C.c_double), ("gravWaveTheta", C.c_double), ("gravWavePhi", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().sx_obs_default_settings(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError(f"unknown observable setting {k!r}")
+            setattr(self, k, float(v))
+
+
+# the observables of observablesFactory (factory.hpp:46-69): SX_OBS_* by name, the sums sx_observables appends to the
+# nine conserved ones, and the columns of the constants.txt row
+OBS_KINDS = {"time_energy": 0, "mach_rms": 1, "kh_growth": 2, "wind_bubble": 3, "grav_waves": 4}
+CONSERVED_SUMS = ["ecin", "eint", "px", "py", "pz", "Lx", "Ly", "Lz", "totalNeighbors"]
+OBS_SUMS = {"time_energy": [], "mach_rms": ["machSquareSum"], "kh_growth": ["sumsi", "sumci", "sumdi"],
+            "wind_bubble": ["survivors"], "grav_waves": ["d2xx", "d2yy", "d2zz", "d2xy", "d2xz", "d2yz"]}
+_ROW_HEAD = ["iteration", "ttot", "minDt", "etot", "ecin", "eint", "egrav"]
+OBS_COLUMNS = {
+    "time_energy": _ROW_HEAD + ["linmom", "angmom"],
+    "mach_rms": _ROW_HEAD + ["linmom", "angmom", "machRms"],
+    "kh_growth": _ROW_HEAD + ["linmom", "angmom", "khgr"],
+    "wind_bubble": _ROW_HEAD + ["linmom", "angmom", "bubbleFraction", "normalizedTime"],
+    "grav_waves": _ROW_HEAD + ["httplus", "httcross"] + OBS_SUMS["grav_waves"],
+}
+
+
+def obs_kind(kind):
+    """(SX_OBS_* value, name) of a kind given by name or value"""
+    names = {v: k for k, v in OBS_KINDS.items()}
+    if kind in OBS_KINDS:
+        return OBS_KINDS[kind], kind
+    if kind in names:
+        return kind, names[kind]
+    raise ValueError(f"unknown observable {kind!r}: one of {sorted(OBS_KINDS)}")
+
+
+def grav_wave_htt(q, theta, phi):
+    """(h+, hx) of the quadrupole's second derivative q = (xx, yy, zz, xy, xz, yz) (sx_grav_wave_htt: computeHtt,
+    grav_waves_calculations.hpp:50-84).  Needs no GPU."""
+    qq = (C.c_double * 6)(*[float(v) for v in q])
+    out = (C.c_double * 2)()
+    if lib().sx_grav_wave_htt(qq, float(theta), float(phi), out) != SX_OK:
+        raise SxError("sx_grav_wave_htt failed")
+    return out[0], out[1]
+
+
+def obs_finalize(kind, sums, num_particles_global, settings=None):
+    """the observable's values from the global sums of Context.observables (sx_obs_finalize): [] for time_energy,
+    [machRms], [khgr], [bubbleFraction] or [h+, hx].  Needs no GPU."""
+    k, name = obs_kind(kind)
+    settings = settings if settings is not None else SxObsSettings()
+    s = np.ascontiguousarray([sums[n] for n in CONSERVED_SUMS + OBS_SUMS[name]] if isinstance(sums, dict) else sums,
+                             dtype=np.float64)
+    if s.size != 9 + len(OBS_SUMS[name]):
+        raise ValueError(f"{name}: {9 + len(OBS_SUMS[name])} sums expected, got {s.size}")
+    out = (C.c_double * 2)()
+    rc = lib().sx_obs_finalize(k, C.byref(settings), s.ctypes.data_as(C.POINTER(C.c_double)),
+                               int(num_particles_global), out)
+    if rc != SX_OK:
+        raise SxError(f"sx_obs_finalize: code {rc}")
+    return list(out)[:{"time_energy": 0, "grav_waves": 2}.get(name, 1)]
+
+
+def format_constants_row(row, kind):
+    """the line fileutils::writeColumns(out, ' ', ...) writes for a row of Sim.observe (main/src/io/file_utils.hpp:14-18):
+    every column preceded by one separator, the iteration an integer, doubles in the stream's default format (%g)"""
+    _, name = obs_kind(kind)
+    cols = OBS_COLUMNS[name]
+    vals = [row[c] for c in cols] if isinstance(row, dict) else list(row)
+    if len(vals) != len(cols):
+        raise ValueError(f"{name}: {len(cols)} columns expected, got {len(vals)}")
+    return "".join([" %d" % int(vals[0])] + [" %g" % float(v) for v in vals[1:]]) + "\n"
+
+
 class SxOctree(C.Structure):
     _fields_ = [("prefixes", _P), ("childOffsets", _P), ("parents", _P), ("levelRange", _P),
                 ("internalToLeaf", _P), ("leafToInternal", _P)]
@@ -269,6 +347,16 @@ def lib():
         "sx_sim_turbulence": (C.c_int, [vp, C.POINTER(vp)]),
         "sx_sim_set_turbulence_state": (C.c_int, [vp, C.POINTER(C.c_double), C.c_uint64, vp, vp, vp, C.c_char_p]),
         "sx_sim_turbulence_times": (C.c_int, [vp, C.POINTER(C.c_float)]),
+        "sx_obs_default_settings": (C.c_int, [C.POINTER(SxObsSettings)]),
+        "sx_obs_num_sums": (C.c_int, [C.c_int]),
+        "sx_observables": (C.c_int, [vp, C.POINTER(SxFields), C.POINTER(SxBox), u32, u32, C.c_int,
+                                     C.POINTER(SxObsSettings), C.c_float, C.c_double, C.POINTER(C.c_double), C.c_int]),
+        "sx_grav_wave_htt": (C.c_int, [C.POINTER(C.c_double), C.c_double, C.c_double, C.POINTER(C.c_double)]),
+        "sx_obs_finalize": (C.c_int, [C.c_int, C.POINTER(SxObsSettings), C.POINTER(C.c_double), C.c_uint64,
+                                      C.POINTER(C.c_double)]),
+        "sx_sim_set_observable": (C.c_int, [vp, C.c_int, C.POINTER(SxObsSettings)]),
+        "sx_sim_observe": (C.c_int, [vp, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int)]),
+        "sx_sim_set_iteration": (C.c_int, [vp, C.c_uint64]),
     }
     for name, (res, args) in sig.items():
         # a measurement build named by SPHEXA_AMD_LIB (an A/B against an older library) may predate an entry
@@ -522,6 +610,20 @@ class Context:
 
     def sync(self):
         self.check(self.L.sx_synchronize(self.h), "sync")
+
+    def observables(self, fields, kind, first=0, last=None, box=None, settings=None, mui=10.0, gamma=5.0 / 3.0,
+                    cap=None):
+        """this rank's sums of one fused pass over [first, last) of an SxFields (sx_observables): a dict with the
+        nine conserved sums (CONSERVED_SUMS) followed by the kind's (OBS_SUMS); kind by name or SX_OBS_* value"""
+        k, name = obs_kind(kind)
+        names = CONSERVED_SUMS + OBS_SUMS[name]
+        cap = len(names) if cap is None else int(cap)
+        out = (C.c_double * max(1, cap))()
+        last = fields.n if last is None else last
+        self.check(self.L.sx_observables(self.h, C.byref(fields), C.byref(box) if box is not None else None,
+                                         int(first), int(last), k, C.byref(settings) if settings is not None else None,
+                                         float(mui), float(gamma), out, cap), "sx_observables")
+        return dict(zip(names, list(out)))
 
 
 class DeviceArray:
@@ -933,6 +1035,45 @@ class Sim:
         names = ["ecin", "eint", "egrav", "etot", "linmom", "angmom", "totalNeighbors", "px", "py", "pz", "Lx", "Ly",
                  "Lz"]
         return dict(zip(names, list(out)))
+
+    def set_observable(self, kind, **settings):
+        """select the observable of observe() (sx_sim_set_observable; observablesFactory, factory.hpp:46-69): "time_energy"
+        (the default), "mach_rms", "kh_growth", "wind_bubble" (rhoInt, uExt, rSphere as the reference's settings;
+        particleMass, default: the first particle's mass) or "grav_waves" (gravWaveTheta, gravWavePhi)"""
+        k, name = obs_kind(kind)
+        allowed = {"wind_bubble": {"rhoInt": "rhoBubble", "uExt": "tempWind", "rSphere": "initialMass",
+                                   "particleMass": "particleMass"},
+                   "grav_waves": {"gravWaveTheta": "gravWaveTheta", "gravWavePhi": "gravWavePhi"}}.get(name, {})
+        bad = [s for s in settings if s not in allowed]
+        if bad:
+            raise TypeError(f"observable {name!r} takes the settings {sorted(allowed)}, not {bad}")
+        if name == "wind_bubble":
+            missing = [s for s in ("rhoInt", "uExt", "rSphere") if s not in settings]
+            if missing:
+                raise TypeError(f"observable 'wind_bubble' needs {missing}")
+            settings.setdefault("particleMass", 0.0)
+        st = SxObsSettings(**{allowed[s]: v for s, v in settings.items()})
+        self.ctx.check(self.L.sx_sim_set_observable(self.h, k, C.byref(st)), "set_observable")
+        self.observable = name
+
+    def observe(self):
+        """the constants.txt row of the current state (sx_sim_observe), a dict under the reference's names in the
+        reference's column order (OBS_COLUMNS); nothing is computed on steps after which this is not called"""
+        row = (C.c_double * 16)()
+        n = C.c_int()
+        self.ctx.check(self.L.sx_sim_set_iteration(self.h, int(self.iteration)), "set_iteration")
+        self.ctx.check(self.L.sx_sim_observe(self.h, row, 16, C.byref(n)), "observe")
+        cols = OBS_COLUMNS[getattr(self, "observable", "time_energy")]
+        assert n.value == len(cols)
+        d = dict(zip(cols, list(row)))
+        d["iteration"] = int(d["iteration"])
+        return d
+
+    def write_constants(self, fileobj):
+        """append the row of observe() to a constants.txt (format_constants_row); returns the row"""
+        row = self.observe()
+        fileobj.write(format_constants_row(row, getattr(self, "observable", "time_energy")))
+        return row
 
     def timestep(self):
         """ve-bdt: the Timestep after the last substep (sx_sim_timestep)"""
