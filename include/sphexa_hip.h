@@ -42,6 +42,8 @@
  *   sx_turb_*              sph::TurbulenceData, updateNoise, computePhases  sph/include/sph/hydro_turb/turbulence_data.hpp:46-184,
  *                                                               driver.hpp:80-92, phases.hpp:47-72, create_modes.hpp:59-244
  *   sx_stir                sph::computeStirringGpu              hydro_turb/stirring.hpp:123-126 (stirParticle :44-79)
+ *   sx_gravity_direct      ryoanji::directSum                   ryoanji/interface/multipole_holder.cuh:72-74, nbody/direct.cuh:52-123
+ *                                                               (CPU form: nbody/traversal_cpu.hpp:234-270)
  *   sx_sim_set_turbulence  TurbVeProp::computeForces            main/src/propagator/turb_ve.hpp:114-119
  *   sx_observables         sphexa::gpuGrowthRate, machSquareSumGpu, survivorsGpu  main/src/observables/gpu_reductions.cu:69-168;
  *                                                               d2QuadpoleMomentum grav_waves_calculations.hpp:87-121
@@ -421,6 +423,29 @@ int sx_gravity_traverse_pbc(sx_ctx* ctx, const sx_groups* g, const sx_fields* f,
                             const sx_box* box, const double* centers, const float* multipoles, float G, int numShells,
                             double* egrav);
 
+/*! ryoanji::directSum (interface/multipole_holder.cuh:72-74, nbody/direct.cuh:52-123, traversal_cpu.hpp:234-270): the
+ *  O(N^2) sum for the targets of g over the sources [0, f->n), the softened P2P of kernel.hpp:514-535 (h_i + h_j formed
+ *  in float), every target shifted by (ix Lx, iy Ly, iz Lz), |ix|, |iy|, |iz| <= numShells (0..4; iz outermost, ix
+ *  innermost).  Reads x, y, z, m, h.  With numShells > 0 the lengths come from box->lim (any shape: no Ewald sum here);
+ *  box may be NULL when numShells == 0.  The view is that of sx_stir: [firstBody, lastBody) or explicit groups of any
+ *  size >= 0; particles outside it are not touched.
+ *  Output: f->ax, ay, az (all three, or none) get (float)((double)ax + G acc), as the walk's; out4 (device, 4 doubles
+ *  per particle of f, or NULL) gets {G m_i phi_i, G ax, G ay, G az} of the reference's CPU function, un-accumulated;
+ *  *egrav = 0.5 sum_i G m_i phi_i over the view (0 for an empty view).  At least one of the two outputs is required.
+ *  sx_set_exact(1): double throughout, 1/sqrt, the reference's order of operations; sources ascending inside a source
+ *  split, splits combined ascending -- with one split the additions per target are those of the CPU loop.  Default:
+ *  packed float with rsqrt on sources relative to their tile's first source, folded into double once per 256-source
+ *  tile.
+ *  The grid is (blocks of 256 targets) x (source splits); a second kernel adds the splits in ascending order, so the
+ *  result is deterministic for a given split count.  Automatic rule: splits = clamp(ceil(16 * 256 / targetBlocks), 1,
+ *  sourceTiles), sourceTiles = ceil(n / 256), targetBlocks = ceil(targets / 256): sixteen workgroups per CU;
+ *  sx_set_direct_splits(ctx, k) overrides it (0: automatic; a k beyond sourceTiles is clamped).  Runs on the context
+ *  stream; synchronises to return *egrav.
+ *  SX_ERR_ARG: numShells out of range, x/y/z/m/h missing, no output, a view reaching beyond f->n. */
+int sx_gravity_direct(sx_ctx* ctx, const sx_groups* g, const sx_fields* f, const sx_box* box, int numShells, float G,
+                      double* out4, double* egrav);
+int sx_set_direct_splits(sx_ctx* ctx, uint32_t splits);
+
 /*! ryoanji::EwaldSettings (nbody/ewald.h:15-22); the reference's defaults: 1, 2.6, 2.8, 2.0, 3e-3 */
 typedef struct
 {
@@ -553,6 +578,16 @@ int    sx_sim_set_gravity_counting(sx_sim* sim, int enable);
  *  the reference's BhStats (nbody/traversal.cuh:346-357, 614-620): {sumP2P (source particles), sumM2P (multipole
  *  nodes)}; synchronises.  SX_ERR_ARG without gravity. */
 int    sx_sim_gravity_interactions(sx_sim* sim, uint64_t out[2]);
+/*! force-error check of the walk: arms the next step (numTargets = 0 disarms).  Right after its gravity walk, on the
+ *  same positions, tree, centers and multipoles, the armed step takes every s-th of its own 64-particle target blocks
+ *  (about numTargets targets), runs the walk once more for them into zeroed scratch accelerations and sx_gravity_direct
+ *  for the same view into a second scratch (periodic box: both with the walk's shell count, both without the Ewald
+ *  correction), and copies the two samples to the host.  Nothing the step computes changes.  One rank, VE and std
+ *  propagators: SX_ERR_ARG (sx_last_error has the reason) without gravity, with a communicator, under ve-bdt. */
+int    sx_sim_set_gravity_check(sx_sim* sim, uint32_t numTargets);
+/*! the last armed step's sample: {targets, mean, median, 99th percentile, max of |a_walk - a_direct| / |a_direct|,
+ *  sqrt(sum |a_walk - a_direct|^2 / sum |a_direct|^2)}.  SX_ERR_ARG when no armed step has run. */
+int    sx_sim_gravity_check(sx_sim* sim, double out[6]);
 /*! computeConservedQuantities (conserved_quantities.hpp:110-179) of the current state, summed over the ranks of the
  *  communicator: {ecin, eint, egrav, etot, |linmom|, |angmom|, totalNeighbors, linmom x y z, angmom x y z}
  *  (egrav of the last step; synchronises) */

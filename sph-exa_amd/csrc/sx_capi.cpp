@@ -13,6 +13,7 @@
 
 #include "../../include/sphexa_hip.h"
 #include "sx_comm.hpp"
+#include "sx_direct.hpp"
 #include "sx_gravity.hpp"
 #include "sx_hydro.hpp"
 #include "sx_kernel_poly.hpp"
@@ -117,6 +118,8 @@ struct sx_ctx
     hipStream_t stream{nullptr};
     bool        exact{false};
     int         packMaxSet{-1}; // sx_set_pack12_max's value; -1: the default (packMax())
+    uint32_t    directSplits{0};         // sx_set_direct_splits: source splits of sx_gravity_direct, 0 = automatic
+    uint32_t    directTargetsPerLane{sx::direct::kDefaultTargetsPerLane}; // fast direct sum (A/B: DESIGN.md 7f)
     Arena       arena;
     float2*     wh{nullptr};
     float2*     whd{nullptr};
@@ -1422,6 +1425,107 @@ extern "C"
             numShells > 4)
             return fail(c, SX_ERR_ARG, "sx_gravity_traverse_pbc: bad arguments");
         return gravityTraverseShells(c, g, f, tree, box, centers, multipoles, G, numShells, egrav);
+    }
+
+    int sx_set_direct_splits(sx_ctx* c, uint32_t splits)
+    {
+        if (!c) return SX_ERR_ARG;
+        c->directSplits = splits;
+        return SX_OK;
+    }
+
+    //! measurement switch of the fast direct sum (direct_bench.py): one or two targets per lane
+    int sx_ctx_direct_targets_per_lane_internal(sx_ctx* c, uint32_t k)
+    {
+        if (!c || k > 2) return SX_ERR_ARG;
+        c->directTargetsPerLane = k ? k : sx::direct::kDefaultTargetsPerLane; // 0: the default
+        return SX_OK;
+    }
+
+    int sx_gravity_direct(sx_ctx* c, const sx_groups* g, const sx_fields* f, const sx_box* box, int numShells, float G,
+                          double* out4, double* egrav)
+    {
+        namespace sd = sx::direct;
+        if (!c) return SX_ERR_ARG;
+        if (!g || !f) return fail(c, SX_ERR_ARG, "sx_gravity_direct: null group view or fields");
+        if (numShells < 0 || numShells > 4) return fail(c, SX_ERR_ARG, "sx_gravity_direct: numShells must be 0..4");
+        if (!f->x || !f->y || !f->z || !f->m || !f->h)
+            return fail(c, SX_ERR_ARG, "sx_gravity_direct: x, y, z, m and h are required");
+        const bool acc3 = f->ax && f->ay && f->az;
+        if ((f->ax || f->ay || f->az) && !acc3)
+            return fail(c, SX_ERR_ARG, "sx_gravity_direct: ax, ay, az go together");
+        if (!acc3 && !out4) return fail(c, SX_ERR_ARG, "sx_gravity_direct: no output (ax/ay/az or out4)");
+        if (numShells > 0 && !box) return fail(c, SX_ERR_ARG, "sx_gravity_direct: image shells need the box");
+        if (!groupsOk(g)) return fail(c, SX_ERR_ARG, "sx_gravity_direct: groupStart and groupEnd go together");
+        if (f->n >= 0xffffffffull) return fail(c, SX_ERR_ARG, "sx_gravity_direct: more than 2^32 - 2 particles");
+
+        sd::DirectArgs a{};
+        a.n = (uint32_t)f->n;
+        // explicit groups of any size: flattened on the host to one particle index per target slot
+        std::vector<uint32_t> slots;
+        if (g->groupStart)
+        {
+            std::vector<uint32_t> gs(g->numGroups), ge(g->numGroups);
+            if (g->numGroups)
+            {
+                SX_HIP(c, hipMemcpyAsync(gs.data(), g->groupStart, 4 * (size_t)g->numGroups, hipMemcpyDeviceToHost,
+                                         c->stream));
+                SX_HIP(c, hipMemcpyAsync(ge.data(), g->groupEnd, 4 * (size_t)g->numGroups, hipMemcpyDeviceToHost,
+                                         c->stream));
+                SX_HIP(c, hipStreamSynchronize(c->stream));
+            }
+            size_t total = 0;
+            for (uint32_t k = 0; k < g->numGroups; ++k)
+            {
+                if (ge[k] > f->n) return fail(c, SX_ERR_ARG, "sx_gravity_direct: a group reaches beyond f->n");
+                if (ge[k] > gs[k]) total += ge[k] - gs[k];
+            }
+            if (total >= 0xffffffffull) return fail(c, SX_ERR_ARG, "sx_gravity_direct: more than 2^32 - 2 targets");
+            slots.reserve(total);
+            for (uint32_t k = 0; k < g->numGroups; ++k)
+                for (uint32_t i = gs[k]; i < ge[k]; ++i)
+                    slots.push_back(i);
+            a.numTargets = (uint32_t)total;
+        }
+        else
+        {
+            if (g->lastBody > f->n) return fail(c, SX_ERR_ARG, "sx_gravity_direct: the view reaches beyond f->n");
+            a.first      = g->firstBody;
+            a.numTargets = g->lastBody > g->firstBody ? g->lastBody - g->firstBody : 0u;
+        }
+        if (a.numTargets == 0)
+        {
+            if (egrav) *egrav = 0.0;
+            return SX_OK;
+        }
+        if (!slots.empty())
+        {
+            uint32_t* d = c->arena.get<uint32_t>("direct.targets", slots.size());
+            if (!d) return fail(c, SX_ERR_NOMEM, "sx_gravity_direct: target list");
+            SX_HIP(c, hipMemcpyAsync(d, slots.data(), 4 * slots.size(), hipMemcpyHostToDevice, c->stream));
+            a.targets = d;
+        }
+        a.x = f->x, a.y = f->y, a.z = f->z, a.m = f->m, a.h = f->h;
+        if (acc3) a.ax = f->ax, a.ay = f->ay, a.az = f->az;
+        a.out4      = out4;
+        a.G         = G;
+        a.numShells = numShells;
+        for (int k = 0; k < 3; ++k)
+            a.boxL[k] = box ? box->lim[2 * k + 1] - box->lim[2 * k] : 0.0;
+        a.targetsPerLane = c->exact ? 1u : c->directTargetsPerLane;
+        sd::planSplits(a, c->directSplits);
+        a.partial = c->arena.get<double>("direct.partial", (size_t)a.splits * a.numTargets * 4);
+        a.blockE  = c->arena.get<double>("direct.blockE", sd::combineBlocks(a.numTargets));
+        a.egrav   = c->arena.get<double>("direct.egrav", 1);
+        if (!a.partial || !a.blockE || !a.egrav) return fail(c, SX_ERR_NOMEM, "sx_gravity_direct: partial sums");
+        SX_HIP(c, c->exact ? sd::directExact(a, c->stream) : sd::directFast(a, c->stream));
+        SX_HIP(c, sd::directCombine(a, c->stream));
+        double eh = 0.0;
+        if (egrav) SX_HIP(c, hipMemcpyAsync(&eh, a.egrav, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        // the host's target list and *egrav: done with both before returning
+        if (egrav || !slots.empty()) SX_HIP(c, hipStreamSynchronize(c->stream));
+        if (egrav) *egrav = eh;
+        return SX_OK;
     }
 
     int sx_gravity_ewald(sx_ctx* c, const sx_groups* g, const sx_fields* f, const sx_box* box, const double* centers,

@@ -1703,6 +1703,109 @@ void maxAccSq(sx_sim* s, hipStream_t st)
 //! admits only boxes periodic along all three axes with self-gravity)
 bool periodicGravity(const sx_sim* s) { return s->p.g != 0.0 && s->box.bnd[0] == 1; }
 
+/*! the armed step's force-error sample (sx_sim_set_gravity_check): every stride-th 64-particle target block of the walk
+ *  that has just run (step: its arguments), walked once more into zeroed scratch accelerations and summed directly
+ *  (sx_gravity_direct) into a second scratch, both read back and compared on the host.  Writes scratch only. */
+int gravityCheck(sx_sim* s, const GravArgs& step, hipStream_t st)
+{
+    s->gravCheckValid = false;
+    const uint32_t first = step.first, last = step.last;
+    if (last <= first) return SX_OK;
+    const uint32_t blocks = (last - first + kWave - 1) / kWave;
+    const uint32_t want   = std::max(1u, (s->gravCheckTargets + kWave - 1) / kWave);
+    const uint32_t stride = std::max(1u, (blocks + want / 2) / want);
+    std::vector<uint32_t> grp; // starts, then ends
+    for (uint32_t b = 0; b < blocks; b += stride)
+        grp.push_back(first + b * kWave);
+    const size_t ng = grp.size();
+    for (size_t k = 0; k < ng; ++k)
+        grp.push_back(std::min(grp[k] + (uint32_t)kWave, last));
+    size_t T = 0;
+    for (size_t k = 0; k < ng; ++k)
+        T += grp[ng + k] - grp[k];
+
+    const size_t n    = s->n;
+    float*       acc  = s->work.get<float>("gravcheck.acc", 6 * n);
+    uint8_t*     mask = s->work.get<uint8_t>("gravcheck.mask", n);
+    uint32_t*    dg   = s->work.get<uint32_t>("gravcheck.groups", 2 * ng);
+    double*      eg   = s->work.get<double>("gravcheck.egrav", 1);
+    uint32_t*    er   = s->work.get<uint32_t>("gravcheck.err", 1);
+    if (!acc || !mask || !dg || !eg || !er) return SX_ERR_NOMEM;
+    SIM_HIP(hipMemsetAsync(acc, 0, 6 * n * sizeof(float), st));
+    SIM_HIP(hipMemsetAsync(mask, 0, n, st));
+    for (size_t k = 0; k < ng; ++k)
+        SIM_HIP(hipMemsetAsync(mask + grp[k], 1, grp[ng + k] - grp[k], st));
+    SIM_HIP(hipMemsetAsync(eg, 0, sizeof(double), st));
+    SIM_HIP(hipMemsetAsync(er, 0, sizeof(uint32_t), st));
+    SIM_HIP(hipMemcpyAsync(dg, grp.data(), grp.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+
+    GravArgs ga     = step;
+    ga.ax           = acc;
+    ga.ay           = acc + n;
+    ga.az           = acc + 2 * n;
+    ga.active       = mask;
+    ga.egrav        = eg;
+    ga.waveE        = nullptr;
+    ga.err          = er;
+    ga.interactions = nullptr;
+    SIM_HIP(gravityTraverse(ga, st));
+
+    sx_fields f{};
+    f.n = n;
+    f.x = s->x, f.y = s->y, f.z = s->z, f.m = s->m, f.h = s->h;
+    f.ax = acc + 3 * n, f.ay = acc + 4 * n, f.az = acc + 5 * n;
+    const sx_groups g{0u, 0u, (uint32_t)ng, dg, dg + ng};
+    if (int rc = sx_gravity_direct(s->ctx, &g, &f, &s->box, step.numShells, step.G, nullptr, nullptr)) return rc;
+
+    std::vector<float> hw(3 * T), hd(3 * T);
+    uint32_t           eb = 0;
+    size_t             o  = 0;
+    for (size_t k = 0; k < ng; ++k)
+    {
+        const size_t len = grp[ng + k] - grp[k];
+        for (int c = 0; c < 3; ++c)
+        {
+            SIM_HIP(hipMemcpyAsync(hw.data() + c * T + o, acc + c * n + grp[k], len * sizeof(float),
+                                   hipMemcpyDeviceToHost, st));
+            SIM_HIP(hipMemcpyAsync(hd.data() + c * T + o, acc + (3 + c) * n + grp[k], len * sizeof(float),
+                                   hipMemcpyDeviceToHost, st));
+        }
+        o += len;
+    }
+    SIM_HIP(hipMemcpyAsync(&eb, er, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SIM_HIP(hipStreamSynchronize(st));
+    if (eb)
+    {
+        sx_ctx_set_error_internal(s->ctx, "GPU traversal stack exhausted in Barnes-Hut (gravity check)");
+        return SX_ERR_TRAVERSAL;
+    }
+    std::vector<double> rel(T);
+    double              sum = 0.0, d2 = 0.0, a2 = 0.0;
+    for (size_t t = 0; t < T; ++t)
+    {
+        double dd = 0.0, aa = 0.0;
+        for (int c = 0; c < 3; ++c)
+        {
+            const double w = hw[c * T + t], d = hd[c * T + t];
+            dd += (w - d) * (w - d);
+            aa += d * d;
+        }
+        rel[t] = std::sqrt(dd) / std::sqrt(aa);
+        sum += rel[t];
+        d2 += dd;
+        a2 += aa;
+    }
+    std::sort(rel.begin(), rel.end());
+    s->gravCheck[0]   = (double)T;
+    s->gravCheck[1]   = sum / (double)T;
+    s->gravCheck[2]   = rel[T / 2];
+    s->gravCheck[3]   = rel[std::min(T - 1, (size_t)(0.99 * (double)T))];
+    s->gravCheck[4]   = rel[T - 1];
+    s->gravCheck[5]   = std::sqrt(d2 / a2);
+    s->gravCheckValid = true;
+    return SX_OK;
+}
+
 //! skin lists serve this sim: one rank, not ve-bdt, cluster lists.  With self-gravity a reuse step traverses the last
 //! sync's tree, its multipoles formed from the current positions and its MAC geometry refreshed (cells + particles).
 //! Not with periodic self-gravity: between syncs a particle that crossed a periodic face is wrapped to the far side of
@@ -2287,6 +2390,12 @@ extern "C"
 
     int sx_sim_set_comm(sx_sim* s, sx_comm* c)
     {
+        if (s->gravCheckTargets)
+        {
+            sx_ctx_set_error_internal(s->ctx, "sx_sim_set_comm: the gravity check (sx_sim_set_gravity_check) runs on "
+                                              "one rank");
+            return SX_ERR_ARG;
+        }
         if (s->turb)
         {
             sx_ctx_set_error_internal(s->ctx, "sx_sim_set_comm: a stirred sim (sx_sim_set_turbulence) runs on one rank");
@@ -2537,6 +2646,38 @@ extern "C"
             hipStream_t st = (hipStream_t)sx_ctx_stream_internal(s->ctx);
             SIM_HIP(hipMemsetAsync(s->work.get<unsigned long long>("grav.inter", 2), 0, 16, st));
         }
+        return SX_OK;
+    }
+
+    int sx_sim_set_gravity_check(sx_sim* s, uint32_t numTargets)
+    {
+        if (!s) return SX_ERR_ARG;
+        const char* why = nullptr;
+        if (s->p.g == 0.0) why = "sx_sim_set_gravity_check: the sim has no self-gravity";
+        else if (s->p.propagator == 2)
+            why = "sx_sim_set_gravity_check: not supported with block time-steps (ve-bdt): its substeps walk the "
+                  "active rungs";
+        else if (s->comm)
+            why = "sx_sim_set_gravity_check: the direct sum needs all sources: the check runs on one rank (a "
+                  "communicator is set)";
+        if (why && numTargets) // disarming is always accepted
+        {
+            sx_ctx_set_error_internal(s->ctx, why);
+            return SX_ERR_ARG;
+        }
+        s->gravCheckTargets = numTargets;
+        return SX_OK;
+    }
+
+    int sx_sim_gravity_check(sx_sim* s, double out[6])
+    {
+        if (!s || !out) return SX_ERR_ARG;
+        if (!s->gravCheckValid)
+        {
+            sx_ctx_set_error_internal(s->ctx, "sx_sim_gravity_check: no armed step has run (sx_sim_set_gravity_check)");
+            return SX_ERR_ARG;
+        }
+        std::copy(s->gravCheck, s->gravCheck + 6, out);
         return SX_OK;
     }
 
@@ -3149,6 +3290,11 @@ extern "C"
                 ga.interactions = nullptr;
             }
             SIM_HIP(gravityTraverse(ga, st));
+            if (s->gravCheckTargets)
+            {
+                if (int e = gravityCheck(s, ga, st)) return e;
+                s->gravCheckTargets = 0; // armed for one step
+            }
             if (pbc)
             {
                 double c4[4];

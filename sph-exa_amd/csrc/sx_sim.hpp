@@ -154,6 +154,11 @@ struct sx_sim
     uint32_t* statsHost;
     int       sortBits{30};          // key bits the local sort orders first (sortLocals)
     bool      gravCount = false; // count the gravity interactions (sx_sim_set_gravity_counting)
+    // force-error check of the walk (sx_sim_set_gravity_check): targets of the armed step (0: not armed), the last
+    // armed step's figures
+    uint32_t  gravCheckTargets{0};
+    bool      gravCheckValid{false};
+    double    gravCheck[6]{};
     bool      keysFresh = false; // keys[0, n) hold the current coordinates' SFC keys (set by the position update,
                                  // consumed by the next localSync; cleared by every entry point that sets state)
     uint64_t  sortStats[4]{0, 0, 0, 0}; // sorts requested, done (not the identity), redone on all bits, moved-only

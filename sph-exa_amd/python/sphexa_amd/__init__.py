@@ -299,6 +299,8 @@ def lib():
         "sx_sim_gravity_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         "sx_sim_gravity_interactions": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         "sx_sim_set_gravity_counting": (C.c_int, [vp, C.c_int]),
+        "sx_sim_set_gravity_check": (C.c_int, [vp, u32]),
+        "sx_sim_gravity_check": (C.c_int, [vp, C.POINTER(C.c_double)]),
         "sx_sim_conserved": (C.c_int, [vp, C.POINTER(C.c_double)]),
         "sx_conserved_quantities": (C.c_int, [vp, C.POINTER(SxFields), u32, u32, C.c_float, C.c_double,
                                               C.POINTER(C.c_double)]),
@@ -327,6 +329,10 @@ def lib():
                                               C.POINTER(SxBox), vp, vp, C.c_float, C.c_int, C.POINTER(C.c_double)]),
         "sx_gravity_ewald": (C.c_int, [vp, C.POINTER(SxGroups), C.POINTER(SxFields), C.POINTER(SxBox), vp, vp,
                                        C.c_float, C.POINTER(SxEwaldSettings), C.POINTER(C.c_double)]),
+        "sx_gravity_direct": (C.c_int, [vp, C.POINTER(SxGroups), C.POINTER(SxFields), C.POINTER(SxBox), C.c_int,
+                                        C.c_float, vp, C.POINTER(C.c_double)]),
+        "sx_set_direct_splits": (C.c_int, [vp, u32]),
+        "sx_ctx_direct_targets_per_lane_internal": (C.c_int, [vp, u32]),
         "sx_domain_halo_layout": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, vp, vp]),
         "sx_turb_default_settings": (C.c_int, [C.POINTER(SxTurbSettings)]),
         "sx_turb_create": (C.c_int, [C.POINTER(vp), C.POINTER(SxTurbSettings)]),
@@ -575,6 +581,30 @@ class Context:
         0 for an exact context; tests set it).  Takes effect with the next search; a Sim reads it when it is created."""
         v = 0xffffffff if max_union is None else int(max_union)
         self.check(self.L.sx_set_pack12_max(self.h, v), "sx_set_pack12_max")
+
+    def set_direct_splits(self, k=0):
+        """source splits of gravity_direct (sx_set_direct_splits): 0 is the automatic rule, a k beyond the number of
+        256-source tiles is clamped"""
+        self.check(self.L.sx_set_direct_splits(self.h, int(k)), "sx_set_direct_splits")
+
+    def gravity_direct(self, fields, groups, box=None, num_shells=0, G=1.0, out4=False):
+        """the direct sum over all sources of fields for the targets of groups (sx_gravity_direct: ryoanji::directSum).
+        Adds G acc to fields.ax, ay, az when the three are set; out4=True also returns {G m phi, G ax, G ay, G az} per
+        particle, (n, 4) doubles, zero outside the view.  Returns (egrav, out4 or None)."""
+        n = int(fields.n)
+        d = None
+        if out4:
+            d = self.alloc(4 * n, np.float64)
+            self.check(self.L.sx_memset(self.h, d.ptr, 0, 32 * n), "sx_memset")
+        e = C.c_double(0.0)
+        try:
+            self.check(self.L.sx_gravity_direct(self.h, C.byref(groups), C.byref(fields),
+                                                C.byref(box) if box is not None else None, int(num_shells), float(G),
+                                                d.ptr if d is not None else None, C.byref(e)), "sx_gravity_direct")
+            return e.value, (d.get().reshape(n, 4) if d is not None else None)
+        finally:
+            if d is not None:
+                self.free(d)
 
     # ---- device arrays --------------------------------------------------------------------------------------
     def alloc(self, n, dtype):
@@ -1091,6 +1121,19 @@ class Sim:
     def set_gravity_counting(self, enable=True):
         """count the gravity interactions of the following steps (sx_sim_set_gravity_counting; off by default)"""
         self.ctx.check(self.L.sx_sim_set_gravity_counting(self.h, 1 if enable else 0), "set_gravity_counting")
+
+    def set_gravity_check(self, num_targets=4096):
+        """arm the next step's force-error check of the walk against the direct sum on about num_targets sampled
+        targets (sx_sim_set_gravity_check; 0 disarms)"""
+        self.ctx.check(self.L.sx_sim_set_gravity_check(self.h, int(num_targets)), "set_gravity_check")
+
+    def gravity_check(self):
+        """the last armed step's |a_walk - a_direct| / |a_direct| over the sample (sx_sim_gravity_check)"""
+        out = (C.c_double * 6)()
+        self.ctx.check(self.L.sx_sim_gravity_check(self.h, out), "gravity_check")
+        d = dict(zip(["targets", "mean", "median", "p99", "max", "rms"], list(out)))
+        d["targets"] = int(d["targets"])
+        return d
 
     def gravity_interactions(self):
         """P2P and M2P interactions of the last step (sx_sim_gravity_interactions; the reference's BhStats)"""
