@@ -1,7 +1,7 @@
 """Multi-rank CPU restatement of the SFC domain decomposition + VE step (TEST INFRASTRUCTURE ONLY).
 
 Never imported by the product path: tests/ use it as the checker of the multi-GPU algorithm on the CPU, with
-torch.distributed (gloo) standing in for RCCL.  It runs the same decomposition as sx_sim.cpp (distributedSync and
+torch.distributed (gloo) standing in for RCCL.  It runs the same decomposition as sx_sim_domain.cpp (distributedSync and
 the halo exchanges of sx_sim_step), which replaces the reference's Domain::sync (domain/include/cstone/domain/
 domain.hpp:196-244) and the halo exchanges of HydroVeProp (main/src/propagator/ve_hydro.hpp:150-186):
 
@@ -190,7 +190,7 @@ class DistOracle:
                 pos += c
 
     def _classify(self, nbr, nc, f, l):
-        """interior / boundary clusters as (c0, c1) target ranges (classifyClustersKernel, sx_sim.cpp)"""
+        """interior / boundary clusters as (c0, c1) target ranges (classifyClustersKernel, sx_sim_domain.cpp)"""
         ng = self.p.ngmax
         inner, bound = [], []
         for c0 in range(f, l, self.CLUSTER):
@@ -242,7 +242,7 @@ class DistOracle:
             nbr, nc = ora.find_neighbors(full, box, f, l, bucket=self.bucket, iterate_h=True, ngmax=p.ngmax,
                                          ng0=p.ng0)
             full.nc[f:l] = nc
-            # every local's final h within its chunk's request radius (sx_sim.cpp chunkCheckKernel), decided globally
+            # every local's final h within its chunk's request radius (sx_sim_domain.cpp chunkCheckKernel), decided globally
             hm = np.repeat(self.my_boxes[:, 6], CHUNK)[: l - f]
             bad = torch.tensor([int(np.any(full.h[f:l].astype(np.float64) > hm * margin))], dtype=torch.int64)
             dist.all_reduce(bad, op=dist.ReduceOp.SUM)
@@ -297,7 +297,7 @@ def C_byref(s):
     return ctypes.byref(s)
 
 
-# ---- multi-rank self-gravity (restates distributedGravity, sph-exa_amd/csrc/sx_sim.cpp) ----------------------------
+# ---- multi-rank self-gravity (restates distributedGravity, sph-exa_amd/csrc/sx_sim_gravity.cpp) --------------------
 CELL_SHIFT = 63 - HIST_BITS  # level-6 SFC cells = the splitter bins: one owner per cell
 
 
@@ -425,7 +425,7 @@ def distributed_gravity(d, full, G, theta):
     return acc, eg, stats
 
 
-# ---- skin lists on several ranks: the argument behind reuse steps (sx_skin.hpp, DESIGN 4c, sx_sim.cpp skinHaloRefresh)
+# ---- skin lists on several ranks: the argument behind reuse steps (sx_skin.hpp, DESIGN 4c, sx_sim_skin.cpp skinHaloRefresh)
 
 SKIN_GRID_N = 16  # displacement-grid cells per axis here (the GPU's 64^3; any resolution gives a valid bound)
 
@@ -522,7 +522,7 @@ COVER_RADII = ("rebuilt skin 2h(1+s)", "exact search 2h")
 
 
 def _cover_inside(d, centre, Rt, sel, drift):
-    """coverListKernel (sx_sim.cpp), per target of one re-searched cluster: the sphere of radius Rt, grown by the
+    """coverListKernel (sx_sim_skin.cpp), per target of one re-searched cluster: the sphere of radius Rt, grown by the
     kernel's 1 + 1e-6, the key-quantisation margin and `drift`, around `centre` inside the request box of the target's
     chunk of 2048 locals as the build sent it to the peers (d.my_boxes; minimum image)"""
     qm = quant_margin(d.box)

@@ -4,7 +4,7 @@
  *
  * The host control flow is the reference's; every particle operation is a call through the same seam the reference's
  * propagator calls (sph_gpu.hpp, ts_groups.cu, positions_gpu.cu, MultipoleHolder), i.e. the C-ABI of this library
- * on the context of the simulation, and the domain operations are sx_sim's (sx_sim.cpp):
+ * on the context of the simulation, and the domain operations are sx_sim's (sx_sim_domain.cpp):
  *
  *   sync (:171-218)       substep 0 of a hierarchy: Domain::sync (keys, sort, SFC exchange, halos, tree; the halo
  *                         request radius grows by the haloFactor 1 + numRungs/40, :215) + computeSpatialGroups,

@@ -1,5 +1,5 @@
 /*! @file sx_domain.cpp
- * @brief Host-side decisions of the multi-GPU SFC domain decomposition (sx_sim.cpp distributedSync), exported
+ * @brief Host-side decisions of the multi-GPU SFC domain decomposition (sx_sim_domain.cpp distributedSync), exported
  *        through the C ABI so the same code drives the GPU path and the CPU (gloo) decomposition tests.
  *
  *   sx_domain_splitters   global key histogram -> P+1 SFC splitter keys with equal particle counts per rank;

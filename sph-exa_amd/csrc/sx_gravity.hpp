@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "sx_device.hpp"
+#include "sx_tree.hpp"
 
 namespace sx
 {
@@ -40,6 +41,20 @@ struct GravArgs
     int    numShells;  // periodic images walked per axis on each side (traversal_cpu.hpp:200-216); 0: the box itself
     double boxL[3];    // box lengths (the image shifts)
 };
+
+//! the tree part of the arguments: the linked octree, its particle layout and geometric node boxes
+inline GravArgs gravArgs(const DevTree& t)
+{
+    GravArgs a{};
+    a.numLeaves      = t.numLeaves;
+    a.numNodes       = t.numNodes;
+    a.childOffsets   = t.childOffsets;
+    a.internalToLeaf = t.internalToLeaf;
+    a.layout         = t.layout;
+    a.geoCenters     = t.centers;
+    a.geoSizes       = t.sizes;
+    return a;
+}
 
 //! a level-6 SFC cell of one rank's particles (multi-rank gravity): mass center, MAC radius^2, quadrupole (Cqi
 //! order, q[0] = mass), cell index (key >> 45) and particle count; box: the MAC geometry relative to the cell's

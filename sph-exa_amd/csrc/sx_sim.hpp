@@ -1,6 +1,7 @@
 /*! @file sx_sim.hpp
- * @brief the device-resident simulation object behind sx_sim_* (sx_sim.cpp: HydroVeProp / HydroProp steps and the
- *        SFC domain; sx_bdt.cpp: HydroVeBdtProp substeps on the same domain)
+ * @brief the device-resident simulation object behind sx_sim_* (sx_sim.cpp: HydroVeProp / HydroProp steps;
+ *        sx_sim_domain.cpp: the SFC domain; sx_sim_gravity.cpp: self-gravity; sx_sim_skin.cpp: skin lists;
+ *        sx_bdt.cpp: HydroVeBdtProp substeps on the same domain)
  */
 #pragma once
 
@@ -105,6 +106,50 @@ struct SkinState
     uint64_t  earlyExact{0}; // exact-search clusters searched concurrently with the rebuild of the others
     // the step's second set of exact lists (sel == nullptr unless the step's search was the skin filter)
     sx::ListsB lb{};
+};
+
+/*! Step scratch that one function requests from an arena and others read.  Each arena tag is requested at one site;
+ *  that site stores the pointer here, again every time it runs (a larger request frees and reallocates), and every
+ *  other user reads the member instead of asking the arena by name. */
+
+//! skin-list scratch (sx_sim_skin.cpp)
+struct SkinBuffers
+{
+    // skinReserveDisp: this step's displacement vectors and the displacement grid (position update, filter, refresh)
+    float *   dx{nullptr}, *dy{nullptr}, *dz{nullptr};
+    uint32_t* cells{nullptr};
+    // skinReserveSearch (skinSearch)
+    float *   rel{nullptr}, *hb{nullptr}, *acc{nullptr};
+    uint32_t *sloc{nullptr}, *scnt{nullptr}, *ucountS{nullptr}, *l1{nullptr}, *l2{nullptr}, *l3{nullptr};
+    uint32_t* host{nullptr}; // pinned: the list counts read back
+    uint8_t * streak{nullptr}, *same{nullptr};
+    uint32_t* hitmask{nullptr};
+    float2*   frz{nullptr};
+    uint32_t *nlocB{nullptr}, *ucountB{nullptr}, *hitmaskB{nullptr}; // the second set of exact lists, or nullptr
+    // skinReserveDrift: several ranks -- the drift bounds of coverListKernel and the locals' positions at the build
+    double *drift{nullptr}, *relg{nullptr}, *x0{nullptr}, *y0{nullptr}, *z0{nullptr};
+    float* h0{nullptr}; // h before a reuse step's filter (searchStage)
+};
+
+struct ReqBox; // sx_sim_internal.hpp
+
+//! domain scratch that outlives distributedSync (sx_sim_domain.cpp): all but mybox requested by domReserveComm
+struct DomBuffers
+{
+    uint32_t* bins{nullptr};
+    uint64_t *split{nullptr}, *seg{nullptr}, *cnth{nullptr};
+    uint32_t *agree{nullptr}, *agreeh{nullptr};
+    unsigned *hflag{nullptr}, *hflagh{nullptr}; // hflag: the five words of the step's decision exchange
+    uint32_t* errh{nullptr};
+    ReqBox*   mybox{nullptr}; // this rank's request boxes of the last sync (distributedSync)
+};
+
+//! gravity scratch shared between functions (sx_sim_gravity.cpp)
+struct GravBuffers
+{
+    unsigned long long* inter{nullptr};  // gravReserveInteractions
+    int32_t*            farL2N{nullptr}; // the far tree's leaf map and empty layout, built once (distributedGravity)
+    uint32_t*           farLay{nullptr};
 };
 
 } // namespace sx::sim
@@ -213,6 +258,9 @@ struct sx_sim
 
     sx::sim::BdtState bdt; // propagator 2 only
     sx::sim::SkinState skin;
+    sx::sim::SkinBuffers skinBuf;
+    sx::sim::DomBuffers  dom;
+    sx::sim::GravBuffers grav;
     sx::turb::SimTurb* turb{nullptr}; // turbulence stirring (sx_sim_set_turbulence), VE propagator on one rank
 
     // the observable of sx_sim_observe (observablesFactory, main/src/observables/factory.hpp:46-69)

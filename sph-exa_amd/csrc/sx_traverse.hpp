@@ -18,7 +18,7 @@ constexpr int kQCap = 512;  //!< internal-node ring per wave (power of 2)
 
 /*! Collect every leaf node passing `overlaps` (whose ancestors all pass) into cand[0..return), at most CCap leaves.
  *  Sets `overflow` if the queue or the candidate list ran out of space (the caller reports an error).  The capacity
- *  is a template parameter: the search builds (sx_neighbors.hip) and the halo discovery (sx_sim.cpp) size it
+ *  is a template parameter: the search builds (sx_neighbors.hip) and the halo discovery (sx_sim_domain.cpp) size it
  *  differently, each in its own translation unit.
  *  The queue holds the FIRST CHILD of every passing internal node (childOffsets[node], loaded with the node's own
  *  leaf test), so a step's chain of dependent global loads is one deep: the children's boxes and child offsets.

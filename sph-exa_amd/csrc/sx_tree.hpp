@@ -246,8 +246,8 @@ struct NsArgs
     // per-workgroup hit-mask scratch, searchScratchBytes() bytes
     uint32_t*       work;
     uint64_t*       hitMasks;
-    // > 0: at most this many workgroups in the large build's persistent grid (two searches sharing the GPU, sx_sim.cpp
-    // skinSearch); 0: the whole resident grid
+    // > 0: at most this many workgroups in the large build's persistent grid (two searches sharing the GPU,
+    // sx_sim_skin.cpp skinSearch); 0: the whole resident grid
     uint32_t        maxGrid;
     // optional: the targets' final neighbor records {x, y, z, h, m} (the pair kernels' RecX), written by the search
     // for every target it completes, so no separate packing pass is needed for [first, last)

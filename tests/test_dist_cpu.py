@@ -178,7 +178,7 @@ def test_decomposed_gravity_matches_reference_two_ranks(tmp_path):
 
 @pytest.mark.parametrize("nproc,side,speed", [(2, 14, 0.04), (3, 14, 0.04), (3, 14, 0.12)])
 def test_skin_premise_several_ranks(tmp_path, nproc, side, speed):
-    """the argument behind multi-rank skin lists (sx_sim.cpp skinHaloRefresh; dist_oracle.skin_premise), on gloo
+    """the argument behind multi-rank skin lists (sx_sim_skin.cpp skinHaloRefresh; dist_oracle.skin_premise), on gloo
     ranks: halos requested with the skin radius hold every particle of every local's skin sphere, and with the
     displacement grid reduced over all ranks every cluster the filter's drift bound admits has all its current
     neighbours in its build-time skin lists -- also the particles of other ranks that were no halo at the build.
@@ -207,7 +207,7 @@ CONVERGE_SPEED = 0.16  # spacings per step: six steps carry the patch 0.96 spaci
                                                     (3, 14, "slide", 0.12)])
 def test_skin_research_cover_several_ranks(tmp_path, nproc, side, field, speed):
     """the clusters the drift bound does NOT admit on a reuse step are searched again over the rank's locals and the
-    halos of the last build (sx_sim.cpp coverListKernel; dist_oracle.skin_premise(cover=True)), with the radius of a
+    halos of the last build (sx_sim_skin.cpp coverListKernel; dist_oracle.skin_premise(cover=True)), with the radius of a
     rebuilt skin and of the exact search.  A particle of another rank that was outside the request box at the build
     and has moved in since is no halo: that search cannot see it.  Under the corrected acceptance rule (the sphere
     grown by a bound of every particle's motion since the build inside the build's box, "build-box+drift") no accepted target's

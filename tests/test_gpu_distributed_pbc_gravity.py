@@ -1,7 +1,7 @@
 """Periodic self-gravity with several ranks (the reference composes it in gravity_wrapper.hpp:133-157:
 the Barnes-Hut walk over one shell of periodic images, then the Ewald correction from the global root multipole).
 
-sx_sim's multi-rank gravity (sx_sim.cpp distributedGravity) walks its near tree (locals + gravity halos) and its far
+sx_sim's multi-rank gravity (sx_sim_gravity.cpp distributedGravity) walks its near tree (locals + gravity halos) and its far
 tree (level-6 cell multipoles) over the images; the near/far split tests the cells' images; the Ewald correction takes
 the two trees' combined root.  On the periodic density-wave IC (oracle/pyoracle.py pbc_wave_state, 16^3 particles,
 G = 1), one step on 1 rank (the single-rank image walk) and on 2 and 3 ranks (host-staged transport on one GPU):

@@ -88,7 +88,7 @@ def test_distributed_skin_converging_patch(tmp_path, nproc, port, skin):
     spacings on its boundary with a resting rank, which moves towards that rank, 0.02 spacings in the step before the
     first and up to 1.1 times more with every step.  The re-search of a stale cluster only sees the halos of the last
     full build; a particle that was outside the request box then is no halo however close it has come
-    (sx_sim.cpp coverListKernel: the sphere grown by a bound of the motion since the build must fit the box, or
+    (sx_sim_skin.cpp coverListKernel: the sphere grown by a bound of the motion since the build must fit the box, or
     every rank redoes the step from a full sync).  Same assertions as test_distributed_skin_equals_fresh_search after
     every step.  And the path was taken: the patch's mean drift passes the box's slack over the search sphere plus the
     skin, (kHaloMargin - 1) (1 + s) 2 h + s 2 h; some reuse step served stale clusters (searched them again) with

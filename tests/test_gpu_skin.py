@@ -134,7 +134,7 @@ def _sorted_rows(sim):
 def test_skin_early_exact_search_equals_fresh_search(ctx):
     """Noh's infall at 80^3 (268k particles): from step 6 on some clusters are stale on the step after their rebuild
     and take the exact search on the auxiliary stream, concurrently with the rebuild + filter of the other stale
-    clusters (sx_sim.cpp skinSearch).  Every step's nc and h equal a fresh sync + search's; on each step with such
+    clusters (sx_sim_skin.cpp skinSearch).  Every step's nc and h equal a fresh sync + search's; on each step with such
     clusters the neighbor sets of all particles do too"""
     st, obox = po.noh_state(80)
     box = gutil.box_to_sx(obox)
