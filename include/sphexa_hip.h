@@ -48,6 +48,8 @@
  *   sx_observables         sphexa::gpuGrowthRate, machSquareSumGpu, survivorsGpu  main/src/observables/gpu_reductions.cu:69-168;
  *                                                               d2QuadpoleMomentum grav_waves_calculations.hpp:87-121
  *   sx_sim_observe         IObservables::computeAndWrite        main/src/observables/factory.hpp:46-69
+ *   sx_nbody_positions     computePositions without temp / u    main/src/propagator/nbody.hpp:161, sph/positions.hpp:77-110
+ *   sx_sim_* (propagator 3) one NbodyProp step (computeForces + integrate), main/src/propagator/nbody.hpp:115-163
  *   sx_sim_*               one HydroVeProp step (sync + computeForces + integrate), main/src/propagator/ve_hydro.hpp:132-218
  *
  * Conventions (reference semantics preserved):
@@ -108,8 +110,9 @@ typedef struct sx_params
     double   g;       /* gravitational constant (ParticlesData::g); sx_sim adds self-gravity when != 0 */
     double   eps, etaAcc; /* accelerationTimestep (ts_global.hpp:47-67): 0.005, 0.2 */
     int32_t  propagator;  /* sx_sim only: 0 = ve (HydroVeProp), 1 = std (HydroProp, std_hydro.hpp), 2 = ve-bdt
-                             (HydroVeBdtProp, ve_hydro_bdt.hpp: block time-steps, one substep per sx_sim_step);
-                             factory.hpp:50-84 */
+                             (HydroVeBdtProp, ve_hydro_bdt.hpp: block time-steps, one substep per sx_sim_step),
+                             3 = nbody (NbodyProp, nbody.hpp: gravity only, needs g != 0; no thermal or hydro field is
+                             allocated); factory.hpp:50-84 */
 } sx_params;
 
 /*! Device pointers in sphexa::ParticlesData field order (particles_data.hpp:247-251); NULL where unused.
@@ -307,6 +310,12 @@ int sx_momentum_energy_std(sx_ctx* ctx, const sx_groups* g, const sx_fields* f, 
  *  as in the CPU path (the reference GPU path passes them as float). */
 int sx_positions(sx_ctx* ctx, uint32_t first, uint32_t last, double dt, double dt_m1, const sx_fields* f,
                  double gamma, float muiConst, const sx_box* box);
+/*! the position update of the gravity-only propagator (NbodyProp::integrate, nbody.hpp:161: computePositions with
+ *  neither temp nor u): the Press update of x, v and x_m1 over [first, last) from f->ax, ay, az, the fixed-boundary skip
+ *  (f->h is read only in a box with a fixed axis) and putInBox.  keys (nullable, indexed like the fields): the SFC
+ *  keys of the updated coordinates in box.  No thermal field of f is read or written. */
+int sx_nbody_positions(sx_ctx* ctx, uint32_t first, uint32_t last, double dt, double dt_m1, const sx_fields* f,
+                       const sx_box* box, uint64_t* keys);
 int sx_update_h(sx_ctx* ctx, uint32_t first, uint32_t last, uint32_t ng0, const uint32_t* nc, float* h);
 /*! updateSmoothingLengthGpu over the targets of a group view (update_h_gpu.cu:49-60; ve_hydro_bdt.hpp:369 passes the
  *  active rungs): explicit groups, or fixed 64-blocks of [firstBody, lastBody) when groupStart is NULL */
@@ -530,7 +539,16 @@ int sx_domain_halo_layout(const uint64_t* recvCounts, int nranks, int rank, uint
 typedef struct sx_sim sx_sim;
 /*! a simulation of up to capacity particles in box.  Self-gravity (p->g != 0) in a periodic box: the walk over one
  *  image shell + the Ewald correction with the reference's EwaldSettings defaults (gravity_wrapper.hpp:135-157), one
- *  rank, VE or std propagator (SX_ERR_ARG for ve-bdt; several ranks: at sx_sim_set_comm). */
+ *  rank, VE or std propagator (SX_ERR_ARG for ve-bdt; several ranks: at sx_sim_set_comm).
+ *  Propagator 3 (NbodyProp, gravity only): SX_ERR_ARG when g == 0; a periodic box under the same rule (all three axes
+ *  periodic, cubic).  Only x y z h m, v, x_m1, id (with their sort buffers), keys, the sort order and ax ay az are
+ *  allocated.  Under it sx_sim_set_state ignores temp, du_m1 and alpha (NULL allowed), sx_sim_fields leaves every field
+ *  that is not kept NULL, sx_sim_scalars reads INFINITY for minDtCourant and minDtRho, the hydro stages of
+ *  sx_sim_stage_times read 0, the internal energy of sx_sim_conserved / sx_sim_observe is 0, and sx_sim_kernel_times has
+ *  an eighth entry, nbodyIntegrate.  Refused with SX_ERR_ARG and a reason in sx_last_error: sx_sim_init_sedov,
+ *  sx_sim_set_turbulence, sx_sim_set_skin, sx_sim_rebuild_lists, sx_sim_export_neighbors, sx_sim_last_stats,
+ *  sx_sim_timestep, sx_sim_set_timestep and the observables that need kx or c (SX_OBS_MACH_RMS, SX_OBS_KH_GROWTH,
+ *  SX_OBS_WIND_BUBBLE). */
 int    sx_sim_create(sx_sim** sim, sx_ctx* ctx, size_t capacity, const sx_params* p, const sx_box* box,
                      uint32_t bucketSize);
 void   sx_sim_destroy(sx_sim* sim);
@@ -548,6 +566,8 @@ int    sx_sim_init_sedov_rank(sx_sim* sim, uint32_t side, int rank, int size);
 int    sx_sim_set_overlap(sx_sim* sim, int on);
 /*! interior and boundary cluster counts of the last distributed step (0, 0 without overlap) */
 int    sx_sim_overlap_stats(sx_sim* sim, uint32_t out[2]);
+/*! bytes the sim holds in its arenas: out[0] device memory, out[1] pinned host memory */
+int    sx_sim_memory(sx_sim* sim, uint64_t out[2]);
 /*! local particle range [first,last) and total (with halos) of the last step */
 int    sx_sim_layout(sx_sim* sim, uint64_t out[4]);
 /*! upload a host state (conserved fields, length n) */

@@ -35,6 +35,7 @@
 #include "sx_timestep.hpp"
 
 extern "C" void* sx_ctx_stream_internal(sx_ctx* c);
+extern "C" void  sx_ctx_set_error_internal(sx_ctx* c, const char* msg);
 
 namespace sx::sim
 {
@@ -459,6 +460,8 @@ int stepBdt(sx_sim* s)
 
 extern "C" int sx_sim_timestep(sx_sim* s, sx_timestep* out)
 {
+    if (s && s->p.propagator == 3)
+        sx_ctx_set_error_internal(s->ctx, "sx_sim_timestep: the gravity-only propagator has no block time-steps");
     if (!s || !out || s->p.propagator != 2) return SX_ERR_ARG;
     *out = s->bdt.ts;
     return SX_OK;
@@ -471,6 +474,8 @@ extern "C" int sx_sim_timestep(sx_sim* s, sx_timestep* out)
  *  uninterrupted run's next substep does. */
 extern "C" int sx_sim_set_timestep(sx_sim* s, const sx_timestep* ts, const uint8_t* rung)
 {
+    if (s && s->p.propagator == 3)
+        sx_ctx_set_error_internal(s->ctx, "sx_sim_set_timestep: the gravity-only propagator has no block time-steps");
     if (!s || !ts || s->p.propagator != 2) return SX_ERR_ARG;
     if (ts->numRungs < 1 || ts->numRungs > SX_MAX_RUNGS) return SX_ERR_ARG;
     if (sx::sim::activeRung(ts->substep, ts->numRungs) != 0) return SX_ERR_ARG;

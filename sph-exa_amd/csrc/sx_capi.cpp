@@ -17,6 +17,7 @@
 #include "sx_gravity.hpp"
 #include "sx_hydro.hpp"
 #include "sx_kernel_poly.hpp"
+#include "sx_nbody.hpp"
 #include "sx_observables.hpp"
 #include "sx_tree.hpp"
 #include "sx_timestep.hpp"
@@ -911,6 +912,28 @@ extern "C"
         a.constCv = idealGasCv(muiConst, gamma);
         c->hydro().positions(a, c->stream);
         SX_HIP(c, hipGetLastError());
+        return SX_OK;
+    }
+
+    int sx_nbody_positions(sx_ctx* c, uint32_t first, uint32_t last, double dt, double dt_m1, const sx_fields* f,
+                           const sx_box* box, uint64_t* keys)
+    {
+        if (!c || !f || !box || last < first || last > f->n) return SX_ERR_ARG;
+        if (!f->x || !f->y || !f->z || !f->x_m1 || !f->y_m1 || !f->z_m1 || !f->vx || !f->vy || !f->vz || !f->ax ||
+            !f->ay || !f->az)
+            return SX_ERR_ARG;
+        NbodyPosArgs a{};
+        a.first = first, a.last = last;
+        a.dt = dt, a.dt_m1 = dt_m1;
+        a.box = toDev(box);
+        if ((a.box.fbc[0] || a.box.fbc[1] || a.box.fbc[2]) && !f->h) return SX_ERR_ARG;
+        a.x = f->x, a.y = f->y, a.z = f->z;
+        a.x_m1 = f->x_m1, a.y_m1 = f->y_m1, a.z_m1 = f->z_m1;
+        a.vx = f->vx, a.vy = f->vy, a.vz = f->vz;
+        a.ax = f->ax, a.ay = f->ay, a.az = f->az;
+        a.h    = f->h;
+        a.keys = keys;
+        SX_HIP(c, nbodyIntegrate(a, c->stream));
         return SX_OK;
     }
 

@@ -53,14 +53,15 @@ DevBox toDevBox(const sx_box* b)
 
 //! rhoTimestep (ts_global.hpp:72-94) and the rank-local part of computeTimestep (:97-112)
 //! useRho = 0: the std propagator, which never sets minDtRho (std_hydro.hpp:170-178: stays INFINITY)
+//! useCourant = 0: the gravity-only propagator, which sets minDtCourant = INFINITY (nbody.hpp:158)
 __global__ void dtCandidateKernel(Scalars* s, double Krho, double maxDtIncrease, double g, double eps, double etaAcc,
-                                  int useRho)
+                                  int useRho, int useCourant)
 {
     unsigned u = s->maxDivvU;
     u          = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
     float maxDivv   = __uint_as_float(u);
     s->minDtRho     = useRho ? Krho / (double)fabsf(maxDivv) : INFINITY;
-    s->minDtCourant = (double)s->courant;
+    s->minDtCourant = useCourant ? (double)s->courant : INFINITY;
     double minDtAcc = INFINITY;
     if (g != 0.0) minDtAcc = etaAcc * sqrt(eps / sqrt(__longlong_as_double((long long)s->maxAccSqBits)));
     double m       = INFINITY;
@@ -125,10 +126,13 @@ namespace sx::sim
 void allocFields(sx_sim* s, size_t cap)
 {
     auto& a  = s->mem;
+    // the gravity-only propagator (NbodyProp, nbody.hpp:74-77) keeps x y z h m, v, x_m1, a and keys: no thermal
+    // field, no hydro dependent field, no packed records and no neighbor lists are requested for it
+    const bool hydro = s->p.propagator != 3;
     s->x     = a.get<double>("x", cap);
     s->y     = a.get<double>("y", cap);
     s->z     = a.get<double>("z", cap);
-    s->temp  = a.get<double>("temp", cap);
+    s->temp  = hydro ? a.get<double>("temp", cap) : nullptr;
     s->h     = a.get<float>("h", cap);
     s->m     = a.get<float>("m", cap);
     s->vx    = a.get<float>("vx", cap);
@@ -137,30 +141,30 @@ void allocFields(sx_sim* s, size_t cap)
     s->xm1   = a.get<float>("x_m1", cap);
     s->ym1   = a.get<float>("y_m1", cap);
     s->zm1   = a.get<float>("z_m1", cap);
-    s->dum1  = a.get<float>("du_m1", cap);
-    s->alpha = a.get<float>("alpha", cap);
+    s->dum1  = hydro ? a.get<float>("du_m1", cap) : nullptr;
+    s->alpha = hydro ? a.get<float>("alpha", cap) : nullptr;
     s->id    = a.get<uint64_t>("id", cap);
     s->keys  = a.get<uint64_t>("keys", cap);
     s->order = a.get<uint32_t>("order", cap);
-    s->nc    = a.get<uint32_t>("nc", cap);
-    s->xm    = a.get<float>("xm", cap);
-    s->kx    = a.get<float>("kx", cap);
-    s->gradh = a.get<float>("gradh", cap);
-    s->prho  = a.get<float>("prho", cap);
-    s->c     = a.get<float>("c", cap);
-    s->divv  = a.get<float>("divv", cap);
-    s->curlv = a.get<float>("curlv", cap);
-    s->c11   = a.get<float>("c11", cap);
-    s->c12   = a.get<float>("c12", cap);
-    s->c13   = a.get<float>("c13", cap);
-    s->c22   = a.get<float>("c22", cap);
-    s->c23   = a.get<float>("c23", cap);
-    s->c33   = a.get<float>("c33", cap);
+    s->nc    = hydro ? a.get<uint32_t>("nc", cap) : nullptr;
+    s->xm    = hydro ? a.get<float>("xm", cap) : nullptr;
+    s->kx    = hydro ? a.get<float>("kx", cap) : nullptr;
+    s->gradh = hydro ? a.get<float>("gradh", cap) : nullptr;
+    s->prho  = hydro ? a.get<float>("prho", cap) : nullptr;
+    s->c     = hydro ? a.get<float>("c", cap) : nullptr;
+    s->divv  = hydro ? a.get<float>("divv", cap) : nullptr;
+    s->curlv = hydro ? a.get<float>("curlv", cap) : nullptr;
+    s->c11   = hydro ? a.get<float>("c11", cap) : nullptr;
+    s->c12   = hydro ? a.get<float>("c12", cap) : nullptr;
+    s->c13   = hydro ? a.get<float>("c13", cap) : nullptr;
+    s->c22   = hydro ? a.get<float>("c22", cap) : nullptr;
+    s->c23   = hydro ? a.get<float>("c23", cap) : nullptr;
+    s->c33   = hydro ? a.get<float>("c33", cap) : nullptr;
     s->ax    = a.get<float>("ax", cap);
     s->ay    = a.get<float>("ay", cap);
     s->az    = a.get<float>("az", cap);
-    s->du    = a.get<double>("du", cap);
-    if (s->p.avClean)
+    s->du    = hydro ? a.get<double>("du", cap) : nullptr;
+    if (hydro && s->p.avClean)
     {
         // GradVFields, allocated only with avClean (ve_hydro.hpp:80-85)
         s->dV[0] = a.get<float>("dV11", cap);
@@ -175,13 +179,16 @@ void allocFields(sx_sim* s, size_t cap)
         s->rho  = a.get<float>("rho", cap);
         s->pres = a.get<float>("p", cap);
     }
-    s->rx    = a.get<RecX>("rx", cap);
-    s->rv    = a.get<RecV>("rv", cap);
-    s->rt    = a.get<RecT>("rt", cap);
+    s->rx    = hydro ? a.get<RecX>("rx", cap) : nullptr;
+    s->rv    = hydro ? a.get<RecV>("rv", cap) : nullptr;
+    s->rt    = hydro ? a.get<RecT>("rt", cap) : nullptr;
     s->rs    = reinterpret_cast<RecS*>(s->rt);
-    s->rc    = a.get<RecC>("rc", cap);
+    s->rc    = hydro ? a.get<RecC>("rc", cap) : nullptr;
+    // a field the propagator does not keep has no spare either: the sort, the particle exchange and the halo moves
+    // go over this list
     auto spare = [&](auto*& field, const char* tag) {
         using T = std::remove_reference_t<decltype(*field)>;
+        if (!field) return;
         s->spares.push_back(
             {reinterpret_cast<void**>(&field), a.get<T>(std::string(tag) + ".alt", cap), (int)sizeof(T)});
     };
@@ -205,7 +212,7 @@ void allocFields(sx_sim* s, size_t cap)
         s->rung = a.get<uint8_t>("rung", cap);
         spare(s->rung, "rung");
     }
-    s->nb.reserve(a, 0, (uint32_t)cap, s->p.ngmax, true);
+    if (hydro) s->nb.reserve(a, 0, (uint32_t)cap, s->p.ngmax, true);
     s->stats      = a.get<uint32_t>("stats", kStatsWords);
     s->statsHost  = a.pinned<uint32_t>("statsHost", kStatsWords);
     s->clsHost    = a.pinned<uint32_t>("ovl.countHost", 2);
@@ -408,6 +415,19 @@ int turbStep(sx_sim* s, hipStream_t st)
         SIM_HIP(hipMemsetAsync(&s->sc->maxAccSqBits, 0, sizeof(unsigned long long), st));
         maxAccSq(s, st);
     }
+    return SX_OK;
+}
+
+// ---- the step's scalars (shared with the gravity-only step, sx_sim_nbody.cpp) ---------------------------------------
+
+void resetStepScalars(sx_sim* s, hipStream_t st) { resetScalarsKernel<<<1, 1, 0, st>>>(s->sc); }
+
+int globalTimestep(sx_sim* s, bool dist, hipStream_t st)
+{
+    dtCandidateKernel<<<1, 1, 0, st>>>(s->sc, s->p.Krho, s->p.maxDtIncrease, s->p.g, s->p.eps, s->p.etaAcc,
+                                       s->p.propagator != 1 && s->p.propagator != 3, s->p.propagator != 3);
+    if (dist) SIM_COMM(s->comm->allreduceMinF64(&s->sc->dtCand, 1, st));
+    dtApplyKernel<<<1, 1, 0, st>>>(s->sc);
     return SX_OK;
 }
 
@@ -851,10 +871,7 @@ int forcesVe(sx_sim* s, StepCtx& c, PairArgs pa)
 int integrateStage(sx_sim* s, StepCtx& c)
 {
     hipStream_t st = c.st;
-    dtCandidateKernel<<<1, 1, 0, st>>>(s->sc, s->p.Krho, s->p.maxDtIncrease, s->p.g, s->p.eps, s->p.etaAcc,
-                                       s->p.propagator != 1);
-    if (c.dist) SIM_COMM(s->comm->allreduceMinF64(&s->sc->dtCand, 1, st));
-    dtApplyKernel<<<1, 1, 0, st>>>(s->sc);
+    if (int e = globalTimestep(s, c.dist, st)) return e;
     PosArgs qa{};
     qa.first   = (uint32_t)s->first;
     qa.last    = (uint32_t)s->last;
@@ -944,10 +961,10 @@ int finishStep(sx_sim* s, const StepCtx& c)
 
 } // namespace
 
-//! one VE or std step (ve-bdt: sx_bdt.cpp)
+//! one VE or std step (ve-bdt: sx_bdt.cpp; gravity only: sx_sim_nbody.cpp)
 static int stepImpl(sx_sim* s)
 {
-    if (s->p.propagator == 2) return stepBdt(s);
+    if (s->p.propagator >= 2) return s->p.propagator == 2 ? stepBdt(s) : stepNbody(s);
     StepCtx c{(hipStream_t)sx_ctx_stream_internal(s->ctx),
               sx_ctx_exact_internal(s->ctx) ? hydro_exact() : hydro_fast(),
               s->comm && s->comm->size() > 1, /*skinOn*/ skinUsable(s), /*reuse*/ false, /*ev*/ 0, /*powTab*/ nullptr};
@@ -983,13 +1000,26 @@ static int stepImpl(sx_sim* s)
 
 } // namespace sx::sim
 
+//! the gravity-only propagator has no neighbor lists, skins, rungs or stirring: SX_ERR_ARG with the reason
+static bool refusedForNbody(sx_sim* s, const char* why)
+{
+    if (!s || s->p.propagator != 3) return false;
+    sx_ctx_set_error_internal(s->ctx, why);
+    return true;
+}
+
 extern "C"
 {
 
     int sx_sim_create(sx_sim** out, sx_ctx* ctx, size_t capacity, const sx_params* p, const sx_box* box,
                       uint32_t bucketSize)
     {
-        if (p->propagator < 0 || p->propagator > 2) return SX_ERR_ARG;
+        if (p->propagator < 0 || p->propagator > 3) return SX_ERR_ARG;
+        if (p->propagator == 3 && p->g == 0.0)
+        {
+            sx_ctx_set_error_internal(ctx, "sx_sim_create: the gravity-only propagator (3) needs g != 0");
+            return SX_ERR_ARG;
+        }
         // self-gravity in a periodic box: the image walk + Ewald correction of the VE / std step (single rank).  The
         // reference decides on boundaryX alone (gravity_wrapper.hpp:77,135) and walks images along all three axes;
         // here a mixed box (some axes periodic, some not) is refused rather than given images along open axes, the
@@ -1025,6 +1055,7 @@ extern "C"
         const char* knames[] = {"findNeighbors", "xmass",          "veDefGradh", "iadDivvCurlv",
                                 "avSwitches",    "momentumEnergy", "gravity"};
         s->kernelNames.assign(std::begin(knames), std::end(knames));
+        if (p->propagator == 3) s->kernelNames.push_back("nbodyIntegrate");
         s->kev.resize(2 * s->kernelNames.size());
         for (auto& e : s->kev)
             (void)hipEventCreate(&e);
@@ -1112,6 +1143,7 @@ extern "C"
     int sx_sim_set_skin(sx_sim* s, float factor, int maxReuse)
     {
         if (!s || !(factor >= 0.0f) || factor > 1.0f || maxReuse < 1) return SX_ERR_ARG;
+        if (refusedForNbody(s, "sx_sim_set_skin: the gravity-only propagator has no neighbor lists")) return SX_ERR_ARG;
         s->skin.factor   = factor;
         s->skin.cur      = factor;
         s->skin.built    = factor;
@@ -1123,6 +1155,8 @@ extern "C"
     int sx_sim_rebuild_lists(sx_sim* s)
     {
         if (!s) return SX_ERR_ARG;
+        if (refusedForNbody(s, "sx_sim_rebuild_lists: the gravity-only propagator has no neighbor lists"))
+            return SX_ERR_ARG;
         s->skin.forceBuild = true;
         return SX_OK;
     }
@@ -1141,6 +1175,8 @@ extern "C"
     int sx_sim_export_neighbors(sx_sim* s, uint32_t* out)
     {
         if (!s || !out) return SX_ERR_ARG;
+        if (refusedForNbody(s, "sx_sim_export_neighbors: the gravity-only propagator has no neighbor lists"))
+            return SX_ERR_ARG;
         if (s->nb.first != s->first || s->nb.last != s->last || s->nb.ngmax != s->p.ngmax) return SX_ERR_ARG;
         NsArgs a = listArgs(s);
         a.lb     = s->skin.lb; // the lists the last step's pair kernels read
@@ -1161,8 +1197,20 @@ extern "C"
         return SX_OK;
     }
 
+    int sx_sim_memory(sx_sim* s, uint64_t out[2])
+    {
+        if (!s || !out) return SX_ERR_ARG;
+        out[0] = out[1] = 0;
+        for (const sx::Arena* a : {&s->mem, &s->work, &s->farMem, &s->gravWork})
+            out[0] += a->bytesAllocated(), out[1] += a->bytesPinned();
+        return SX_OK;
+    }
+
     int sx_sim_init_sedov_rank(sx_sim* s, uint32_t side, int rank, int size)
     {
+        if (refusedForNbody(s, "sx_sim_init_sedov: the Sedov blast needs the thermal fields the gravity-only "
+                               "propagator does not keep"))
+            return SX_ERR_ARG;
         s->keysFresh  = false;
         s->skin.valid = false;
         size_t N  = (size_t)side * side * side;
@@ -1214,15 +1262,16 @@ extern "C"
         SIM_HIP(cp(s->z, z, 8));
         SIM_HIP(cp(s->h, h, 4));
         SIM_HIP(cp(s->m, m, 4));
-        SIM_HIP(cp(s->temp, temp, 8));
+        // the gravity-only propagator keeps no temp, du_m1, alpha: the arguments may be NULL and are ignored
+        if (s->temp) SIM_HIP(cp(s->temp, temp, 8));
         SIM_HIP(cp(s->vx, vx, 4));
         SIM_HIP(cp(s->vy, vy, 4));
         SIM_HIP(cp(s->vz, vz, 4));
         SIM_HIP(cp(s->xm1, x_m1, 4));
         SIM_HIP(cp(s->ym1, y_m1, 4));
         SIM_HIP(cp(s->zm1, z_m1, 4));
-        SIM_HIP(cp(s->dum1, du_m1, 4));
-        SIM_HIP(cp(s->alpha, alpha, 4));
+        if (s->dum1) SIM_HIP(cp(s->dum1, du_m1, 4));
+        if (s->alpha) SIM_HIP(cp(s->alpha, alpha, 4));
         SIM_HIP(cp(s->id, id, 8));
         if (s->rung) SIM_HIP(hipMemset(s->rung, 0, n));
         s->bdt.started = false;
@@ -1236,43 +1285,45 @@ extern "C"
         // pointers to the LOCAL particles [first, last) of the last step
         std::memset(f, 0, sizeof(*f));
         size_t o = s->first;
+        // a field the propagator does not keep is NULL (the gravity-only propagator: every thermal and hydro field)
+        auto at = [o](auto* p) { return p ? p + o : nullptr; };
         f->n     = s->last - s->first;
-        f->x     = s->x + o;
-        f->y     = s->y + o;
-        f->z     = s->z + o;
-        f->x_m1  = s->xm1 + o;
-        f->y_m1  = s->ym1 + o;
-        f->z_m1  = s->zm1 + o;
-        f->vx    = s->vx + o;
-        f->vy    = s->vy + o;
-        f->vz    = s->vz + o;
-        f->prho  = s->prho + o;
-        f->rho   = s->rho ? s->rho + o : nullptr;
-        f->p     = s->pres ? s->pres + o : nullptr;
-        f->h     = s->h + o;
-        f->m     = s->m + o;
-        f->c     = s->c + o;
-        f->ax    = s->ax + o;
-        f->ay    = s->ay + o;
-        f->az    = s->az + o;
-        f->du    = s->du + o;
-        f->du_m1 = s->dum1 + o;
-        f->c11   = s->c11 + o;
-        f->c12   = s->c12 + o;
-        f->c13   = s->c13 + o;
-        f->c22   = s->c22 + o;
-        f->c23   = s->c23 + o;
-        f->c33   = s->c33 + o;
-        f->temp  = s->temp + o;
-        f->xm    = s->xm + o;
-        f->kx    = s->kx + o;
-        f->divv  = s->divv + o;
-        f->curlv = s->curlv + o;
-        f->alpha = s->alpha + o;
-        f->gradh = s->gradh + o;
-        f->keys  = s->keys + o;
-        f->nc    = s->nc + o;
-        f->rung  = s->rung ? s->rung + o : nullptr;
+        f->x     = at(s->x);
+        f->y     = at(s->y);
+        f->z     = at(s->z);
+        f->x_m1  = at(s->xm1);
+        f->y_m1  = at(s->ym1);
+        f->z_m1  = at(s->zm1);
+        f->vx    = at(s->vx);
+        f->vy    = at(s->vy);
+        f->vz    = at(s->vz);
+        f->prho  = at(s->prho);
+        f->rho   = at(s->rho);
+        f->p     = at(s->pres);
+        f->h     = at(s->h);
+        f->m     = at(s->m);
+        f->c     = at(s->c);
+        f->ax    = at(s->ax);
+        f->ay    = at(s->ay);
+        f->az    = at(s->az);
+        f->du    = at(s->du);
+        f->du_m1 = at(s->dum1);
+        f->c11   = at(s->c11);
+        f->c12   = at(s->c12);
+        f->c13   = at(s->c13);
+        f->c22   = at(s->c22);
+        f->c23   = at(s->c23);
+        f->c33   = at(s->c33);
+        f->temp  = at(s->temp);
+        f->xm    = at(s->xm);
+        f->kx    = at(s->kx);
+        f->divv  = at(s->divv);
+        f->curlv = at(s->curlv);
+        f->alpha = at(s->alpha);
+        f->gradh = at(s->gradh);
+        f->keys  = at(s->keys);
+        f->nc    = at(s->nc);
+        f->rung  = at(s->rung);
         if (s->dV[0])
         {
             f->dV11 = s->dV[0] + o, f->dV12 = s->dV[1] + o, f->dV13 = s->dV[2] + o;
@@ -1384,6 +1435,9 @@ extern "C"
             why = "kx was empty. KHGrowthRate only supported with volume elements (--prop ve)";
         else if (kind == kObsWindBubble && s->p.propagator == 1)
             why = "kx was empty. Wind Shock surviving fraction is only supported with volume elements (--prop ve)";
+        else if (s->p.propagator == 3 && kind != kObsTimeEnergy && kind != kObsGravWaves)
+            why = "sx_sim_set_observable: the gravity-only propagator keeps neither kx nor c (time_energy and "
+                  "grav_waves are supported)";
         if (why)
         {
             sx_ctx_set_error_internal(s->ctx, why);
@@ -1531,6 +1585,8 @@ extern "C"
 
     int sx_sim_last_stats(sx_sim* s, sx_nbstats* st)
     {
+        if (refusedForNbody(s, "sx_sim_last_stats: the gravity-only propagator does no neighbor search"))
+            return SX_ERR_ARG;
         *st = s->lastStats;
         return SX_OK;
     }
@@ -1542,6 +1598,8 @@ extern "C"
         if (!s) return SX_ERR_ARG;
         const char* why = nullptr;
         if (!set) why = "sx_sim_set_turbulence: no settings";
+        else if (s->p.propagator == 3) why = "sx_sim_set_turbulence: the gravity-only propagator is not stirred (the "
+                                             "reference stirs the VE propagators, turb_ve.hpp)";
         else if (s->p.propagator == 1) why = "sx_sim_set_turbulence: the std propagator has no stirred counterpart "
                                              "(the reference stirs the VE propagators, turb_ve.hpp)";
         else if (s->p.propagator == 2) why = "sx_sim_set_turbulence: stirring with block time-steps (ve-bdt) is not "

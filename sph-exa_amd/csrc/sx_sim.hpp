@@ -1,7 +1,7 @@
 /*! @file sx_sim.hpp
  * @brief the device-resident simulation object behind sx_sim_* (sx_sim.cpp: HydroVeProp / HydroProp steps;
  *        sx_sim_domain.cpp: the SFC domain; sx_sim_gravity.cpp: self-gravity; sx_sim_skin.cpp: skin lists;
- *        sx_bdt.cpp: HydroVeBdtProp substeps on the same domain)
+ *        sx_bdt.cpp: HydroVeBdtProp substeps on the same domain; sx_sim_nbody.cpp: the gravity-only NbodyProp step)
  */
 #pragma once
 
@@ -300,8 +300,16 @@ int ewaldStep(sx_sim* s, const double c4[4], const float m8[8], const uint8_t* a
 //! max |a|^2 of the locals into the device scalars (accelerationTimestep)
 void maxAccSq(sx_sim* s, hipStream_t st);
 
+//! the step's accumulators (courant, maxDivvU, egrav, maxAccSqBits, gravErr) back to their start values
+void resetStepScalars(sx_sim* s, hipStream_t st);
+//! computeTimestep (ts_global.hpp:97-112) on the device scalars: the rank's candidate, its minimum over the ranks,
+//! then ttot, minDt_m1, minDt
+int globalTimestep(sx_sim* s, bool dist, hipStream_t st);
+
 //! HydroVeBdtProp: one substep of the block time-step hierarchy (sx_bdt.cpp)
 int stepBdt(sx_sim* s);
+//! NbodyProp: one gravity-only step (sx_sim_nbody.cpp)
+int stepNbody(sx_sim* s);
 //! ve-bdt buffers (called by sx_sim_create for propagator 2)
 int allocBdt(sx_sim* s);
 

@@ -57,8 +57,11 @@ __global__ void packPRecKernel(Fields f, size_t n, PRec* out)
     if (i >= n) return;
     // ve-bdt: the rung rides in the top byte of the id slot (particle ids < 2^56)
     const uint64_t id = f.rung ? (f.id[i] | (uint64_t)f.rung[i] << 56) : f.id[i];
-    out[i] = PRec{f.x[i],   f.y[i],   f.z[i],   f.temp[i], f.h[i],    f.m[i],     f.vx[i], f.vy[i],
-                  f.vz[i],  f.xm1[i], f.ym1[i], f.zm1[i],  f.dum1[i], f.alpha[i], id};
+    // the gravity-only propagator has no temp, du_m1, alpha (null members): their slots travel as zeros
+    const double temp = f.temp ? f.temp[i] : 0.0;
+    const float  dum1 = f.dum1 ? f.dum1[i] : 0.0f, alpha = f.alpha ? f.alpha[i] : 0.0f;
+    out[i] = PRec{f.x[i],   f.y[i],   f.z[i],   temp,     f.h[i], f.m[i], f.vx[i], f.vy[i],
+                  f.vz[i],  f.xm1[i], f.ym1[i], f.zm1[i], dum1,   alpha,  id};
 }
 
 __global__ void unpackPRecKernel(const PRec* in, size_t n, Fields f)
@@ -69,7 +72,7 @@ __global__ void unpackPRecKernel(const PRec* in, size_t n, Fields f)
     f.x[i]    = r.x;
     f.y[i]    = r.y;
     f.z[i]    = r.z;
-    f.temp[i] = r.temp;
+    if (f.temp) f.temp[i] = r.temp;
     f.h[i]    = r.h;
     f.m[i]    = r.m;
     f.vx[i]   = r.vx;
@@ -78,8 +81,8 @@ __global__ void unpackPRecKernel(const PRec* in, size_t n, Fields f)
     f.xm1[i]  = r.xm1;
     f.ym1[i]  = r.ym1;
     f.zm1[i]  = r.zm1;
-    f.dum1[i] = r.dum1;
-    f.alpha[i] = r.alpha;
+    if (f.dum1) f.dum1[i] = r.dum1;
+    if (f.alpha) f.alpha[i] = r.alpha;
     f.id[i]   = f.rung ? r.id & ((1ull << 56) - 1) : r.id;
     if (f.rung) f.rung[i] = (uint8_t)(r.id >> 56);
 }

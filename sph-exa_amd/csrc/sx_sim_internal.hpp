@@ -1,6 +1,7 @@
 /*! @file sx_sim_internal.hpp
  * @brief what the translation units of the step driver share beyond sx_sim.hpp: sx_sim.cpp (C API, step orchestrator),
- *        sx_sim_domain.cpp (SFC domain), sx_sim_gravity.cpp (self-gravity), sx_sim_skin.cpp (skin-list driver)
+ *        sx_sim_domain.cpp (SFC domain), sx_sim_gravity.cpp (self-gravity), sx_sim_skin.cpp (skin-list driver),
+ *        sx_sim_nbody.cpp (gravity-only step)
  */
 #pragma once
 
@@ -20,6 +21,7 @@
 #include "sx_comm.hpp"
 #include "sx_gravity.hpp"
 #include "sx_hydro.hpp"
+#include "sx_nbody.hpp"
 #include "sx_observables.hpp"
 #include "sx_sim.hpp"
 #include "sx_skin.hpp"

@@ -1,0 +1,91 @@
+/*! @file sx_sim_nbody.cpp
+ * @brief The gravity-only step of sx_sim (propagator 3): NbodyProp::computeForces + integrate
+ *        (main/src/propagator/nbody.hpp:115-163) on one GPU or SFC-decomposed over several.
+ *
+ * Step = sync -> a = 0 -> upsweep + walk (+ Ewald in a periodic box) -> acceleration time-step, min over the ranks
+ *        -> positions.  The sync, the gravity stage and the time-step are the VE step's (sx_sim_domain.cpp,
+ *        sx_sim_gravity.cpp, globalTimestep); the position update is nbodyIntegrateKernel (sx_nbody.hip), which touches
+ *        no thermal field.  h is never updated, as in the reference.
+ *
+ * Several ranks: distributedSync as it is.  Its SPH halo discovery (request boxes grown by 2 h, here twice the
+ * softening length) is kept although the walk does not read those halos: the request boxes it leaves (DomBuffers::mybox)
+ * are what distributedGravity classifies near and far cells against, and with h a softening length the halos are few.
+ * The halo masses are not overwritten with m[first] (nbody.hpp:127-129): gravity halos carry their own mass.
+ *
+ * Stage times keep the VE step's names and order (consumers index by position): "sync", "Gravity" and
+ * "UpdateQuantities" are timed, the hydro stages read 0.
+ */
+#include "sx_sim_internal.hpp"
+
+using namespace sx;
+using namespace sx::sim;
+
+namespace sx::sim
+{
+
+int stepNbody(sx_sim* s)
+{
+    hipStream_t st   = (hipStream_t)sx_ctx_stream_internal(s->ctx);
+    const bool  dist = s->comm && s->comm->size() > 1;
+    // stage events: [0] start, [1] after the sync, [2 .. 8] the hydro stages (empty), [9] after gravity, [10] the end
+    const size_t nStages = s->stageNames.size();
+    SIM_HIP(hipEventRecord(s->ev[0], st));
+    // kernel events: every hot kernel of the VE step but gravity is an empty interval
+    for (size_t k = 0; k < 12; ++k)
+        SIM_HIP(hipEventRecord(s->kev[k], st));
+
+    // ---- sync: keys, sort, tree (nbody.hpp:118)
+    if (int e = dist ? distributedSync(s, st, kHaloMargin) : localSync(s, st)) return e;
+    for (size_t k = 1; k + 1 < nStages; ++k)
+        SIM_HIP(hipEventRecord(s->ev[k], st));
+
+    // ---- computeForces: a = 0 for the locals, then upsweep and walk add G acc (nbody.hpp:131-138)
+    resetStepScalars(s, st);
+    const size_t nl = s->last - s->first;
+    if (nl)
+    {
+        SIM_HIP(hipMemsetAsync(s->ax + s->first, 0, nl * sizeof(float), st));
+        SIM_HIP(hipMemsetAsync(s->ay + s->first, 0, nl * sizeof(float), st));
+        SIM_HIP(hipMemsetAsync(s->az + s->first, 0, nl * sizeof(float), st));
+    }
+    SIM_HIP(hipEventRecord(s->kev[12], st));
+    if (int e = gravityStage(s, st, dist, false)) return e;
+    SIM_HIP(hipEventRecord(s->kev[13], st));
+    SIM_HIP(hipEventRecord(s->ev[nStages - 1], st));
+
+    // ---- integrate: minDtCourant = INFINITY, computeTimestep, computePositions (nbody.hpp:152-163)
+    if (int e = globalTimestep(s, dist, st)) return e;
+    NbodyPosArgs qa{};
+    qa.first = (uint32_t)s->first, qa.last = (uint32_t)s->last;
+    qa.dtPtr = &s->sc->minDt;
+    qa.box   = s->dbox;
+    qa.x = s->x, qa.y = s->y, qa.z = s->z;
+    qa.x_m1 = s->xm1, qa.y_m1 = s->ym1, qa.z_m1 = s->zm1;
+    qa.vx = s->vx, qa.vy = s->vy, qa.vz = s->vz;
+    qa.ax = s->ax, qa.ay = s->ay, qa.az = s->az;
+    qa.h  = s->h;
+    // one rank: the next localSync's keys come from this pass (the coordinates are in registers here)
+    qa.keys = dist ? nullptr : s->keys;
+    SIM_HIP(hipEventRecord(s->kev[14], st));
+    SIM_HIP(nbodyIntegrate(qa, st));
+    SIM_HIP(hipEventRecord(s->kev[15], st));
+    s->keysFresh = qa.keys != nullptr;
+    SIM_HIP(hipEventRecord(s->ev[nStages], st));
+
+    // ---- the end of the step: wait for it, stage and kernel times, the walk's error flag
+    SIM_HIP(hipGetLastError());
+    SIM_HIP(hipStreamSynchronize(st));
+    for (size_t k = 0; k < s->stageMs.size(); ++k)
+        (void)hipEventElapsedTime(&s->stageMs[k], s->ev[k], s->ev[k + 1]);
+    for (size_t k = 0; k < s->kernelMs.size(); ++k)
+        (void)hipEventElapsedTime(&s->kernelMs[k], s->kev[2 * k], s->kev[2 * k + 1]);
+    SIM_HIP(hipMemcpy(s->scHost, s->sc, sizeof(Scalars), hipMemcpyDeviceToHost));
+    if (s->scHost->gravErr)
+    {
+        fprintf(stderr, "sx_sim_step: GPU traversal stack exhausted in Barnes-Hut\n");
+        return SX_ERR_TRAVERSAL;
+    }
+    return SX_OK;
+}
+
+} // namespace sx::sim

@@ -37,6 +37,13 @@ public:
             if (!kv.second.host) s += kv.second.bytes;
         return s;
     }
+    size_t bytesPinned() const
+    {
+        size_t s = 0;
+        for (auto& kv : bufs_)
+            if (kv.second.host) s += kv.second.bytes;
+        return s;
+    }
     void release()
     {
         for (auto& kv : bufs_)

@@ -281,6 +281,8 @@ def lib():
                                              C.POINTER(SxBox), C.POINTER(C.c_float)]),
         "sx_positions": (C.c_int, [vp, u32, u32, C.c_double, C.c_double, C.POINTER(SxFields), C.c_double,
                                    C.c_float, C.POINTER(SxBox)]),
+        "sx_nbody_positions": (C.c_int, [vp, u32, u32, C.c_double, C.c_double, C.POINTER(SxFields), C.POINTER(SxBox),
+                                         vp]),
         "sx_update_h": (C.c_int, [vp, u32, u32, u32, vp, vp]),
         "sx_update_h_groups": (C.c_int, [vp, vp, u32, vp, vp]),
         "sx_max_divv": (C.c_int, [vp, u32, u32, vp, C.POINTER(C.c_float)]),
@@ -306,6 +308,7 @@ def lib():
                                               C.POINTER(C.c_double)]),
         "sx_sim_init_sedov_rank": (C.c_int, [vp, u32, C.c_int, C.c_int]),
         "sx_sim_layout": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        "sx_sim_memory": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         "sx_sim_set_overlap": (C.c_int, [vp, C.c_int]),
         "sx_sim_overlap_stats": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
         "sx_sim_timestep": (C.c_int, [vp, C.POINTER(SxTimestep)]),
@@ -398,19 +401,19 @@ def halo_layout(recv_counts, rank, num_local):
     return off, tuple(int(v) for v in out)
 
 
-def default_params(K=None, ngmax=150, ng0=100, av_clean=False, g=0.0, theta=0.5, std=False, bdt=False):
+def default_params(K=None, ngmax=150, ng0=100, av_clean=False, g=0.0, theta=0.5, std=False, bdt=False, nbody=False):
     """ParticlesData defaults (particles_data.hpp:86-138); av_clean selects HydroVeProp<true> (with bdt:
-    HydroVeBdtProp<true>), std the std propagator (HydroProp) and bdt the block time-step VE propagator
-    (HydroVeBdtProp, one substep per step) in sx_sim."""
-    if std and bdt:
-        raise ValueError("std and bdt are different propagators")
+    HydroVeBdtProp<true>), std the std propagator (HydroProp), bdt the block time-step VE propagator
+    (HydroVeBdtProp, one substep per step) and nbody the gravity-only propagator (NbodyProp, needs g != 0) in sx_sim."""
+    if std + bdt + nbody > 1:
+        raise ValueError("std, bdt and nbody are different propagators")
     if K is None:
         K = lib().sx_kernel_constant()
     return SxParams(K=K, ng0=ng0, ngmax=ngmax, Kcour=0.2, Krho=0.06, gamma=5.0 / 3.0, muiConst=10.0, alphamin=0.05,
                     alphamax=1.0, decay_constant=0.2, Atmin=0.1, Atmax=0.2,
                     ramp=float(np.float32(1.0) / (np.float32(0.2) - np.float32(0.1))), maxDtIncrease=1.1,
                     avClean=1 if av_clean else 0, theta=theta, g=g, eps=0.005, etaAcc=0.2,
-                    propagator=1 if std else (2 if bdt else 0))
+                    propagator=1 if std else (2 if bdt else (3 if nbody else 0)))
 
 
 def make_box(lim, bnd):
@@ -790,12 +793,16 @@ class Comm:
 
 
 class Sim:
-    """device-resident VE propagator on one GPU (sx_sim_*)"""
+    """device-resident propagator on one GPU (sx_sim_*): VE by default; params.propagator (or the propagator keyword,
+    which overrides it) selects 0 = ve, 1 = std, 2 = ve-bdt, 3 = nbody (gravity only: params.g must not be 0)"""
 
-    def __init__(self, ctx, capacity, box, params=None, bucket=64):
+    def __init__(self, ctx, capacity, box, params=None, bucket=64, propagator=None):
         self.ctx = ctx
         self.L = ctx.L
         self.params = params or default_params()
+        if propagator is not None:
+            self.params = SxParams.from_buffer_copy(self.params)  # the caller's params stay as they are
+            self.params.propagator = int(propagator)
         self.box = box
         self.iteration = 0  # completed steps (the reference's "iteration" attribute)
         self.stirred = False  # set_turbulence was called: checkpoints carry the turbulence state
@@ -854,16 +861,33 @@ class Sim:
         return dict(first=out[0], last=out[1], n=out[2], haloRetries=out[3])
 
     def set_state(self, st, minDt=1e-6, minDt_m1=1e-6):
-        arrs = [np.ascontiguousarray(st[k], dtype=t) for k, t in [
+        """upload the conserved fields (sx_sim_set_state); the gravity-only propagator keeps no temp, du_m1 and alpha:
+        they may be missing from st and are ignored if given"""
+        skip = self.NBODY_ABSENT if self.params.propagator == 3 else ()
+        arrs = [None if k in skip else np.ascontiguousarray(st[k], dtype=t) for k, t in [
             ("x", np.float64), ("y", np.float64), ("z", np.float64), ("h", np.float32), ("m", np.float32),
             ("temp", np.float64), ("vx", np.float32), ("vy", np.float32), ("vz", np.float32), ("x_m1", np.float32),
             ("y_m1", np.float32), ("z_m1", np.float32), ("du_m1", np.float32), ("alpha", np.float32),
             ("id", np.uint64)]]
         self._keep = arrs
-        self.ctx.check(self.L.sx_sim_set_state(self.h, arrs[0].size, *[a.ctypes.data for a in arrs],
+        self.ctx.check(self.L.sx_sim_set_state(self.h, arrs[0].size,
+                                               *[None if a is None else a.ctypes.data for a in arrs],
                                                float(minDt), float(minDt_m1)), "set_state")
 
     CONSERVED = ["x", "y", "z", "h", "m", "temp", "vx", "vy", "vz", "x_m1", "y_m1", "z_m1", "du_m1", "alpha", "id"]
+    NBODY_ABSENT = ("temp", "du_m1", "alpha")  # conserved fields of VE that NbodyProp does not keep (nbody.hpp:74)
+
+    def conserved_fields(self):
+        """the fields a restart file of this propagator holds (Propagator::conservedFields)"""
+        if self.params.propagator == 3:
+            return [k for k in self.CONSERVED if k not in self.NBODY_ABSENT]
+        return list(self.CONSERVED)
+
+    def memory(self):
+        """bytes the sim holds (sx_sim_memory): device and pinned host memory"""
+        out = (C.c_uint64 * 2)()
+        self.ctx.check(self.L.sx_sim_memory(self.h, out), "memory")
+        return dict(device=int(out[0]), pinned=int(out[1]))
 
     def save_checkpoint(self, path, num_particles_global=None):
         """restart file of this rank: the conserved fields under the reference's field names
@@ -880,10 +904,11 @@ class Sim:
                 # the state is not restartable (drifted inactive rungs, halo lists of the hierarchy's sync)
                 raise ValueError(f"ve-bdt checkpoint inside a time-step hierarchy (substep {ts['substep']} of "
                                  f"{1 << (ts['numRungs'] - 1)}): save after the hierarchy's last substep")
-        st = self.get(self.CONSERVED + (["rung"] if bdt else []))
+        st = self.get(self.conserved_fields() + (["rung"] if bdt else []))
         # a run restarted from this file begins with a full sync + neighbor build; so does this one's next step, so
-        # the two take identical steps (skin lists, sx_sim_rebuild_lists)
-        self.rebuild_lists()
+        # the two take identical steps (skin lists, sx_sim_rebuild_lists); the gravity-only propagator syncs every step
+        if self.params.propagator != 3:
+            self.rebuild_lists()
         if num_particles_global is None:
             num_particles_global = self.size()
             comm = getattr(self, "comm", None)
@@ -923,7 +948,7 @@ class Sim:
         if str(path).endswith(".h5"):
             from . import h5part
 
-            names = self.CONSERVED + (["rung"] if self.params.propagator == 2 else [])
+            names = self.conserved_fields() + (["rung"] if self.params.propagator == 2 else [])
             with h5part.H5PartFile(path, "r") as f:
                 f.set_step(step)
                 present = set(f.attrib_names())
@@ -949,7 +974,7 @@ class Sim:
         if bad:
             raise ValueError("restart file parameters differ from this Sim's: " +
                              ", ".join(f"{k}={d[k]!r} (Sim: {mine[k]!r})" for k in bad))
-        st = {k: d[k] for k in self.CONSERVED}
+        st = {k: d[k] for k in self.conserved_fields()}
         self.set_state(st, float(d["minDt"]), float(d["minDt_m1"]))
         if self.params.propagator == 2 and "ts::numRungs" in d:
             # HydroVeBdtProp::load (ve_hydro_bdt.hpp:155-168): Timestep numRungs + dt_m1, substep 0, and the rungs
@@ -1025,10 +1050,16 @@ class Sim:
         return dict(zip(["minDt", "minDt_m1", "ttot", "minDtCourant", "minDtRho", "egrav"], list(out)))
 
     def fields(self):
+        """(SxFields, id pointer) of the locals (sx_sim_fields); a field the propagator does not keep is None"""
         f = SxFields()
         idp = C.c_void_p()
         self.L.sx_sim_fields(self.h, C.byref(f), C.byref(idp))
         return f, idp.value
+
+    def allocated_fields(self):
+        """names of the fields this propagator keeps (the non-NULL members of sx_sim_fields, and id)"""
+        f, _ = self.fields()
+        return [name for name, _ in FIELD_ORDER if getattr(f, name)] + ["id"]
 
     def get(self, names):
         f, idp = self.fields()
@@ -1036,6 +1067,8 @@ class Sim:
         out = {}
         for name in names:
             ptr = idp if name == "id" else getattr(f, name)
+            if not ptr:
+                raise KeyError(f"field {name!r} is not allocated under propagator {self.params.propagator}")
             dt = np.uint64 if name == "id" else DTYPES[name]
             out[name] = DeviceArray(self.ctx, ptr, n, dt).get()
         return out
@@ -1054,7 +1087,7 @@ class Sim:
 
     def stats(self):
         s = SxNbStats()
-        self.L.sx_sim_last_stats(self.h, C.byref(s))
+        self.ctx.check(self.L.sx_sim_last_stats(self.h, C.byref(s)), "last_stats")
         return dict(sumNeighbors=s.sumNeighbors, maxNeighbors=s.maxNeighbors, numFailed=s.numFailed,
                     sumCandidates=s.sumCandidates, sumUnion=s.sumUnion, build=s.build, maxUnion=s.maxUnion)
 

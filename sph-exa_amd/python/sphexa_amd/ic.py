@@ -107,3 +107,50 @@ def evrard(side):
     f["h"][:] = (np.cbrt(3.0 / (4.0 * math.pi) * 100 / (c0 / np.maximum(radius, 1e-12))) * 0.5).astype(np.float32)
     lo, hi = -1.25 * r, 1.25 * r
     return f, [lo, hi, lo, hi, lo, hi], [0, 0, 0], 1e-4
+
+
+def plummer(n, seed=0, a=1.0, rmax=8.0, dt0=1e-4):
+    """Plummer sphere in virial equilibrium for the gravity-only propagator (propagator 3), G = 1, total mass 1, scale
+    radius a: the sampling of Aarseth, Henon & Wielen (1974) -- radii from the inverted mass profile
+    r = a / sqrt(u^(-2/3) - 1), redrawn beyond rmax * a, isotropic speeds q * v_esc(r) with q from q^2 (1 - q^2)^(7/2)
+    by rejection -- then shifted to zero centre of mass and zero total momentum.  Equal masses 1/n, h a constant
+    softening a / n^(1/3), x_m1 = v * dt0.  No thermal field.  Open box [-1.5 rmax a, 1.5 rmax a]^3.
+    Returns (arrays, box limits, boundary, dt0)."""
+    rng = np.random.default_rng(seed)
+    r = np.empty(0)
+    while r.size < n:
+        u = rng.uniform(0.0, 1.0, 2 * n)
+        u = u[u > 0.0]
+        c = 1.0 / np.sqrt(u ** (-2.0 / 3.0) - 1.0)
+        r = np.concatenate([r, c[c <= rmax]])
+    r = r[:n]
+
+    def directions(k):
+        cz = rng.uniform(-1.0, 1.0, k)
+        ph = rng.uniform(0.0, 2.0 * math.pi, k)
+        s = np.sqrt(1.0 - cz * cz)
+        return s * np.cos(ph), s * np.sin(ph), cz
+
+    q = np.empty(0)
+    while q.size < n:
+        cand = rng.uniform(0.0, 1.0, 4 * n)
+        y = rng.uniform(0.0, 0.1, 4 * n)  # max of q^2 (1 - q^2)^3.5 is 0.0925
+        q = np.concatenate([q, cand[y < cand * cand * (1.0 - cand * cand) ** 3.5]])
+    q = q[:n]
+    speed = q * math.sqrt(2.0) * (1.0 + r * r) ** -0.25 / math.sqrt(a)
+    dx, dy, dz = directions(n)
+    ux, uy, uz = directions(n)
+    pos = [a * r * dx, a * r * dy, a * r * dz]
+    vel = [speed * ux, speed * uy, speed * uz]
+    f = {}
+    for k, p, v in zip("xyz", pos, vel):
+        f[k] = p - p.mean()  # equal masses: the centre of mass is the mean
+        v32 = (v - v.mean()).astype(np.float32)
+        v32 = (v32 - np.float32(v32.astype(np.float64).mean())).astype(np.float32)  # the float rounding's residue
+        f["v" + k] = v32
+        f[k + "_m1"] = (v32.astype(np.float64) * dt0).astype(np.float32)
+    f["m"] = np.full(n, np.float32(1.0 / n))
+    f["h"] = np.full(n, np.float32(a / np.cbrt(n)))
+    f["id"] = np.arange(n, dtype=np.uint64)
+    lim = 1.5 * rmax * a
+    return f, [-lim, lim, -lim, lim, -lim, lim], [0, 0, 0], dt0
