@@ -19,7 +19,11 @@ Fixtures
   std_kernels.npz  Sedov n=12 after 2 std steps + neighbor list and the outputs of density, EOS_HydroStd, IAD,
                    momentumEnergySTD (the reference's std *Impl loops)
 
-    python oracle/gen_golden.py [--only gravity|std]
+  boxes.npz      two small variants of the box cases of tests/box_cases.py (`mixed` at 16x8x4: a periodic, an open and
+                 a fixed axis off the origin; `gresho` at 21x21x3: 1 x 1 x 0.111 periodic): inputs, Hilbert keys and
+                 the state after 2 VE steps
+
+    python oracle/gen_golden.py [--only gravity|std|boxes]
 """
 import os
 import sys
@@ -110,6 +114,26 @@ def std_fixture(ref):
     np.savez_compressed(os.path.join(OUT, "std_kernels.npz"), **out)
 
 
+def boxes_fixture(ref):
+    """the reference's keys and two VE steps in a mixed-boundary off-origin box and a thin periodic one"""
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+    import box_cases as bc
+
+    out = {}
+    for name, dims in (("mixed", (16, 8, 4)), ("gresho", (21, 21, 3))):
+        st, box = bc.state(name, dims=dims)
+        out[f"{name}_box"] = box_arr(box)
+        out[f"{name}_keys"] = ref.sfc_keys(st, box).copy()
+        st.keys[:] = 0
+        out.update({f"{name}_in_{k}": st.arrays[k].copy() for k in po.CONSERVED})
+        for _ in range(2):
+            ref.step(st, box)
+        keep = po.CONSERVED + ["nc", "du", "ax", "ay", "az", "divv"]
+        out.update({k: v for k, v in snapshot(st, f"{name}_s2_").items()
+                    if k.endswith("scalars") or k[len(name) + 4:] in keep})
+    np.savez_compressed(os.path.join(OUT, "boxes.npz"), **out)
+
+
 def main():
     ref = po.load_ref()
     if ref is None:
@@ -120,6 +144,8 @@ def main():
         std_fixture(ref)
     if only in (None, "gravity"):
         gravity_fixture(ref)
+    if only in (None, "boxes"):
+        boxes_fixture(ref)
     if only is not None:
         return
 

@@ -79,6 +79,17 @@ def make_box(lo=-0.5, hi=0.5, periodic=True):
     return b
 
 
+def make_box6(lim, bnd):
+    """a general box: lim = (xmin, xmax, ymin, ymax, zmin, zmax), bnd per axis 0 open, 1 periodic, 2 fixed
+    (cstone::BoundaryType, box.hpp)"""
+    b = OxBox()
+    for k in range(6):
+        b.lim[k] = float(lim[k])
+    for k in range(3):
+        b.bnd[k] = int(bnd[k])
+    return b
+
+
 class HostState:
     """numpy-owned particle state with an OxState view."""
 

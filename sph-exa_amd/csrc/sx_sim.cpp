@@ -1028,7 +1028,15 @@ extern "C"
         {
             const bool allPbc = box->bnd[0] == 1 && box->bnd[1] == 1 && box->bnd[2] == 1;
             const double lx = box->lim[1] - box->lim[0], ly = box->lim[3] - box->lim[2], lz = box->lim[5] - box->lim[4];
-            if (!allPbc || lx != ly || lx != lz || p->propagator == 2) return SX_ERR_ARG;
+            if (!allPbc || lx != ly || lx != lz || p->propagator == 2)
+            {
+                sx_ctx_set_error_internal(ctx, !allPbc ? "sx_sim_create: self-gravity needs a box that is open or "
+                                                         "periodic along all three axes"
+                                               : (p->propagator == 2
+                                                      ? "sx_sim_create: ve-bdt has no periodic self-gravity"
+                                                      : "sx_sim_create: periodic self-gravity (Ewald) needs a cubic box"));
+                return SX_ERR_ARG;
+            }
         }
         auto* s   = new sx_sim;
         s->ctx    = ctx;

@@ -1,7 +1,7 @@
 """Worker for the multi-rank tests (launched by torch.distributed.run with the gloo control plane).
 
   python -m torch.distributed.run --nproc-per-node P --master-addr 127.0.0.1 --master-port X \
-      tests/dist_worker.py --out DIR [--backend host|rccl] [--side S] [--steps K] [--ic sedov|sedov_dev]
+      tests/dist_worker.py --out DIR [--backend host|rccl] [--side S] [--steps K] [--ic sedov|sedov_dev|box:<name>]
 
 Each rank owns an index slice of the IC, runs K distributed VE steps, and writes its local particles
 (id, nc, h and the compared float fields) plus scalars to DIR/rank<r>.npz.
@@ -27,7 +27,8 @@ def main():
     ap.add_argument("--side", type=int, default=16)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--ic", default="sedov",
-                    help="sedov | sedov_dev | noh | evrard (self-gravity, G = 1) | pbc_wave (periodic self-gravity, G = 1)")
+                    help="sedov | sedov_dev | noh | evrard (self-gravity, G = 1) | pbc_wave (periodic self-gravity, G = 1) | "
+                         "box:<name> (a case of tests/box_cases.py, --side unused)")
     ap.add_argument("--std", action="store_true", help="std propagator (HydroProp)")
     ap.add_argument("--no-overlap", action="store_true", help="serial halo exchanges (no interior/boundary split)")
     ap.add_argument("--av-clean", action="store_true", help="avClean momentum (dV halos)")
@@ -46,8 +47,13 @@ def main():
     ctx = sx.Context(0 if args.backend == "host" else local)
     comm = sx.Comm(args.backend)
     ic = {"evrard": po.evrard_state, "noh": po.noh_state, "pbc_wave": po.pbc_wave_state}.get(args.ic, po.sedov_state)
-    st, obox = ic(args.side)
-    if args.ic in ("evrard", "noh"):
+    if args.ic.startswith("box:"):
+        import box_cases as bc
+
+        st, obox = bc.state(args.ic[4:])
+    else:
+        st, obox = ic(args.side)
+    if args.ic in ("evrard", "noh") or args.ic.startswith("box:"):
         po.converge_h(po.load_oracle(), st, obox)  # these ICs' h would iterate (and may not converge) in the first search
     box = sx.make_box(list(obox.lim), list(obox.bnd))
     g = args.g if args.g is not None else (1.0 if args.ic in ("evrard", "pbc_wave") else 0.0)

@@ -202,8 +202,9 @@ def test_cluster_kernels_fixture(ctx, ora):
     run_cluster_kernels(ctx, st, gutil.box_to_sx(box), inputs, ref, sc, ora.params(), st.minDt, False)
 
 
-def advanced_state(ora, ic, side, steps, params):
-    st, box = (po.sedov_state if ic == "sedov" else po.noh_state)(side)
+def advanced_state(ora, ic, side, steps, params, state=None):
+    """state = (st, box): advance that state instead of the Sedov / Noh IC (the box cases of box_cases.py)"""
+    st, box = state if state is not None else (po.sedov_state if ic == "sedov" else po.noh_state)(side)
     for _ in range(steps):
         ora.step(st, box, params=params)
     gutil.sorted_state(st, box, ora)
@@ -252,7 +253,14 @@ def test_cluster_kernels_std_vs_oracle(ctx, ora, ic, side, steps):
     momentumEnergySTD as cluster kernels, each in isolation on the oracle's inputs"""
     params = ora.params(std=True)
     st, box, nbr = advanced_state(ora, ic, side, steps, params)
+    run_std_chain(ctx, ora, st, box, nbr, params)
+
+
+def run_std_chain(ctx, ora, st, box, nbr, params):
+    """the std cluster kernels on the key-sorted state st with the oracle's neighbor list nbr, see
+    test_cluster_kernels_std_vs_oracle; returns the worst error / scale per field"""
     chk = st.copy()
+    worst = {}
     sc = ora.scales_on(st.n)
     try:
         ora.density(chk, box, nbr, params=params)
@@ -279,7 +287,8 @@ def test_cluster_kernels_std_vs_oracle(ctx, ora, ic, side, steps):
     def close(k, scale):
         a, b = ds.get(k).astype(np.float64), ref[k].astype(np.float64)
         err = np.abs(a - b)
-        assert np.all(err <= RTOL * scale), (k, float(np.max(err / (scale + 1e-300))))
+        worst[k] = float(np.max(err / (scale + 1e-300)))
+        assert np.all(err <= RTOL * scale), (k, worst[k])
 
     ctx.check(L.sx_density_only(h, C.byref(g), C.byref(f), C.byref(p), C.byref(box_sx)), "density")
     close("rho", np.abs(ref["rho"]))
@@ -301,6 +310,7 @@ def test_cluster_kernels_std_vs_oracle(ctx, ora, ic, side, steps):
         close(k, sc["a"])
     assert mdt.value == pytest.approx(dt, rel=1e-5)
     ctx.free_all()
+    return worst
 
 
 def test_mark_ramp_on_cluster_lists(ctx, ora):

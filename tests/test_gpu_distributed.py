@@ -83,6 +83,35 @@ def test_distributed_steps_match_oracle(tmp_path, nproc, port, side):
             assert last > first and n > last - first
 
 
+def test_distributed_box_steps_match_oracle(tmp_path):
+    """2 ranks, 3 steps in `windshock` (0.5 x 0.125 x 0.125 periodic: the longest axis 4 times the others, which the
+    halo margin and the halo layout see in no cube), then in `mixed` (a periodic, an open and a fixed axis off the
+    origin), against the single-domain oracle from the same converged h: nc and h exact on every step, the float
+    fields within compare_state's bounds"""
+    import box_cases as bc
+    from test_gpu_parity import compare_state
+
+    ora = po.load_oracle()
+    for name, port in (("windshock", 29645), ("mixed", 29646)):
+        out = tmp_path / name
+        out.mkdir()
+        steps = 3
+        ranks = run_ranks(out, 2, 0, steps, port, ic="box:" + name)
+        st, obox = bc.state(name)
+        po.converge_h(ora, st, obox)  # as the worker: halos keep the pre-iteration h, so start from the converged one
+        ref = st.copy()
+        for s in range(steps):
+            ora.step(ref, obox)
+            got = merged(ranks, s)
+            assert got["id"].size == st.n and np.array_equal(got["id"], np.arange(st.n)), (name, s)
+            compare_state(got, ref, strict_discrete=True)
+            dts = {tuple(d[f"s{s}_scalars"]) for d in ranks}
+            assert len(dts) == 1 and list(dts)[0][0] == pytest.approx(ref.minDt, rel=1e-5), (name, s)
+            for d in ranks:
+                first, last, n, _ = d[f"s{s}_layout"]
+                assert last > first and n > last - first, (name, s)
+
+
 def test_distributed_device_ic_conserves(tmp_path):
     """slab IC generated on the device per rank, first sync redistributes by SFC; energy conserved"""
     ranks = run_ranks(tmp_path, 2, 20, 3, 29643, ic="sedov_dev")

@@ -44,6 +44,12 @@ def ctx():
 def test_skin_sets_equal_fresh_search(ctx, kind, side, steps, factor):
     """each filtered step's neighbor sets, nc and h equal a fresh search's from the same state"""
     st, obox = _ic(kind, side)
+    skin_vs_fresh(ctx, st, obox, steps, factor, (kind, side))
+
+
+def skin_vs_fresh(ctx, st, obox, steps, factor, label):
+    """the body of test_skin_sets_equal_fresh_search on any state and box; returns the skin statistics"""
+    kind = label
     box = gutil.box_to_sx(obox)
     a = sx.Sim(ctx, st.n, box)
     a.set_skin(factor, 24)
@@ -67,8 +73,9 @@ def test_skin_sets_equal_fresh_search(ctx, kind, side, steps, factor):
             bad = [k for k in na if not np.array_equal(na[k], nb[k])]
             assert not bad, (kind, s, len(bad), bad[:3])
         ks = a.skin_stats()
-        print(kind, side, factor, ks)
+        print(label, factor, ks)
         assert ks["reuse_steps"] > 0, ks
+        return ks
     finally:
         a.close()
         b.close()

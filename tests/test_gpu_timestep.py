@@ -7,12 +7,16 @@ reference's positions.hpp:54-88 formulas and ts_groups.cu:17-108):
 on spatial groups (sx_spatial_groups) and on the implicit fixed 64-groups, with rung arrays and without.
 temp is bit-exact while u stays positive; energyUpdate's u < 0 guard (cooling) evaluates u_old*exp(x) with |x| up to
 ~50 when du is random, where an ulp of the device exp vs glibc's, amplified by |x| through the drift's two updates,
-shows up: the test with such du holds temp to a relative 1e-13 instead."""
+shows up: the test with such du holds temp to a relative 1e-13 instead.
+The *_boxes tests repeat the seam, and sx_positions (the VE step's update), in boxes with a periodic, an open and a
+fixed axis of different lengths off the origin (box_cases.positions_state): wraps on the periodic axis only, the
+fixed-boundary skip of particles at rest within 2h of a fixed wall."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import box_cases as bc
 import gpu_util as gutil
 import pyoracle as po
 import sphexa_amd as sx
@@ -72,9 +76,64 @@ def groups_of(ctx, ora, st, obox, spatial):
 @pytest.mark.parametrize("spatial,use_rung,periodic,cooling", [(True, True, True, False), (False, True, False, False),
                                                                (True, False, True, False), (True, True, True, True)])
 def test_positions_drift_groupdt_bitexact(ctx, olib, spatial, use_rung, periodic, cooling):
-    ora = po.load_oracle()
     st, obox = moving_state(20, 3, periodic, cooling)
-    ttol = 1e-13 if cooling else 0.0
+    run_seam(ctx, olib, st, obox, spatial, use_rung, 1e-13 if cooling else 0.0)
+
+
+@pytest.mark.parametrize("spatial,use_rung", [(True, True), (False, False)])
+@pytest.mark.parametrize("boxname", list(bc.POSITION_BOXES))
+def test_positions_drift_groupdt_bitexact_boxes(ctx, olib, boxname, spatial, use_rung):
+    """the same seam in a box with a periodic, an open and a fixed axis of different lengths off the origin
+    (box_cases.positions_state): particles that must wrap on the periodic axis only, particles at rest within 2h of a
+    fixed wall that must stay, particles at rest elsewhere and moving ones near the wall that must move"""
+    ora = po.load_oracle()
+    st, obox, cls = bc.positions_state(boxname)
+    cls = cls[bc.sort_all(st, obox, ora)]
+    # without the drift: it sets v of every particle, and the fixed-boundary skip is for particles at rest
+    before, after = run_seam(ctx, olib, st, obox, spatial, use_rung, 0.0, drift=False)
+    bc.check_position_classes(before, after, cls, obox)
+
+
+@pytest.mark.parametrize("exact", [True, False])
+@pytest.mark.parametrize("boxname", list(bc.POSITION_BOXES))
+def test_positions_boxes_bitexact(ctx, boxname, exact):
+    """sx_positions (the VE step's position update, putInBox and the fixed-boundary skip per axis) against the
+    oracle's ox_positions in the same boxes, on a sub-range: x, x_m1, v and du_m1 bit-exact in both variants, the
+    particles outside the range untouched.  temp is bit-exact in the exact variant; the production variant contracts
+    the energy update's sum to FMAs, so there it is held to StepChecker's 1e-15 relative (a few ulp of a double)"""
+    ora = po.load_oracle()
+    ctx.set_exact(exact)
+    st, obox, cls = bc.positions_state(boxname)
+    st.minDt, st.minDt_m1 = 1.7e-4, 1.1e-4
+    ds = sx.DeviceState(ctx, gutil.host_dict(st))
+    box = gutil.box_to_sx(obox)
+    first, last = 37, st.n - 11
+    ctx.check(ctx.L.sx_positions(ctx.h, first, last, st.minDt, st.minDt_m1, C.byref(ds.fields), 5.0 / 3.0, 10.0,
+                                 C.byref(box)), "positions")
+    ref = st.copy()
+    ora.positions(ref, obox, first, last)
+    ctx.set_exact(False)
+    for k in ("x", "y", "z", "vx", "vy", "vz", "x_m1", "y_m1", "z_m1", "du_m1"):
+        assert np.array_equal(ds.get(k), ref.arrays[k]), k
+    temp = ds.get("temp")
+    print("sx_positions", boxname, "exact" if exact else "fast", "temp worst rel",
+          float(np.max(np.abs(temp - ref.temp) / ref.temp)))
+    assert np.array_equal(temp, ref.temp) if exact else np.all(np.abs(temp - ref.temp) <= 1e-15 * np.abs(ref.temp))
+    inside = np.zeros(st.n, bool)
+    inside[first:last] = True
+    assert np.array_equal(ref.x[~inside], st.x[~inside])
+    sub, rsub = po.HostState(last - first), po.HostState(last - first)
+    for k in ("x", "y", "z", "vx", "vy", "vz", "x_m1", "y_m1", "z_m1"):
+        sub.arrays[k][:] = st.arrays[k][first:last]
+        rsub.arrays[k][:] = ref.arrays[k][first:last]
+    bc.check_position_classes(sub, rsub, cls[first:last], obox)
+    ctx.free_all()
+
+
+def run_seam(ctx, olib, st, obox, spatial, use_rung, ttol, drift=True):
+    """group time-steps, rung storage, drift (unless drift is False) and the rung-aware position update on st in obox
+    against the oracle; returns the oracle's state before and after the position update"""
+    ora = po.load_oracle()
     gs, ge, bounds = groups_of(ctx, ora, st, obox, spatial)
     ng = gs.size
     rng = np.random.default_rng(4)
@@ -122,21 +181,25 @@ def test_positions_drift_groupdt_bitexact(ctx, olib, spatial, use_rung, periodic
         assert np.array_equal(rg.get(), want)
 
     # drift of every group, then the rung-aware position update
-    ctx.check(L.sx_drift_positions(h, C.byref(grp), dt, dt_back, dt_m1.ctypes.data,
-                                   drung.ptr if use_rung else None, C.byref(ds.fields), 5.0 / 3.0, constCv), "drift")
     ref = st.copy()
     s = ref.struct()
     rp = rung.ctypes.data if use_rung else None
-    olib.ox_drift_positions(C.byref(s), gs.ctypes.data, ge.ctypes.data, ng, dt, dt_back, dt_m1.ctypes.data, rp,
-                            constCv)
-    for k in ("x", "y", "z", "vx", "vy", "vz", "x_m1", "du_m1"):
-        assert np.array_equal(ds.get(k), ref.arrays[k]), ("drift", k)
-    assert np.allclose(ds.get("temp"), ref.temp, rtol=ttol, atol=0), "drift temp"
+    if drift:
+        ctx.check(L.sx_drift_positions(h, C.byref(grp), dt, dt_back, dt_m1.ctypes.data,
+                                       drung.ptr if use_rung else None, C.byref(ds.fields), 5.0 / 3.0, constCv),
+                  "drift")
+        olib.ox_drift_positions(C.byref(s), gs.ctypes.data, ge.ctypes.data, ng, dt, dt_back, dt_m1.ctypes.data, rp,
+                                constCv)
+        for k in ("x", "y", "z", "vx", "vy", "vz", "x_m1", "du_m1"):
+            assert np.array_equal(ds.get(k), ref.arrays[k]), ("drift", k)
+        assert np.allclose(ds.get("temp"), ref.temp, rtol=ttol, atol=0), "drift temp"
     ctx.check(L.sx_positions_rungs(h, C.byref(grp), dt, dt_m1.ctypes.data, drung.ptr if use_rung else None,
                                    C.byref(ds.fields), 5.0 / 3.0, constCv, C.byref(box)), "positions")
+    drifted = ref.copy()
     olib.ox_positions_rungs(C.byref(s), gs.ctypes.data, ge.ctypes.data, ng, dt, dt_m1.ctypes.data, rp, constCv,
                             C.byref(obox))
     for k in ("x", "y", "z", "vx", "vy", "vz", "x_m1", "y_m1", "z_m1", "du_m1"):
         assert np.array_equal(ds.get(k), ref.arrays[k]), ("positions", k)
     assert np.allclose(ds.get("temp"), ref.temp, rtol=ttol, atol=0), "positions temp"
     ctx.free_all()
+    return drifted, ref

@@ -84,6 +84,28 @@ def test_tree_and_neighbors_bitwise(ora):
     assert np.array_equal(st.h, d["h_iter"])
 
 
+@pytest.mark.parametrize("name", ["mixed", "gresho"])
+def test_boxes_bitwise(ora, name):
+    """boxes.npz: the reference's keys and two VE steps in a mixed-boundary off-origin box (16x8x4) and a thin
+    periodic one (21x21x3); re-pins the oracle's per-axis box arithmetic where oracle/_ref does not exist"""
+    d = gu.load("boxes.npz")
+    box = gu.box_from(d[f"{name}_box"])
+    n = d[f"{name}_in_x"].size
+    st = po.HostState(n)
+    for k in po.CONSERVED:
+        st.arrays[k][:] = d[f"{name}_in_{k}"]
+    sc = d[f"{name}_s2_scalars"]
+    st.minDt = st.minDt_m1 = 1e-5
+    assert np.array_equal(ora.sfc_keys(st, box), d[f"{name}_keys"])
+    for _ in range(2):
+        ora.step(st, box)
+    stored = [k[len(name) + 4:] for k in d if k.startswith(f"{name}_s2_") and not k.endswith("scalars")]
+    assert len(stored) >= len(po.CONSERVED) + 6
+    for k in stored:
+        assert np.array_equal(st.arrays[k], d[f"{name}_s2_{k}"]), (name, k)
+    assert (st.minDt, st.minDt_m1, st.ttot) == (sc[0], sc[1], sc[2])
+
+
 def test_oracle_rejects_out_of_range_neighbor_indices():
     """a neighbor list exported from the path under test is input to the checker: an index beyond the state fails as
     an assertion (sph_oracle.c lists_ok), it does not crash the process"""
