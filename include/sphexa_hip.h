@@ -198,7 +198,7 @@ int         sx_create(sx_ctx** ctx, int device);
 void        sx_destroy(sx_ctx* ctx);
 int         sx_set_stream(sx_ctx* ctx, void* hipStream); /* NULL = the context's own stream */
 void*       sx_get_stream(sx_ctx* ctx);
-const char* sx_last_error(sx_ctx* ctx);
+const char* sx_last_error(sx_ctx* ctx); /* ctx NULL: the calling thread's last refused host-only call (sx_map_check) */
 /*! 1: bit-reproducible arithmetic (no FMA contraction; matches the CPU reference bit-for-bit given the same neighbor
  *  order); 0 (default): FMA-contracted kernels. */
 int    sx_set_exact(sx_ctx* ctx, int exact);
@@ -407,6 +407,62 @@ int sx_grav_wave_htt(const double q[6], double theta, double phi, double out[2])
  *    SX_OBS_GRAV_WAVES   h+, hx at (gravWaveTheta, gravWavePhi)   (gravitational_waves.hpp:86) */
 int sx_obs_finalize(int kind, const sx_obs_settings* settings, const double* globalSums, uint64_t numParticlesGlobal,
                     double* out);
+
+/* ---- maps: column density and slices of the particles as images (sph-exa_amd/csrc/sx_map.hpp) -----------------
+ * The device-side counterpart of the reference's in-situ "Density" scene (viz::execute, main/src/insitu_viz.h:35;
+ * ascent_adaptor.h:41-48, 109-132, which renders host copies through Ascent): the state reduced to an image without
+ * leaving the device.  For an image plane with normal `axis` the in-plane axes (u, v) are its cyclic successors: (y, z),
+ * (z, x), (x, y).  With W(q) = sinc(pi q / 2)^6, Y(q) = 2 int_0^sqrt(4 - q^2) W(sqrt(q^2 + s^2)) ds and the pixel
+ * centre P:
+ *   SX_MAP_COLUMN  sum0(P) = sum_j m_j K Y(b_j / he_j) / he_j^2, b_j the in-plane distance, he_j = max(h_j, half the
+ *                  larger pixel size) so that no particle falls between the pixel centres: the column density.  depth > 0
+ *                  keeps the particles whose normal coordinate lies within depth / 2 of center's.
+ *   SX_MAP_SLICE   sum0(P) = sum_j m_j K W(r_j / h_j) / h_j^3, r_j the distance to P on the plane through center: the
+ *                  SPH mass density there (h is not clamped).
+ *   sum1(P) = sum_j w_j a_j over the same weights w_j: sum1 / sum0 is the mass-weighted mean of the column a.
+ * Distances are minimum-image on periodic axes, plain on open and fixed ones; the window may straddle a periodic edge.
+ * Neither map reads rho or a volume element, so the VE, std and gravity-only layouts are served alike (the last with h
+ * as the softening length).  Accumulation is in float in ascending particle index per pixel, stored as double: the
+ * image does not depend on the run, the device's scheduling or the pair cap. */
+#define SX_MAP_COLUMN 0
+#define SX_MAP_SLICE 1
+typedef struct sx_map
+{
+    int32_t  kind, axis; /* axis = normal: 0 x, 1 y, 2 z */
+    double   center[3];  /* window centre; its normal component is the slice plane / slab centre */
+    double   width[2];   /* extent along u, v */
+    double   depth;      /* column: slab thickness, 0 = unbounded; slice: ignored */
+    uint32_t npix[2];    /* pixels along u, v; image is npix[1] rows of npix[0], u fastest */
+} sx_map;
+/*! host only, needs no GPU: SX_OK, or SX_ERR_ARG with the reason in sx_last_error(NULL) (per thread).  Refused, each
+ *  with its own message: a NULL argument, an unknown kind, an unknown axis, npix of 0 or above 4096, a width that is
+ *  not positive, a width above the box length on a periodic axis, a negative depth. */
+int sx_map_check(const sx_map* map, const sx_box* box);
+/*! host evaluation of the register-resident Y(t), t = q^2, of the column maps (mapKernelY, sx_kernel_poly.hpp), for
+ *  checking it against a quadrature; like sx_kernel_poly */
+int sx_map_kernel(const float* t, size_t n, float* y);
+/*! records the render kernel stages through LDS at a time (tests place a tile's list length around its multiples) */
+uint32_t sx_map_chunk_records(void);
+/*! pairs (tile, particle) produced and sorted at a time: a render works through the image in bands of whole rows of
+ *  16 x 16-pixel tiles whose pairs stay within this cap; 0 = the default (2^27: 24 B per pair with the sort's storage, 3.2 GB at most).  The
+ *  image is bit-identical for every cap.  A render in which one tile row alone exceeds the cap (or 2^31 - 1 pairs)
+ *  returns SX_ERR_ARG. */
+int sx_set_map_pair_cap(sx_ctx* ctx, uint64_t pairs);
+/*! renders map over the particles [first, last) of f into sum0 (and sum1), device arrays of npix[0] * npix[1] doubles.
+ *  Reads x y z h m of f and K (sx_params.K); a: any device column of length f->n, float or double (aIsDouble), or NULL:
+ *  then sum1 is not touched.  sum0 and sum1 are overwritten, not added to.  Runs on the context stream and synchronises
+ *  it once, after counting the pairs (the bands are planned on the host); the images are complete when the stream is.
+ *  The scratch (pairs, sort buffers) lives in the context.  SX_ERR_ARG: whatever sx_map_check refuses, missing fields,
+ *  first > last or last > f->n, a tile row beyond the pair cap. */
+int sx_map_render(sx_ctx* ctx, const sx_fields* f, const sx_box* box, uint32_t first, uint32_t last, double K,
+                  const sx_map* map, const void* a, int aIsDouble, double* sum0, double* sum1);
+/*! the context's last render: {pairs, bands, longest tile list, particles with a footprint in the window};
+ *  synchronises.  SX_ERR_ARG before the first render. */
+int sx_map_stats(sx_ctx* ctx, uint64_t out[4]);
+/*! measurement: with on != 0 the following renders time their stages with HIP events (and synchronise after every
+ *  band); sx_map_times: {binning, sort, render} in ms and out[3] = the scratch bytes of the last render */
+int sx_set_map_timing(sx_ctx* ctx, int on);
+int sx_map_times(sx_ctx* ctx, double out[4]);
 
 /* ---- self-gravity: ryoanji MultipoleHolder seam (multipole_holder.cuh:40-66, gravity_wrapper.hpp:104-174) ----- */
 /*! expansion centers (mass centers, {x,y,z,mac^2}, numNodes x 4 doubles; mac = 2 max(node size)/theta + |com-geo|,
@@ -635,6 +691,33 @@ int    sx_sim_set_observable(sx_sim* sim, int kind, const sx_obs_settings* setti
 int    sx_sim_observe(sx_sim* sim, double* row, int cap, int* ncols);
 /*! the iteration a restarted run continues from (the restart file's "iteration" attribute) */
 int    sx_sim_set_iteration(sx_sim* sim, uint64_t iteration);
+/*! the column a of sx_sim_render */
+#define SX_MAP_FIELD_NONE 0
+#define SX_MAP_FIELD_TEMP 1
+#define SX_MAP_FIELD_P 2
+#define SX_MAP_FIELD_C 3
+#define SX_MAP_FIELD_VX 4
+#define SX_MAP_FIELD_VY 5
+#define SX_MAP_FIELD_VZ 6
+#define SX_MAP_FIELD_DIVV 7
+#define SX_MAP_FIELD_CURLV 8
+#define SX_MAP_FIELD_ALPHA 9
+#define SX_MAP_FIELD_H 10
+/*! sx_map_render of this rank's local particles in their current positions, one f64-sum reduction per image over the
+ *  communicator when one is set, and the images copied to the host arrays hostSum0, hostSum1 (npix[0] * npix[1] doubles
+ *  each; hostSum1 is not touched for SX_MAP_FIELD_NONE and may be NULL); synchronises.  Every propagator, any number
+ *  of ranks (every rank calls it and receives the whole image); under ve-bdt between any two substeps.  Nothing in
+ *  sx_sim_step calls it and it changes no state.  The dependent fields (p, c, divv, curlv) are those of the last force
+ *  stage: stale by the one position update that followed it.  A field the layout does not keep is refused with
+ *  SX_ERR_ARG and a reason: under the gravity-only propagator everything except NONE, VX, VY, VZ, H; p under VE, which
+ *  keeps p / rho only.  A refusal that only one rank meets (a tile row of its particles above the pair cap, no memory for
+ *  its pairs) travels with the images through the reduction: that rank returns its code, every other rank SX_ERR_ARG,
+ *  none waits for ever; a rank that cannot allocate the image buffers themselves does not take part, which is fatal for
+ *  the communicator.  The image buffers and the pair scratch are allocated by the first render and counted by
+ *  sx_sim_memory from then on.  sx_sim_map_stats: sx_map_stats of the sim's last render (this rank's figures). */
+int    sx_sim_render(sx_sim* sim, const sx_map* map, int field, double* hostSum0, double* hostSum1);
+int    sx_sim_map_stats(sx_sim* sim, uint64_t out[4]);
+int    sx_sim_set_map_pair_cap(sx_sim* sim, uint64_t pairs);
 /*! device time (ms) of each hot kernel alone in the last step (HIP events on the launch stream, bracketing just the
  *  launch): findNeighbors, xmass, veDefGradh, iadDivvCurlv, avSwitches, momentumEnergy */
 int    sx_sim_kernel_times(sx_sim* sim, float* ms, int cap, const char** names);

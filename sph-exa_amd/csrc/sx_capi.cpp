@@ -17,6 +17,7 @@
 #include "sx_gravity.hpp"
 #include "sx_hydro.hpp"
 #include "sx_kernel_poly.hpp"
+#include "sx_map.hpp"
 #include "sx_nbody.hpp"
 #include "sx_observables.hpp"
 #include "sx_tree.hpp"
@@ -122,6 +123,7 @@ struct sx_ctx
     uint32_t    directSplits{0};         // sx_set_direct_splits: source splits of sx_gravity_direct, 0 = automatic
     uint32_t    directTargetsPerLane{sx::direct::kDefaultTargetsPerLane}; // fast direct sum (A/B: DESIGN.md 7f)
     Arena       arena;
+    sx::map::MapBuffers mapBuf;          // pair scratch and figures of sx_map_render
     float2*     wh{nullptr};
     float2*     whd{nullptr};
     double      K{0};
@@ -168,9 +170,13 @@ static const float* ensurePowTab(sx_ctx* c, uint32_t ng0)
     return c->powTab;
 }
 
+//! the reason of the calling thread's last refused host-only call (sx_map_check), read through sx_last_error(NULL)
+static thread_local std::string hostErr;
+
 static int fail(sx_ctx* c, int code, const std::string& msg)
 {
     if (c) c->err = msg;
+    else hostErr = msg;
     return code;
 }
 
@@ -259,6 +265,7 @@ extern "C"
     {
         if (!c) return;
         (void)hipDeviceSynchronize();
+        sx::map::release(c->mapBuf);
         c->arena.release();
         if (c->own) (void)hipStreamDestroy(c->own);
         delete c;
@@ -270,7 +277,7 @@ extern "C"
         return SX_OK;
     }
     void*       sx_get_stream(sx_ctx* c) { return c->stream; }
-    const char* sx_last_error(sx_ctx* c) { return c ? c->err.c_str() : "no context"; }
+    const char* sx_last_error(sx_ctx* c) { return c ? c->err.c_str() : hostErr.empty() ? "no context" : hostErr.c_str(); }
     int         sx_set_exact(sx_ctx* c, int e)
     {
         c->exact = e != 0;
@@ -1448,6 +1455,68 @@ extern "C"
             numShells > 4)
             return fail(c, SX_ERR_ARG, "sx_gravity_traverse_pbc: bad arguments");
         return gravityTraverseShells(c, g, f, tree, box, centers, multipoles, G, numShells, egrav);
+    }
+
+    // ---- maps ---------------------------------------------------------------------------------------------------
+
+    int sx_map_check(const sx_map* m, const sx_box* box)
+    {
+        if (const char* why = sx::map::checkSpec(m, box)) return fail(nullptr, SX_ERR_ARG, why);
+        return SX_OK;
+    }
+
+    int sx_map_kernel(const float* t, size_t n, float* y)
+    {
+        for (size_t k = 0; k < n; ++k)
+            y[k] = mapKernelY(t[k]);
+        return SX_OK;
+    }
+
+    uint32_t sx_map_chunk_records(void) { return sx::map::kChunk; }
+
+    int sx_set_map_pair_cap(sx_ctx* c, uint64_t pairs)
+    {
+        if (!c) return SX_ERR_ARG;
+        c->mapBuf.pairCap = pairs;
+        return SX_OK;
+    }
+
+    int sx_set_map_timing(sx_ctx* c, int on)
+    {
+        if (!c) return SX_ERR_ARG;
+        c->mapBuf.timing = on != 0;
+        return SX_OK;
+    }
+
+    int sx_map_times(sx_ctx* c, double out[4])
+    {
+        if (!c || !out) return SX_ERR_ARG;
+        for (int k = 0; k < 3; ++k)
+            out[k] = c->mapBuf.ms[k];
+        out[3] = (double)c->mapBuf.scratchBytes;
+        return SX_OK;
+    }
+
+    int sx_map_render(sx_ctx* c, const sx_fields* f, const sx_box* box, uint32_t first, uint32_t last, double K,
+                      const sx_map* m, const void* a, int aIsDouble, double* sum0, double* sum1)
+    {
+        if (!c) return SX_ERR_ARG;
+        if (!f || !box || !m || !sum0) return fail(c, SX_ERR_ARG, "sx_map_render: null fields, box, map or sum0");
+        if (!f->x || !f->y || !f->z || !f->h || !f->m) return fail(c, SX_ERR_ARG, "sx_map_render: x, y, z, h and m are required");
+        if (first > last || last > f->n) return fail(c, SX_ERR_ARG, "sx_map_render: [first, last) is not a range of f");
+        if (a && !sum1) return fail(c, SX_ERR_ARG, "sx_map_render: a column needs sum1");
+        sx::map::Args args{*m, *box, f->x, f->y, f->z, f->h, f->m, a, aIsDouble, first, last, K, sum0, sum1};
+        std::string   err;
+        const int     rc = sx::map::render(c->arena, c->mapBuf, args, c->stream, err);
+        return rc == SX_OK ? SX_OK : fail(c, rc, err);
+    }
+
+    int sx_map_stats(sx_ctx* c, uint64_t out[4])
+    {
+        if (!c || !out) return SX_ERR_ARG;
+        const int rc = sx::map::stats(c->mapBuf, c->stream, out);
+        if (rc == sx::map::kStatsMismatch) return fail(c, SX_ERR_HIP, std::string("sx_map_stats: ") + sx::map::kStatsMismatchText);
+        return rc == SX_OK ? SX_OK : fail(c, rc, rc == SX_ERR_ARG ? "sx_map_stats: nothing has been rendered" : "sx_map_stats: copy failed");
     }
 
     int sx_set_direct_splits(sx_ctx* c, uint32_t splits)

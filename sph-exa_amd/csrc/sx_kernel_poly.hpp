@@ -8,6 +8,20 @@
  * |dW - sinc6d| < 8e-7 over [0, 2) (the float-interpolated tables: 1.1e-7 and 2.2e-7) -- a few float ulps of W(0) = 1
  * (tests/test_capi_cpu.py::test_kernel_poly_matches_sinc6_and_tables checks this against the exact function and the tables, through
  * sx_kernel_poly()).  Both are 0 for v >= 2, like lt::lookup's last interval.
+ *
+ * mapKernelY(t) is W integrated along a line of sight at impact parameter q, t = q^2 (the column maps of sx_map.hip):
+ * Y(q) = 2 int_0^sqrt(4 - q^2) W(sqrt(q^2 + s^2)) ds, Y(0) = 1.09986220787, K int Y 2 pi q dq = 1.  Towards the edge
+ * of the support W ~ ((2 - r) / 2)^6, so Y ~ u^6.5 with u = 1 - t / 4: a polynomial in t alone keeps an absolute error
+ * floor there (degree 12 in t: 3.3e-7 Y(0) everywhere, a relative error without bound over the outer third of the disc),
+ * and the maps' per-pixel relative check needs the relative error.  So Y = u^6 sqrt(u) R(u) with R = Y / u^6.5, a smooth
+ * function between 0.0213 and Y(0): a least-squares polynomial of degree 10 in u on [0, 1], fitted to relative error in
+ * double on 6000 Chebyshev nodes against a 200-node Gauss-Legendre quadrature, stored as float, Horner in u (which is
+ * exact at the edge).  Fit error in double 1.8e-8 relative; evaluated in float with FMA on 400001 points of [0, 4]
+ * (through sx_map_kernel): max |Y_poly - Y| = 5.5e-7 Y(0) -- of the order of kernelW's -- and max |Y_poly / Y - 1| =
+ * 8.8e-7 for u > 1e-3; most of both is the rounding of u and of the five products behind u^6.5, not the fit (degree 9
+ * fits to 1.2e-7).  Nearer the edge Y < 1e-19 Y(0) and u^6 runs into the float denormals.  u is clamped at 0: t >= 4
+ * gives exactly 0 and no value is negative (tests/test_map_capi_cpu.py checks all of this through
+ * sx_map_kernel()).
  */
 #pragma once
 
@@ -72,6 +86,25 @@ __host__ __device__ __forceinline__ void kernelWdW(float v, float& w, float& dw)
     float s4 = s2 * s2;
     w        = s4 * s2;
     dw       = 6.0f * s4 * s * v * dsincPolyOverV(t);
+}
+
+//! Y(t), t = q^2: the kernel integrated along the line of sight (see the file header); exactly 0 for t >= 4
+__host__ __device__ __forceinline__ float mapKernelY(float t)
+{
+    const float u = fmaxf(fmaf(t, -0.25f, 1.0f), 0.0f);
+    float       s = 0.0087612435387116779f;
+    s             = fmaf(s, u, -0.010187234241781817f);
+    s             = fmaf(s, u, 0.042689993427930437f);
+    s             = fmaf(s, u, 0.030267166061782289f);
+    s             = fmaf(s, u, 0.10669873237637979f);
+    s             = fmaf(s, u, 0.16356153873887344f);
+    s             = fmaf(s, u, 0.22687781410082566f);
+    s             = fmaf(s, u, 0.23839661608874291f);
+    s             = fmaf(s, u, 0.18197386561421483f);
+    s             = fmaf(s, u, 0.089510442574192911f);
+    s             = fmaf(s, u, 0.021312021455030951f);
+    const float u2 = u * u, u4 = u2 * u2;
+    return u4 * u2 * sqrtf(u) * s;
 }
 
 } // namespace sx

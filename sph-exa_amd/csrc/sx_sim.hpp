@@ -15,6 +15,7 @@
 #include "../../include/sphexa_hip.h"
 #include "sx_comm.hpp"
 #include "sx_hydro.hpp"
+#include "sx_map.hpp"
 #include "sx_tree.hpp"
 
 namespace sx::turb
@@ -261,6 +262,7 @@ struct sx_sim
     sx::sim::SkinBuffers skinBuf;
     sx::sim::DomBuffers  dom;
     sx::sim::GravBuffers grav;
+    sx::map::MapBuffers  mapBuf; // sx_sim_render: the device images and the pair scratch (in `work`, from the first render on)
     sx::turb::SimTurb* turb{nullptr}; // turbulence stirring (sx_sim_set_turbulence), VE propagator on one rank
 
     // the observable of sx_sim_observe (observablesFactory, main/src/observables/factory.hpp:46-69)

@@ -171,6 +171,51 @@ def format_constants_row(row, kind):
     return "".join([" %d" % int(vals[0])] + [" %g" % float(v) for v in vals[1:]]) + "\n"
 
 
+class SxMap(C.Structure):
+    """sx_map: an image plane with normal `axis` (0 x, 1 y, 2 z; in-plane axes u, v = its cyclic successors), the window
+    centre (its normal component: the slice plane / slab centre), the extent along u and v, the slab thickness of a
+    column map (0: unbounded) and the pixels along u and v"""
+    _fields_ = [("kind", C.c_int32), ("axis", C.c_int32), ("center", C.c_double * 3), ("width", C.c_double * 2),
+                ("depth", C.c_double), ("npix", C.c_uint32 * 2)]
+
+    def __init__(self, kind="column", axis=2, center=(0.0, 0.0, 0.0), width=(1.0, 1.0), depth=0.0, npix=(512, 512)):
+        npix = (npix, npix) if np.isscalar(npix) else npix
+        width = (width, width) if np.isscalar(width) else width
+        super().__init__(MAP_KINDS.get(kind, kind), int(axis), (C.c_double * 3)(*[float(v) for v in center]),
+                         (C.c_double * 2)(*[float(v) for v in width]), float(depth),
+                         (C.c_uint32 * 2)(*[int(v) for v in npix]))
+
+    @property
+    def shape(self):
+        """the image as a numpy shape: npix[1] rows of npix[0]"""
+        return int(self.npix[1]), int(self.npix[0])
+
+
+MAP_KINDS = {"column": 0, "slice": 1}
+# the column a of Sim.render (SX_MAP_FIELD_*)
+MAP_FIELDS = {None: 0, "none": 0, "temp": 1, "p": 2, "c": 3, "vx": 4, "vy": 5, "vz": 6, "divv": 7, "curlv": 8,
+              "alpha": 9, "h": 10}
+
+
+def map_check(spec, box):
+    """sx_map_check: raises SxError with the reason for a specification a render would refuse.  Needs no GPU."""
+    if lib().sx_map_check(C.byref(spec), C.byref(box)) != SX_OK:
+        raise SxError(lib().sx_last_error(None).decode())
+
+
+def map_kernel(t):
+    """the column maps' line-of-sight kernel Y(t), t = q^2, as the device evaluates it (sx_map_kernel).  Needs no GPU."""
+    t = np.ascontiguousarray(t, dtype=np.float32)
+    y = np.empty_like(t)
+    lib().sx_map_kernel(t.ctypes.data, t.size, y.ctypes.data)
+    return y
+
+
+def map_chunk_records():
+    """records per LDS chunk of the render kernel (sx_map_chunk_records)"""
+    return int(lib().sx_map_chunk_records())
+
+
 class SxOctree(C.Structure):
     _fields_ = [("prefixes", _P), ("childOffsets", _P), ("parents", _P), ("levelRange", _P),
                 ("internalToLeaf", _P), ("leafToInternal", _P)]
@@ -366,6 +411,18 @@ def lib():
         "sx_sim_set_observable": (C.c_int, [vp, C.c_int, C.POINTER(SxObsSettings)]),
         "sx_sim_observe": (C.c_int, [vp, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int)]),
         "sx_sim_set_iteration": (C.c_int, [vp, C.c_uint64]),
+        "sx_map_check": (C.c_int, [C.POINTER(SxMap), C.POINTER(SxBox)]),
+        "sx_map_kernel": (C.c_int, [vp, sz, vp]),
+        "sx_map_chunk_records": (u32, []),
+        "sx_set_map_pair_cap": (C.c_int, [vp, C.c_uint64]),
+        "sx_map_render": (C.c_int, [vp, C.POINTER(SxFields), C.POINTER(SxBox), u32, u32, C.c_double, C.POINTER(SxMap),
+                                    vp, C.c_int, vp, vp]),
+        "sx_map_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        "sx_set_map_timing": (C.c_int, [vp, C.c_int]),
+        "sx_map_times": (C.c_int, [vp, C.POINTER(C.c_double)]),
+        "sx_sim_render": (C.c_int, [vp, C.POINTER(SxMap), C.c_int, vp, vp]),
+        "sx_sim_map_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        "sx_sim_set_map_pair_cap": (C.c_int, [vp, C.c_uint64]),
     }
     for name, (res, args) in sig.items():
         # a measurement build named by SPHEXA_AMD_LIB (an A/B against an older library) may predate an entry
@@ -644,6 +701,53 @@ class Context:
     def sync(self):
         self.check(self.L.sx_synchronize(self.h), "sync")
 
+    def set_map_pair_cap(self, pairs=0):
+        """(tile, particle) pairs render_map produces and sorts at a time (sx_set_map_pair_cap); 0: the default"""
+        self.check(self.L.sx_set_map_pair_cap(self.h, int(pairs)), "sx_set_map_pair_cap")
+
+    def render_map(self, fields, box, spec, a=None, first=0, last=None, K=None, sum0=None, sum1=None):
+        """the map `spec` (an SxMap) of the particles [first, last) of an SxFields (sx_map_render): (sum0, sum1) as
+        arrays of shape spec.shape, sum1 None without a.  a: a DeviceArray of float32 or float64, one value per particle
+        of fields.  sum0, sum1: DeviceArrays to render into (the caller reads them); by default temporaries."""
+        ny, nx = spec.shape
+        last = fields.n if last is None else last
+        if sum0 is not None and a is not None and sum1 is None:
+            raise ValueError("render_map: a column rendered into the caller's sum0 needs the caller's sum1 too")
+        d0 = sum0 if sum0 is not None else self.alloc(nx * ny, np.float64)
+        d1 = sum1 if (sum1 is not None or a is None) else self.alloc(nx * ny, np.float64)  # None: no a, sum1 untouched
+        try:
+            if a is not None and a.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+                raise TypeError("render_map: a must be float32 or float64")
+            self.check(self.L.sx_map_render(self.h, C.byref(fields), C.byref(box), int(first), int(last),
+                                            float(self.L.sx_kernel_constant() if K is None else K), C.byref(spec),
+                                            a.ptr if a is not None else None,
+                                            int(a is not None and a.dtype == np.dtype(np.float64)), d0.ptr,
+                                            d1.ptr if d1 is not None else None),
+                       "sx_map_render")
+            if sum0 is not None:
+                return None, None
+            return d0.get().reshape(ny, nx), (d1.get().reshape(ny, nx) if a is not None else None)
+        finally:
+            if sum0 is None:
+                self.free(d0)
+            if sum1 is None and d1 is not None:
+                self.free(d1)
+
+    def map_stats(self):
+        """the last render_map: {pairs, bands, longest (tile list), footprints (particles with one in the window)}"""
+        out = (C.c_uint64 * 4)()
+        self.check(self.L.sx_map_stats(self.h, out), "sx_map_stats")
+        return dict(zip(["pairs", "bands", "longest", "footprints"], [int(v) for v in out]))
+
+    def set_map_timing(self, on=True):
+        self.check(self.L.sx_set_map_timing(self.h, 1 if on else 0), "sx_set_map_timing")
+
+    def map_times(self):
+        """{binning, sort, render} in ms and the scratch bytes of the last render_map (after set_map_timing)"""
+        out = (C.c_double * 4)()
+        self.check(self.L.sx_map_times(self.h, out), "sx_map_times")
+        return {"binning_ms": out[0], "sort_ms": out[1], "render_ms": out[2], "scratch_bytes": int(out[3])}
+
     def observables(self, fields, kind, first=0, last=None, box=None, settings=None, mui=10.0, gamma=5.0 / 3.0,
                     cap=None):
         """this rank's sums of one fused pass over [first, last) of an SxFields (sx_observables): a dict with the
@@ -806,6 +910,7 @@ class Sim:
         self.box = box
         self.iteration = 0  # completed steps (the reference's "iteration" attribute)
         self.stirred = False  # set_turbulence was called: checkpoints carry the turbulence state
+        self.last_sum1 = None  # sum1 of the last render() with a field (the numerator of its mean); None without one
         self.h = C.c_void_p()
         ctx.check(self.L.sx_sim_create(C.byref(self.h), ctx.h, int(capacity), C.byref(self.params), C.byref(box),
                                        bucket), "sx_sim_create")
@@ -1131,6 +1236,44 @@ class Sim:
         d = dict(zip(cols, list(row)))
         d["iteration"] = int(d["iteration"])
         return d
+
+    def map_spec(self, kind="column", axis=2, center=None, width=None, npix=512, depth=0.0):
+        """the SxMap of render(): center and width default to the whole box"""
+        lim = list(self.box.lim)
+        u, v = (axis + 1) % 3, (axis + 2) % 3
+        if center is None:
+            center = [0.5 * (lim[2 * k] + lim[2 * k + 1]) for k in range(3)]
+        if width is None:
+            width = (lim[2 * u + 1] - lim[2 * u], lim[2 * v + 1] - lim[2 * v])
+        return SxMap(kind, axis, center, width, depth, npix)
+
+    def render(self, kind="column", axis=2, center=None, width=None, npix=512, depth=0.0, field=None, spec=None):
+        """a column-density ("column") or slice map of the current state over all ranks (sx_sim_render): (sum0, mean),
+        arrays of npix[1] rows of npix[0].  sum0 is the column density or the density on the plane; mean = sum1 / sum0 is
+        the mass-weighted mean of `field` (one of MAP_FIELDS) where sum0 > 0 and NaN elsewhere, None without a field.
+        center and width default to the whole box; spec: a ready SxMap instead of the keywords."""
+        spec = spec if spec is not None else self.map_spec(kind, axis, center, width, npix, depth)
+        if field not in MAP_FIELDS:
+            raise ValueError(f"unknown map field {field!r}: one of {sorted(k for k in MAP_FIELDS if k)}")
+        s0 = np.empty(spec.shape, np.float64)
+        s1 = np.empty(spec.shape, np.float64) if MAP_FIELDS[field] else None
+        self.ctx.check(self.L.sx_sim_render(self.h, C.byref(spec), MAP_FIELDS[field], s0.ctypes.data,
+                                            s1.ctypes.data if s1 is not None else None), "sx_sim_render")
+        self.last_sum1 = s1  # the numerator of the mean, None after a render without a field
+        if s1 is None:
+            return s0, None
+        mean = np.full(spec.shape, np.nan)
+        np.divide(s1, s0, out=mean, where=s0 > 0)
+        return s0, mean
+
+    def map_stats(self):
+        """this rank's figures of the last render(): {pairs, bands, longest, footprints}"""
+        out = (C.c_uint64 * 4)()
+        self.ctx.check(self.L.sx_sim_map_stats(self.h, out), "sx_sim_map_stats")
+        return dict(zip(["pairs", "bands", "longest", "footprints"], [int(v) for v in out]))
+
+    def set_map_pair_cap(self, pairs=0):
+        self.ctx.check(self.L.sx_sim_set_map_pair_cap(self.h, int(pairs)), "sx_sim_set_map_pair_cap")
 
     def write_constants(self, fileobj):
         """append the row of observe() to a constants.txt (format_constants_row); returns the row"""
