@@ -25,17 +25,8 @@
  * inside a hierarchy the reference keeps its halos whatever happens (the halo factor is its only margin) and so does
  * this, with a warning and a count (sx_sim_layout out[3] counts both).
  */
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-
-#include "sx_sim.hpp"
+#include "sx_sim_internal.hpp"
 #include "sx_timestep.hpp"
-
-extern "C" void* sx_ctx_stream_internal(sx_ctx* c);
-extern "C" void  sx_ctx_set_error_internal(sx_ctx* c, const char* msg);
 
 namespace sx::sim
 {
@@ -71,54 +62,6 @@ sx_groups sliced(const sx_groups& v, uint32_t first, uint32_t last)
     g.groupStart = v.groupStart + first;
     g.groupEnd   = v.groupEnd + first;
     return g;
-}
-
-//! sphexa::ParticlesData fields of the simulation, halos included (length n)
-sx_fields allFields(const sx_sim* s)
-{
-    sx_fields f{};
-    f.n     = s->n;
-    f.x     = s->x;
-    f.y     = s->y;
-    f.z     = s->z;
-    f.x_m1  = s->xm1;
-    f.y_m1  = s->ym1;
-    f.z_m1  = s->zm1;
-    f.vx    = s->vx;
-    f.vy    = s->vy;
-    f.vz    = s->vz;
-    f.prho  = s->prho;
-    f.h     = s->h;
-    f.m     = s->m;
-    f.c     = s->c;
-    f.ax    = s->ax;
-    f.ay    = s->ay;
-    f.az    = s->az;
-    f.du    = s->du;
-    f.du_m1 = s->dum1;
-    f.c11   = s->c11;
-    f.c12   = s->c12;
-    f.c13   = s->c13;
-    f.c22   = s->c22;
-    f.c23   = s->c23;
-    f.c33   = s->c33;
-    f.temp  = s->temp;
-    f.xm    = s->xm;
-    f.kx    = s->kx;
-    f.divv  = s->divv;
-    f.curlv = s->curlv;
-    f.alpha = s->alpha;
-    f.gradh = s->gradh;
-    f.keys  = s->keys;
-    f.nc    = s->nc;
-    f.dV11  = s->dV[0];
-    f.dV12  = s->dV[1];
-    f.dV13  = s->dV[2];
-    f.dV22  = s->dV[3];
-    f.dV23  = s->dV[4];
-    f.dV33  = s->dV[5];
-    f.rung  = s->rung;
-    return f;
 }
 
 //! OctreeNsView of the last full sync with the substep's searchExtFactor
@@ -214,7 +157,8 @@ int gravity(sx_sim* s, hipStream_t st, bool newHierarchy)
         if (err) return SX_ERR_TRAVERSAL;
         return SX_OK;
     }
-    sx_fields f    = allFields(s);
+    sx_fields f    = simFields(s); // halos included
+    f.n            = s->n;
     sx_tree   t    = treeView(s);
     double*   cent = s->work.get<double>("bdt.gcenters", 4 * (size_t)s->tree.numNodes);
     float*    mp   = s->work.get<float>("bdt.gmultipoles", 8 * (size_t)s->tree.numNodes);
@@ -225,8 +169,9 @@ int gravity(sx_sim* s, hipStream_t st, bool newHierarchy)
 }
 
 //! computeForces (:222-290)
-int computeForces(sx_sim* s, hipStream_t st, int& ev)
+int computeForces(sx_sim* s, hipStream_t st)
 {
+    StepTimer&  T       = s->timer;
     BdtState&   b       = s->bdt;
     const bool  dist    = distributed(s);
     const bool  synced  = activeRung(b.ts.substep, b.ts.numRungs) == 0;
@@ -234,7 +179,8 @@ int computeForces(sx_sim* s, hipStream_t st, int& ev)
     sx_ctx*     ctx     = s->ctx;
     double      margin  = kHaloMargin * (1.0 + (double)b.ts.numRungs / 40.0); // setHaloFactor (:215)
     float*      h0      = dist ? s->work.get<float>("bdt.h0", s->cap) : nullptr;
-    (void)hipEventRecord(s->ev[ev++], st);
+    sx_fields   f{};
+    BDT_HIP(T.start(st));
     for (int attempt = 0;; ++attempt)
     {
         if (synced)
@@ -247,13 +193,10 @@ int computeForces(sx_sim* s, hipStream_t st, int& ev)
             b.margin = margin;
         }
         else if (attempt == 0) BDT_CK(partialSync(s, st));
-        if (attempt == 0)
-        {
-            (void)hipEventRecord(s->ev[ev++], st);
-            (void)hipEventRecord(s->ev[ev++], st); // search and XMass share one seam call
-        }
-        sx_fields f = allFields(s);
-        sx_tree   t = treeView(s);
+        if (attempt == 0) BDT_HIP(T.stageEnd(Stage::sync, st));
+        f         = simFields(s); // halos included; again after every sync, which moves the conserved fields
+        f.n       = s->n;
+        sx_tree t = treeView(s);
         BDT_CK(sx_xmass(ctx, &b.active, &f, &p, &s->box, &t));
         if (!dist) break;
         unsigned hf = 0;
@@ -274,22 +217,22 @@ int computeForces(sx_sim* s, hipStream_t st, int& ev)
         margin *= 1.5;
         s->haloRetries++;
     }
-    sx_fields f = allFields(s);
-    (void)hipEventRecord(s->ev[ev++], st);
+    // search and XMass share one seam call: FindNeighbors is not marked and reads 0
+    BDT_HIP(T.stageEnd(Stage::XMass, st));
     BDT_CK(haloExchange(s, {{s->xm, 4}}, st));
     BDT_CK(sx_ve_def_gradh(ctx, &b.active, &f, &p, &s->box));
-    (void)hipEventRecord(s->ev[ev++], st);
+    BDT_HIP(T.stageEnd(Stage::VeDefGradh, st));
     BDT_CK(sx_eos(ctx, (uint32_t)s->first, (uint32_t)s->last, p.muiConst, p.gamma, s->temp, s->m, s->kx, s->xm,
                   s->gradh, s->prho, s->c, nullptr, nullptr));
-    (void)hipEventRecord(s->ev[ev++], st);
+    BDT_HIP(T.stageEnd(Stage::EOS, st));
     BDT_CK(haloExchange(s, {{s->vx, 4}, {s->vy, 4}, {s->vz, 4}, {s->prho, 4}, {s->c, 4}, {s->kx, 4}}, st));
     BDT_CK(sx_iad_divv_curlv(ctx, &b.active, &f, &p, &s->box));
     BDT_CK(sx_group_divv_timestep(ctx, (float)p.Krho, &b.active, s->divv, b.groupDt));
-    (void)hipEventRecord(s->ev[ev++], st);
+    BDT_HIP(T.stageEnd(Stage::IadDivvCurlv, st));
     BDT_CK(haloExchange(
         s, {{s->c11, 4}, {s->c12, 4}, {s->c13, 4}, {s->c22, 4}, {s->c23, 4}, {s->c33, 4}, {s->divv, 4}}, st));
     BDT_CK(sx_av_switches(ctx, &b.active, &f, &p, &s->box, b.minDt));
-    (void)hipEventRecord(s->ev[ev++], st);
+    BDT_HIP(T.stageEnd(Stage::AVswitches, st));
     // with avClean the reference exchanges dV11,dV12,dV22,dV23,dV33 + alpha (:262-266); all six are exchanged here
     if (p.avClean)
     {
@@ -304,9 +247,9 @@ int computeForces(sx_sim* s, hipStream_t st, int& ev)
         BDT_CK(haloExchange(s, {{s->alpha, 4}}, st));
         BDT_CK(sx_momentum_energy(ctx, &b.active, b.groupDt, &f, &p, &s->box, nullptr));
     }
-    (void)hipEventRecord(s->ev[ev++], st);
+    BDT_HIP(T.stageEnd(Stage::MomentumEnergy, st));
     if (p.g != 0.0) BDT_CK(gravity(s, st, synced));
-    (void)hipEventRecord(s->ev[ev++], st);
+    BDT_HIP(T.stageEnd(Stage::Gravity, st));
     // groupAccTimestep: groupAccTimestepGpu(d.etaAcc * std::sqrt(d.eps), ...) (ts_rungs.hpp:58-65)
     const float eta = (float)(p.etaAcc * std::sqrt(p.eps));
     BDT_CK(sx_group_acc_timestep(ctx, eta, &b.active, s->ax, s->ay, s->az, b.groupDt));
@@ -362,7 +305,8 @@ int integrate(sx_sim* s, hipStream_t st)
     sx_box         openBox{{0.0, 1.0, 0.0, 1.0, 0.0, 1.0}, {0, 0, 0}}; // cstone::Box<T>(0, 1, open)
     const sx_box&  subBox       = lastSubstep ? s->box : openBox;
     const double   gamma        = s->p.gamma, cv = constCv(s->p);
-    const sx_fields f           = allFields(s);
+    sx_fields      f            = simFields(s); // halos included
+    f.n                         = s->n;
     for (int i = 0; i < ts.numRungs; ++i)
     {
         const bool      useRung = ts.substep == ts.substep % (1 << i); // drift back to the start of the hierarchy
@@ -435,10 +379,9 @@ int stepBdt(sx_sim* s)
         b.ttot        = sc.ttot;
         b.started     = true;
     }
-    int ev = 0;
-    BDT_CK(computeForces(s, st, ev));
+    BDT_CK(computeForces(s, st));
     BDT_CK(integrate(s, st));
-    (void)hipEventRecord(s->ev[ev++], st);
+    BDT_HIP(s->timer.stageEnd(Stage::UpdateQuantities, st));
     // the time-step scalars of ParticlesData, readable through sx_sim_scalars / sx_sim_conserved
     Scalars* hs = s->scHost;
     BDT_HIP(hipMemcpyAsync(hs, s->sc, sizeof(Scalars), hipMemcpyDeviceToHost, st));
@@ -449,9 +392,7 @@ int stepBdt(sx_sim* s)
     if (s->p.g != 0.0 && !distributed(s)) hs->egrav = b.egrav; // single rank: from the seam's traversal
     BDT_HIP(hipMemcpyAsync(s->sc, hs, sizeof(Scalars), hipMemcpyHostToDevice, st));
     BDT_HIP(hipStreamSynchronize(st));
-    for (size_t k = 0; k + 1 < s->ev.size() && (int)k + 1 < ev; ++k)
-        (void)hipEventElapsedTime(&s->stageMs[k], s->ev[k], s->ev[k + 1]);
-    std::fill(s->kernelMs.begin(), s->kernelMs.end(), 0.f);
+    s->timer.collect(); // stages only: the seam calls time no kernel on its own
     b.substeps++;
     return SX_OK;
 }

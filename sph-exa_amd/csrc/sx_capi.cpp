@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/sphexa_hip.h"
+#include "sx_args.hpp"
 #include "sx_comm.hpp"
 #include "sx_direct.hpp"
 #include "sx_gravity.hpp"
@@ -594,60 +595,17 @@ int checkList(sx_ctx* c, const sx_groups* g, const sx_params* p)
 PairArgs pairArgs(sx_ctx* c, const sx_groups* g, const sx_fields* f, const sx_params* p, const sx_box* box,
                   const Records& r)
 {
-    PairArgs a{};
-    a.first          = g->firstBody;
-    a.last           = g->lastBody;
-    a.numGroups      = (g->lastBody - g->firstBody + kGroupSize - 1) / kGroupSize;
-    a.ngmax          = p->ngmax;
-    a.localLists     = c->nb.local;
-    a.nidx           = c->nb.nidx;
-    a.nloc           = c->nb.nloc;
-    a.uni            = c->nb.uni;
-    a.ucount         = c->nb.ucount;
-    a.ucap           = c->nb.ucap;
-    a.packMax        = c->nb.packMax;
-    a.nc             = f->nc;
-    a.rx             = r.rx;
-    a.rv             = r.rv;
-    a.rt             = r.rt;
-    a.rc             = r.rc;
-    a.wh             = c->wh;
-    a.whd            = c->whd;
-    a.box            = toDev(box);
-    a.K              = p->K;
-    a.xm             = f->xm;
-    a.kx             = f->kx;
-    a.gradh          = f->gradh;
-    a.c11            = f->c11;
-    a.c12            = f->c12;
-    a.c13            = f->c13;
-    a.c22            = f->c22;
-    a.c23            = f->c23;
-    a.c33            = f->c33;
-    a.divv           = f->divv;
-    a.curlv          = f->curlv;
-    a.alpha          = f->alpha;
-    a.ax             = f->ax;
-    a.ay             = f->ay;
-    a.az             = f->az;
-    a.du             = f->du;
-    a.minDt          = c->minDt;
-    a.blockDt        = c->arena.get<float>("pair.blockdt", std::max<size_t>(1, (size_t(g->lastBody - g->firstBody) + kCluster - 1) / kCluster));
-    a.alphamin       = p->alphamin;
-    a.alphamax       = p->alphamax;
-    a.decay_constant = p->decay_constant;
-    a.Atmin          = p->Atmin;
-    a.Atmax          = p->Atmax;
-    a.ramp           = p->ramp;
-    a.Kcour          = (float)p->Kcour;
-    a.dV11           = f->dV11;
-    a.dV12           = f->dV12;
-    a.dV13           = f->dV13;
-    a.dV22           = f->dV22;
-    a.dV23           = f->dV23;
-    a.dV33           = f->dV33;
-    a.avClean        = 0;
-    a.active         = c->viewActive;
+    PairArgs a = pairArgsCommon(g->firstBody, g->lastBody, *f, c->nb, *p, toDev(box));
+    a.rx       = r.rx;
+    a.rv       = r.rv;
+    a.rt       = r.rt;
+    a.rc       = r.rc;
+    a.wh       = c->wh;
+    a.whd      = c->whd;
+    a.minDt    = c->minDt;
+    a.blockDt  = c->arena.get<float>("pair.blockdt", std::max<size_t>(1, (size_t(g->lastBody - g->firstBody) + kCluster - 1) / kCluster));
+    a.avClean  = 0;
+    a.active   = c->viewActive;
     return a;
 }
 
@@ -893,30 +851,9 @@ extern "C"
     int sx_positions(sx_ctx* c, uint32_t first, uint32_t last, double dt, double dt_m1, const sx_fields* f,
                      double gamma, float muiConst, const sx_box* box)
     {
-        PosArgs a{};
-        a.first   = first;
-        a.last    = last;
+        PosArgs a = posArgs(first, last, *f, toDev(box), muiConst, gamma);
         a.dt      = dt;
         a.dt_m1   = dt_m1;
-        a.dtPtr   = nullptr;
-        a.box     = toDev(box);
-        a.x       = f->x;
-        a.y       = f->y;
-        a.z       = f->z;
-        a.x_m1    = f->x_m1;
-        a.y_m1    = f->y_m1;
-        a.z_m1    = f->z_m1;
-        a.vx      = f->vx;
-        a.vy      = f->vy;
-        a.vz      = f->vz;
-        a.ax      = f->ax;
-        a.ay      = f->ay;
-        a.az      = f->az;
-        a.temp    = f->temp;
-        a.du      = f->du;
-        a.du_m1   = f->du_m1;
-        a.h       = f->h;
-        a.constCv = idealGasCv(muiConst, gamma);
         c->hydro().positions(a, c->stream);
         SX_HIP(c, hipGetLastError());
         return SX_OK;
@@ -929,16 +866,9 @@ extern "C"
         if (!f->x || !f->y || !f->z || !f->x_m1 || !f->y_m1 || !f->z_m1 || !f->vx || !f->vy || !f->vz || !f->ax ||
             !f->ay || !f->az)
             return SX_ERR_ARG;
-        NbodyPosArgs a{};
-        a.first = first, a.last = last;
-        a.dt = dt, a.dt_m1 = dt_m1;
-        a.box = toDev(box);
+        NbodyPosArgs a = nbodyPosArgs(first, last, *f, toDev(box));
         if ((a.box.fbc[0] || a.box.fbc[1] || a.box.fbc[2]) && !f->h) return SX_ERR_ARG;
-        a.x = f->x, a.y = f->y, a.z = f->z;
-        a.x_m1 = f->x_m1, a.y_m1 = f->y_m1, a.z_m1 = f->z_m1;
-        a.vx = f->vx, a.vy = f->vy, a.vz = f->vz;
-        a.ax = f->ax, a.ay = f->ay, a.az = f->az;
-        a.h    = f->h;
+        a.dt = dt, a.dt_m1 = dt_m1;
         a.keys = keys;
         SX_HIP(c, nbodyIntegrate(a, c->stream));
         return SX_OK;
@@ -1260,8 +1190,7 @@ extern "C"
     {
         if (last > first && !(f->x && f->y && f->z && f->vx && f->vy && f->vz && f->m && (f->u || f->temp)))
             return fail(c, SX_ERR_ARG, "sx_conserved_quantities: null field");
-        ConservedArgs a{first, last, f->x, f->y, f->z, f->vx, f->vy, f->vz, f->m, f->temp, f->u, f->nc,
-                        (double)idealGasCv(muiConst, gamma)};
+        const ConservedArgs a = conservedArgs(first, last, *f, muiConst, gamma);
         double* scratch = c->arena.get<double>("obs.scratch", conservedScratch(last > first ? last - first : 0));
         double* dout    = c->arena.get<double>("obs.out", 10);
         double* hout    = c->arena.pinned<double>("obs.host", 10);
@@ -1313,8 +1242,7 @@ extern "C"
         if (why) return fail(c, SX_ERR_ARG, why);
 
         ObsArgs a{};
-        a.c = ConservedArgs{first, last, f->x, f->y, f->z, f->vx, f->vy, f->vz, f->m, f->temp, f->u, f->nc,
-                            (double)idealGasCv(muiConst, gamma)};
+        a.c         = conservedArgs(first, last, *f, muiConst, gamma);
         a.conserved = cons;
         a.cs = f->c, a.kx = f->kx, a.xm = f->xm, a.ax = f->ax, a.ay = f->ay, a.az = f->az;
         a.ybox    = box ? box->lim[3] - box->lim[2] : 0.0;

@@ -223,57 +223,19 @@ void allocFields(sx_sim* s, size_t cap)
 
 PairArgs simPairArgs(sx_sim* s)
 {
-    PairArgs a{};
-    a.lb             = s->skin.lb; // the step's second set of lists (skin filter), or none
-    a.first          = (uint32_t)s->first;
-    a.last           = (uint32_t)s->last;
-    a.numGroups      = (uint32_t)((s->last - s->first + kGroupSize - 1) / kGroupSize);
-    a.ngmax          = s->p.ngmax;
-    a.localLists     = s->nb.local;
-    a.nidx           = s->nb.nidx;
-    a.nloc           = s->nb.nloc;
-    a.uni            = s->nb.uni;
-    a.ucount         = s->nb.ucount;
-    a.ucap           = s->nb.ucap;
-    a.packMax        = s->nb.packMax;
-    a.nc             = s->nc;
-    a.rx             = s->rx;
-    a.rv             = s->rv;
-    a.rt             = s->rt;
-    a.rc             = s->rc;
-    a.wh             = sx_ctx_table_internal(s->ctx, 0);
-    a.whd            = sx_ctx_table_internal(s->ctx, 1);
-    a.box            = s->dbox;
-    a.K              = s->p.K;
-    a.xm             = s->xm;
-    a.kx             = s->kx;
-    a.gradh          = s->gradh;
-    a.c11            = s->c11;
-    a.c12            = s->c12;
-    a.c13            = s->c13;
-    a.c22            = s->c22;
-    a.c23            = s->c23;
-    a.c33            = s->c33;
-    a.divv           = s->divv;
-    a.curlv          = s->curlv;
-    a.alpha          = s->alpha;
-    a.ax             = s->ax;
-    a.ay             = s->ay;
-    a.az             = s->az;
-    a.du             = s->du;
-    a.minDt          = &s->sc->courant;
-    a.blockDt        = s->mem.get<float>("pair.blockdt", std::max<size_t>(1, (s->last - s->first + kCluster - 1) / kCluster));
-    a.alphamin       = s->p.alphamin;
-    a.alphamax       = s->p.alphamax;
-    a.decay_constant = s->p.decay_constant;
-    a.dtPtr          = &s->sc->minDt;
-    a.Atmin          = s->p.Atmin;
-    a.Atmax          = s->p.Atmax;
-    a.ramp           = s->p.ramp;
-    a.Kcour          = (float)s->p.Kcour;
-    a.dV11 = s->dV[0], a.dV12 = s->dV[1], a.dV13 = s->dV[2], a.dV22 = s->dV[3], a.dV23 = s->dV[4], a.dV33 = s->dV[5];
-    a.rs   = s->rs;
-    a.avClean = s->p.avClean ? 1 : 0;
+    PairArgs a = pairArgsCommon((uint32_t)s->first, (uint32_t)s->last, simFields(s), s->nb, s->p, s->dbox);
+    a.lb       = s->skin.lb; // the step's second set of lists (skin filter), or none
+    a.rx       = s->rx;
+    a.rv       = s->rv;
+    a.rt       = s->rt;
+    a.rc       = s->rc;
+    a.rs       = s->rs;
+    a.wh       = sx_ctx_table_internal(s->ctx, 0);
+    a.whd      = sx_ctx_table_internal(s->ctx, 1);
+    a.minDt    = &s->sc->courant;
+    a.blockDt  = s->mem.get<float>("pair.blockdt", std::max<size_t>(1, (s->last - s->first + kCluster - 1) / kCluster));
+    a.dtPtr    = &s->sc->minDt;
+    a.avClean  = s->p.avClean ? 1 : 0;
     return a;
 }
 
@@ -445,7 +407,6 @@ struct StepCtx
     bool               skinOn; // the step searches through skin lists (sx_skin.hpp)
     bool               reuse;  // ... as a reuse step: order and tree of the last full build are kept, the skin lists
                                // filtered (false again when the step's search is redone from a full sync)
-    int                ev;     // the next stage-event slot (s->ev)
     const float*       powTab; // the h-update table of the step's search
 };
 
@@ -505,16 +466,21 @@ int searchReps(sx_sim* s, const NsArgs& na, hipStream_t st)
     const int R  = std::max(1, atoi(reps));
     s->skin.listsKept = false; // this search rewrites the exact lists
     s->skin.lb        = ListsB{};
-    SIM_HIP(hipEventRecord(s->kev[0], st));
+    hipEvent_t t0 = nullptr, t1 = nullptr; // its own: the step's timer is mid-step (a failing run keeps them)
+    SIM_HIP(hipEventCreate(&t0));
+    SIM_HIP(hipEventCreate(&t1));
+    SIM_HIP(hipEventRecord(t0, st));
     for (int r = 0; r < R; ++r)
     {
         SIM_HIP(hipMemsetAsync(s->stats, 0, kStatsWords * 4, st));
         SIM_HIP(findNeighbors(x, st));
     }
-    SIM_HIP(hipEventRecord(s->kev[1], st));
-    SIM_HIP(hipEventSynchronize(s->kev[1]));
+    SIM_HIP(hipEventRecord(t1, st));
+    SIM_HIP(hipEventSynchronize(t1));
     float ms = 0;
-    (void)hipEventElapsedTime(&ms, s->kev[0], s->kev[1]);
+    (void)hipEventElapsedTime(&ms, t0, t1);
+    (void)hipEventDestroy(t0);
+    (void)hipEventDestroy(t1);
     fprintf(stderr, "search-reps: %.3f ms per search (%d reps)\n", ms / R, R);
     return SX_OK;
 }
@@ -563,7 +529,8 @@ int searchOnce(sx_sim* s, StepCtx& c, const NsArgs& na, SkinCounts& skc, bool& r
     hipStream_t st = c.st;
     SIM_HIP(hipMemsetAsync(s->stats, 0, kStatsWords * 4, st));
     resetScalarsKernel<<<1, 1, 0, st>>>(s->sc);
-    SIM_HIP(hipEventRecord(s->kev[0], st));
+    // a repeated attempt begins the interval again; one given up below (skinRedoFromSync) never ends it
+    SIM_HIP(s->timer.begin(Kernel::findNeighbors, st));
     resync = false;
     if (c.skinOn)
     {
@@ -589,7 +556,7 @@ int searchOnce(sx_sim* s, StepCtx& c, const NsArgs& na, SkinCounts& skc, bool& r
         s->skin.lb        = ListsB{}; // the plain search writes the primary set
         SIM_HIP(findNeighbors(na, st));
     }
-    SIM_HIP(hipEventRecord(s->kev[1], st));
+    SIM_HIP(s->timer.end(Kernel::findNeighbors, st));
     SIM_HIP(hipMemcpyAsync(s->statsHost, s->stats, kStatsWords * 4, hipMemcpyDeviceToHost, st));
     if (s->evStats) SIM_HIP(hipEventRecord(s->evStats, st));
     return SX_OK;
@@ -648,7 +615,7 @@ int searchStage(sx_sim* s, StepCtx& c)
         // 2 h (1 + s) of a target (several ranks)
         const double skinMargin = c.skinOn ? 1.0 + (double)s->skin.cur : 1.0;
         if (int e = syncForSearch(s, c, h0, restoreH0, margin * skinMargin, synced)) return e;
-        if (attempt == 0) SIM_HIP(hipEventRecord(s->ev[c.ev++], st));
+        if (attempt == 0) SIM_HIP(s->timer.stageEnd(Stage::sync, st));
 
         NsArgs na{};
         if (int e = buildSearchArgs(s, na)) return e;
@@ -687,34 +654,33 @@ int searchStage(sx_sim* s, StepCtx& c)
         }
         break;
     }
-    SIM_HIP(hipEventRecord(s->ev[c.ev++], st));
+    SIM_HIP(s->timer.stageEnd(Stage::FindNeighbors, st));
     return SX_OK;
 }
 
 /*! HydroProp::computeForces (std_hydro.hpp:124-166): density, EOS, [v,rho,p,c] halos, IAD, [c_ij] halos, momentum +
- *  energy.  The stage/kernel event slots follow the VE order: density in "xmass", IAD in "iadDivvCurlv",
- *  momentumEnergySTD in "momentumEnergy". */
+ *  energy.  The times go under the VE names: density under XMass / xmass, IAD under IadDivvCurlv / iadDivvCurlv,
+ *  momentumEnergySTD under MomentumEnergy / momentumEnergy. */
 int forcesStd(sx_sim* s, StepCtx& c, const PairArgs& pa)
 {
     hipStream_t        st = c.st;
     const HydroLaunch& H  = c.H;
-    int&               ev = c.ev;
+    StepTimer&         T  = s->timer;
     packXHalos(s, st);
-    SIM_HIP(hipEventRecord(s->kev[2], st));
+    SIM_HIP(T.begin(Kernel::xmass, st));
     PairArgs da = pa;
     da.xm       = s->rho; // computeDensity: xmass written to rho (xmass_gpu.cu:151-153)
     xmassRest(s, H, da, st);
     H.xmassToRho((uint32_t)s->first, (uint32_t)s->last, s->m, s->rho, st);
-    SIM_HIP(hipEventRecord(s->kev[3], st));
-    SIM_HIP(hipEventRecord(s->ev[ev++], st));
-    SIM_HIP(hipEventRecord(s->kev[4], st));
-    SIM_HIP(hipEventRecord(s->kev[5], st));
+    SIM_HIP(T.end(Kernel::xmass, st));
+    SIM_HIP(T.stageEnd(Stage::XMass, st));
     EosArgs ea{(uint32_t)s->first, (uint32_t)s->last, s->p.muiConst, s->p.gamma, s->temp, s->m, nullptr, nullptr,
                nullptr, nullptr, s->c, s->rho, s->pres};
     H.eosStd(ea, st);
-    SIM_HIP(hipEventRecord(s->ev[ev++], st));
-    SIM_HIP(hipEventRecord(s->ev[ev++], st));
-    SIM_HIP(hipEventRecord(s->kev[6], st));
+    // the std EOS is what this propagator reports as the VeDefGradh stage (consumers read it there); the EOS and
+    // AVswitches stages and the veDefGradh and avSwitches kernels are not marked and read 0
+    SIM_HIP(T.stageEnd(Stage::VeDefGradh, st));
+    SIM_HIP(T.begin(Kernel::iadDivvCurlv, st));
     if (int e = exchangeThen(
             s, H, {{s->vx, 4}, {s->vy, 4}, {s->vz, 4}, {s->rho, 4}, {s->pres, 4}, {s->c, 4}},
             [&](size_t a, size_t b)
@@ -724,12 +690,9 @@ int forcesStd(sx_sim* s, StepCtx& c, const PairArgs& pa)
             },
             [&](const PairArgs& p) { H.iadStd(p, st); }, pa, st))
         return e;
-    SIM_HIP(hipEventRecord(s->kev[7], st));
-    SIM_HIP(hipEventRecord(s->ev[ev++], st));
-    SIM_HIP(hipEventRecord(s->kev[8], st));
-    SIM_HIP(hipEventRecord(s->kev[9], st));
-    SIM_HIP(hipEventRecord(s->ev[ev++], st));
-    SIM_HIP(hipEventRecord(s->kev[10], st));
+    SIM_HIP(T.end(Kernel::iadDivvCurlv, st));
+    SIM_HIP(T.stageEnd(Stage::IadDivvCurlv, st));
+    SIM_HIP(T.begin(Kernel::momentumEnergy, st));
     if (int e = exchangeThen(
             s, H, {{s->c11, 4}, {s->c12, 4}, {s->c13, 4}, {s->c22, 4}, {s->c23, 4}, {s->c33, 4}},
             [&](size_t a, size_t b)
@@ -739,8 +702,8 @@ int forcesStd(sx_sim* s, StepCtx& c, const PairArgs& pa)
             },
             [&](const PairArgs& p) { H.momentumStd(p, st); }, pa, st))
         return e;
-    SIM_HIP(hipEventRecord(s->kev[11], st));
-    SIM_HIP(hipEventRecord(s->ev[ev++], st));
+    SIM_HIP(T.end(Kernel::momentumEnergy, st));
+    SIM_HIP(T.stageEnd(Stage::MomentumEnergy, st));
     return SX_OK;
 }
 
@@ -750,7 +713,7 @@ int forcesVe(sx_sim* s, StepCtx& c, PairArgs pa)
 {
     hipStream_t        st = c.st;
     const HydroLaunch& H  = c.H;
-    int&               ev = c.ev;
+    StepTimer&         T  = s->timer;
     // ---- XMass
     packXHalos(s, st);
     // the cluster kernels write the locals' records as they produce them (PairArgs::rtOut / rcOut, EosArgs):
@@ -763,16 +726,16 @@ int forcesVe(sx_sim* s, StepCtx& c, PairArgs pa)
         if (a < s->first) fn(a, std::min(b, (size_t)s->first));
         if (b > s->last) fn(std::max(a, (size_t)s->last), b);
     };
-    SIM_HIP(hipEventRecord(s->kev[2], st));
+    SIM_HIP(T.begin(Kernel::xmass, st));
     {
         PairArgs xa = pa;
         xa.rtOut    = fused ? s->rt : nullptr;
         xmassRest(s, H, xa, st);
     }
-    SIM_HIP(hipEventRecord(s->kev[3], st));
+    SIM_HIP(T.end(Kernel::xmass, st));
     // ---- [xm] halos, VeDefGradh (overlapped: interior clusters while the halos are in flight)
-    SIM_HIP(hipEventRecord(s->ev[ev++], st));
-    SIM_HIP(hipEventRecord(s->kev[4], st));
+    SIM_HIP(T.stageEnd(Stage::XMass, st));
+    SIM_HIP(T.begin(Kernel::veDefGradh, st));
     // the cluster VeDefGradh also runs the EOS of its targets (PairArgs::eos): kx and gradh stay in registers
     PairArgs va = pa;
     if (fused)
@@ -787,8 +750,8 @@ int forcesVe(sx_sim* s, StepCtx& c, PairArgs pa)
             },
             [&](const PairArgs& p) { H.veDefGradh(p, st); }, va, st))
         return e;
-    SIM_HIP(hipEventRecord(s->kev[5], st));
-    SIM_HIP(hipEventRecord(s->ev[ev++], st));
+    SIM_HIP(T.end(Kernel::veDefGradh, st));
+    SIM_HIP(T.stageEnd(Stage::VeDefGradh, st));
     // ---- EOS (unless fused above), then the v/prho/c/kx halo exchange
     if (!fused)
     {
@@ -796,7 +759,7 @@ int forcesVe(sx_sim* s, StepCtx& c, PairArgs pa)
                    s->xm, s->gradh, s->prho, s->c, nullptr, nullptr};
         H.eos(ea, st);
     }
-    SIM_HIP(hipEventRecord(s->ev[ev++], st));
+    SIM_HIP(T.stageEnd(Stage::EOS, st));
     // ---- [v, prho, c, kx] halos, IAD + divv/curlv, rho time-step
     auto packVT = [&](size_t a, size_t b)
     {
@@ -808,15 +771,15 @@ int forcesVe(sx_sim* s, StepCtx& c, PairArgs pa)
              });
     };
     pa.rcOut = fused ? s->rc : nullptr; // IAD writes the locals' {c_ij, divv}
-    SIM_HIP(hipEventRecord(s->kev[6], st));
+    SIM_HIP(T.begin(Kernel::iadDivvCurlv, st));
     if (int e = exchangeThen(s, H, {{s->vx, 4}, {s->vy, 4}, {s->vz, 4}, {s->prho, 4}, {s->c, 4}, {s->kx, 4}},
                              packVT, [&](const PairArgs& p) { H.iadDivvCurlv(p, st); }, pa, st))
         return e;
-    SIM_HIP(hipEventRecord(s->kev[7], st));
+    SIM_HIP(T.end(Kernel::iadDivvCurlv, st));
     SIM_HIP(maxFloat(s->divv, (uint32_t)s->first, (uint32_t)s->last, &s->sc->maxDivvU, st));
-    SIM_HIP(hipEventRecord(s->ev[ev++], st));
+    SIM_HIP(T.stageEnd(Stage::IadDivvCurlv, st));
     // ---- [c_ij, divv] halos, AV switches
-    SIM_HIP(hipEventRecord(s->kev[8], st));
+    SIM_HIP(T.begin(Kernel::avSwitches, st));
     if (int e = exchangeThen(
             s, H, {{s->c11, 4}, {s->c12, 4}, {s->c13, 4}, {s->c22, 4}, {s->c23, 4}, {s->c33, 4}, {s->divv, 4}},
             [&](size_t a, size_t b)
@@ -841,8 +804,8 @@ int forcesVe(sx_sim* s, StepCtx& c, PairArgs pa)
             pa, st))
         return e;
     pa.rcOut = nullptr;
-    SIM_HIP(hipEventRecord(s->kev[9], st));
-    SIM_HIP(hipEventRecord(s->ev[ev++], st));
+    SIM_HIP(T.end(Kernel::avSwitches, st));
+    SIM_HIP(T.stageEnd(Stage::AVswitches, st));
     // ---- [alpha (+ dV)] halos, momentum + energy.  With avClean the reference exchanges dV11,dV12,dV22,
     //      dV23,dV33 + alpha (ve_hydro.hpp:182-185) and leaves the halo dV13 undefined; all six are exchanged
     //      here so the result does not depend on the decomposition
@@ -852,7 +815,7 @@ int forcesVe(sx_sim* s, StepCtx& c, PairArgs pa)
              { packT(v - u, s->xm + u, s->kx + u, s->prho + u, s->alpha + u, s->rt + u, st); });
     };
     auto launchMe = [&](const PairArgs& p) { H.momentumEnergy(p, st); };
-    SIM_HIP(hipEventRecord(s->kev[10], st));
+    SIM_HIP(T.begin(Kernel::momentumEnergy, st));
     if (s->p.avClean)
     {
         if (int e = exchangeThen(s, H,
@@ -862,8 +825,8 @@ int forcesVe(sx_sim* s, StepCtx& c, PairArgs pa)
             return e;
     }
     else if (int e = exchangeThen(s, H, {{s->alpha, 4}}, packTa, launchMe, pa, st)) return e;
-    SIM_HIP(hipEventRecord(s->kev[11], st));
-    SIM_HIP(hipEventRecord(s->ev[ev++], st));
+    SIM_HIP(T.end(Kernel::momentumEnergy, st));
+    SIM_HIP(T.stageEnd(Stage::MomentumEnergy, st));
     return SX_OK;
 }
 
@@ -872,28 +835,8 @@ int integrateStage(sx_sim* s, StepCtx& c)
 {
     hipStream_t st = c.st;
     if (int e = globalTimestep(s, c.dist, st)) return e;
-    PosArgs qa{};
-    qa.first   = (uint32_t)s->first;
-    qa.last    = (uint32_t)s->last;
+    PosArgs qa = posArgs((uint32_t)s->first, (uint32_t)s->last, simFields(s), s->dbox, s->p.muiConst, s->p.gamma);
     qa.dtPtr   = &s->sc->minDt;
-    qa.box     = s->dbox;
-    qa.x       = s->x;
-    qa.y       = s->y;
-    qa.z       = s->z;
-    qa.x_m1    = s->xm1;
-    qa.y_m1    = s->ym1;
-    qa.z_m1    = s->zm1;
-    qa.vx      = s->vx;
-    qa.vy      = s->vy;
-    qa.vz      = s->vz;
-    qa.ax      = s->ax;
-    qa.ay      = s->ay;
-    qa.az      = s->az;
-    qa.temp    = s->temp;
-    qa.du      = s->du;
-    qa.du_m1   = s->dum1;
-    qa.h       = s->h;
-    qa.constCv = idealGasCv(s->p.muiConst, s->p.gamma);
     // one rank: the next localSync's keys come from this pass (the coordinates are in registers here)
     // (not when the next step will be served by the skin filter: it does not sync; should it resync after all,
     // localSync computes the keys itself, keysFresh being false)
@@ -904,7 +847,7 @@ int integrateStage(sx_sim* s, StepCtx& c)
     c.H.positions(qa, st);
     s->keysFresh = qa.keys != nullptr;
     c.H.updateH((uint32_t)s->first, (uint32_t)s->last, s->p.ng0, s->nc, s->h, c.powTab, st);
-    SIM_HIP(hipEventRecord(s->ev[c.ev++], st));
+    SIM_HIP(s->timer.stageEnd(Stage::UpdateQuantities, st));
     return SX_OK;
 }
 
@@ -915,10 +858,7 @@ int finishStep(sx_sim* s, const StepCtx& c)
     SIM_HIP(hipGetLastError());
     SIM_HIP(hipStreamSynchronize(c.st));
 
-    for (size_t k = 0; k < s->stageMs.size(); ++k)
-        (void)hipEventElapsedTime(&s->stageMs[k], s->ev[k], s->ev[k + 1]);
-    for (size_t k = 0; k < s->kernelMs.size(); ++k)
-        (void)hipEventElapsedTime(&s->kernelMs[k], s->kev[2 * k], s->kev[2 * k + 1]);
+    s->timer.collect();
     if (s->turb)
         for (int k = 0; k < 2; ++k)
             (void)hipEventElapsedTime(&s->turb->ms[k], s->turb->ev[k], s->turb->ev[k + 1]);
@@ -967,9 +907,9 @@ static int stepImpl(sx_sim* s)
     if (s->p.propagator >= 2) return s->p.propagator == 2 ? stepBdt(s) : stepNbody(s);
     StepCtx c{(hipStream_t)sx_ctx_stream_internal(s->ctx),
               sx_ctx_exact_internal(s->ctx) ? hydro_exact() : hydro_fast(),
-              s->comm && s->comm->size() > 1, /*skinOn*/ skinUsable(s), /*reuse*/ false, /*ev*/ 0, /*powTab*/ nullptr};
+              s->comm && s->comm->size() > 1, /*skinOn*/ skinUsable(s), /*reuse*/ false, /*powTab*/ nullptr};
     hipStream_t st = c.st;
-    SIM_HIP(hipEventRecord(s->ev[c.ev++], st));
+    SIM_HIP(s->timer.start(st));
 
     // skin lists (sx_skin.hpp): a reuse step keeps the order and tree of the last full build and filters the
     // skin lists instead of syncing and searching
@@ -986,11 +926,11 @@ static int stepImpl(sx_sim* s)
     const PairArgs pa = simPairArgs(s);
     if (int e = s->p.propagator == 1 ? forcesStd(s, c, pa) : forcesVe(s, c, pa)) return e;
     // ---- self-gravity (ve_hydro.hpp:193-202), added to ax, ay, az
-    SIM_HIP(hipEventRecord(s->kev[12], st));
+    SIM_HIP(s->timer.begin(Kernel::gravity, st));
     if (s->p.g != 0.0)
         if (int e = gravityStage(s, st, c.dist, c.reuse)) return e;
-    SIM_HIP(hipEventRecord(s->kev[13], st));
-    SIM_HIP(hipEventRecord(s->ev[c.ev++], st));
+    SIM_HIP(s->timer.end(Kernel::gravity, st));
+    SIM_HIP(s->timer.stageEnd(Stage::Gravity, st));
     // ---- turbulence stirring (TurbVeProp::computeForces, turb_ve.hpp:114-119)
     if (s->turb)
         if (int e = turbStep(s, st)) return e;
@@ -1053,21 +993,6 @@ extern "C"
             delete s;
             return SX_ERR_NOMEM;
         }
-        const char* names[] = {"sync",         "FindNeighbors", "XMass",          "VeDefGradh", "EOS",
-                               "IadDivvCurlv", "AVswitches",    "MomentumEnergy", "Gravity",    "UpdateQuantities"};
-        s->stageNames.assign(std::begin(names), std::end(names));
-        s->ev.resize(s->stageNames.size() + 1);
-        for (auto& e : s->ev)
-            (void)hipEventCreate(&e);
-        s->stageMs.assign(s->stageNames.size(), 0.f);
-        const char* knames[] = {"findNeighbors", "xmass",          "veDefGradh", "iadDivvCurlv",
-                                "avSwitches",    "momentumEnergy", "gravity"};
-        s->kernelNames.assign(std::begin(knames), std::end(knames));
-        if (p->propagator == 3) s->kernelNames.push_back("nbodyIntegrate");
-        s->kev.resize(2 * s->kernelNames.size());
-        for (auto& e : s->kev)
-            (void)hipEventCreate(&e);
-        s->kernelMs.assign(s->kernelNames.size(), 0.f);
         if (hipStreamCreateWithFlags(&s->commStream, hipStreamNonBlocking) != hipSuccess) s->commStream = nullptr;
         (void)hipEventCreateWithFlags(&s->evProd, hipEventDisableTiming);
         (void)hipEventCreateWithFlags(&s->evComm, hipEventDisableTiming);
@@ -1083,7 +1008,7 @@ extern "C"
         }
         (void)hipEventCreateWithFlags(&s->evAuxIn, hipEventDisableTiming);
         (void)hipEventCreateWithFlags(&s->evAuxOut, hipEventDisableTiming);
-        Scalars init{1e-6, 1e-6, 0.0, INFINITY, INFINITY, 0.0, 1e10f, 0, 0.0, 0ull, 0u};
+        const Scalars init = freshScalars();
         (void)hipMemcpy(s->sc, &init, sizeof(Scalars), hipMemcpyHostToDevice);
         *out = s;
         return SX_OK;
@@ -1093,10 +1018,6 @@ extern "C"
     {
         if (!s) return;
         (void)hipDeviceSynchronize();
-        for (auto& e : s->ev)
-            (void)hipEventDestroy(e);
-        for (auto& e : s->kev)
-            (void)hipEventDestroy(e);
         if (s->evProd) (void)hipEventDestroy(s->evProd);
         if (s->evComm) (void)hipEventDestroy(s->evComm);
         if (s->evStats) (void)hipEventDestroy(s->evStats);
@@ -1241,7 +1162,7 @@ extern "C"
                                                      (float)hInit, (float)(1.0 / N), ener0, width * width, 1e-8, cv);
         if (s->rung && n) SIM_HIP(hipMemsetAsync(s->rung, 0, n, st));
         s->bdt.started = false;
-        Scalars init{1e-6, 1e-6, 0.0, INFINITY, INFINITY, 0.0, 1e10f, 0, 0.0, 0ull, 0u};
+        const Scalars init = freshScalars();
         SIM_HIP(hipMemcpyAsync(s->sc, &init, sizeof(Scalars), hipMemcpyHostToDevice, st));
         SIM_HIP(hipStreamSynchronize(st));
         return SX_OK;
@@ -1284,7 +1205,7 @@ extern "C"
         SIM_HIP(cp(s->id, id, 8));
         if (s->rung) SIM_HIP(hipMemset(s->rung, 0, n));
         s->bdt.started = false;
-        Scalars init{minDt, minDt_m1, 0.0, INFINITY, INFINITY, 0.0, 1e10f, 0};
+        const Scalars init = freshScalars(minDt, minDt_m1);
         SIM_HIP(hipMemcpy(s->sc, &init, sizeof(Scalars), hipMemcpyHostToDevice));
         return SX_OK;
     }
@@ -1292,61 +1213,16 @@ extern "C"
     int sx_sim_fields(sx_sim* s, sx_fields* f, uint64_t** id)
     {
         // pointers to the LOCAL particles [first, last) of the last step
-        std::memset(f, 0, sizeof(*f));
-        size_t o = s->first;
-        // a field the propagator does not keep is NULL (the gravity-only propagator: every thermal and hydro field)
-        auto at = [o](auto* p) { return p ? p + o : nullptr; };
-        f->n     = s->last - s->first;
-        f->x     = at(s->x);
-        f->y     = at(s->y);
-        f->z     = at(s->z);
-        f->x_m1  = at(s->xm1);
-        f->y_m1  = at(s->ym1);
-        f->z_m1  = at(s->zm1);
-        f->vx    = at(s->vx);
-        f->vy    = at(s->vy);
-        f->vz    = at(s->vz);
-        f->prho  = at(s->prho);
-        f->rho   = at(s->rho);
-        f->p     = at(s->pres);
-        f->h     = at(s->h);
-        f->m     = at(s->m);
-        f->c     = at(s->c);
-        f->ax    = at(s->ax);
-        f->ay    = at(s->ay);
-        f->az    = at(s->az);
-        f->du    = at(s->du);
-        f->du_m1 = at(s->dum1);
-        f->c11   = at(s->c11);
-        f->c12   = at(s->c12);
-        f->c13   = at(s->c13);
-        f->c22   = at(s->c22);
-        f->c23   = at(s->c23);
-        f->c33   = at(s->c33);
-        f->temp  = at(s->temp);
-        f->xm    = at(s->xm);
-        f->kx    = at(s->kx);
-        f->divv  = at(s->divv);
-        f->curlv = at(s->curlv);
-        f->alpha = at(s->alpha);
-        f->gradh = at(s->gradh);
-        f->keys  = at(s->keys);
-        f->nc    = at(s->nc);
-        f->rung  = at(s->rung);
-        if (s->dV[0])
-        {
-            f->dV11 = s->dV[0] + o, f->dV12 = s->dV[1] + o, f->dV13 = s->dV[2] + o;
-            f->dV22 = s->dV[3] + o, f->dV23 = s->dV[4] + o, f->dV33 = s->dV[5] + o;
-        }
-        if (id) *id = s->id + o;
+        *f   = simFields(s, s->first);
+        f->n = s->last - s->first;
+        if (id) *id = s->id + s->first;
         return SX_OK;
     }
 
     int sx_sim_conserved(sx_sim* s, double out[13])
     {
         hipStream_t   st = (hipStream_t)sx_ctx_stream_internal(s->ctx);
-        ConservedArgs a{s->first, s->last, s->x, s->y, s->z, s->vx, s->vy, s->vz, s->m, s->temp, nullptr, s->nc,
-                        (double)idealGasCv(s->p.muiConst, s->p.gamma)};
+        const ConservedArgs a = conservedArgs(s->first, s->last, simFields(s), s->p.muiConst, s->p.gamma);
         double* scratch = s->work.get<double>("obs.scratch", conservedScratch(s->last - s->first));
         double* q       = s->work.get<double>("obs.q", 10);
         SIM_HIP(conservedQuantities(a, scratch, q, st));
@@ -1597,8 +1473,7 @@ extern "C"
         }
         hipStream_t st = (hipStream_t)sx_ctx_stream_internal(s->ctx);
         ObsArgs     a{};
-        a.c = ConservedArgs{s->first, s->last, s->x, s->y, s->z, s->vx, s->vy, s->vz, s->m, s->temp, nullptr, s->nc,
-                            (double)idealGasCv(s->p.muiConst, s->p.gamma)};
+        a.c         = conservedArgs(s->first, s->last, simFields(s), s->p.muiConst, s->p.gamma);
         a.conserved = true;
         a.cs = s->c, a.kx = s->kx, a.xm = s->xm, a.ax = s->ax, a.ay = s->ay, a.az = s->az;
         a.ybox    = s->box.lim[3] - s->box.lim[2];
@@ -1679,11 +1554,13 @@ extern "C"
 
     int sx_sim_kernel_times(sx_sim* s, float* ms, int cap, const char** names)
     {
-        int k = 0;
-        for (; k < cap && k < (int)s->kernelMs.size(); ++k)
+        // Kernel::nbodyIntegrate, the last one, is the gravity-only propagator's alone
+        const int n = s->p.propagator == 3 ? kNumKernels : kNumKernels - 1;
+        int       k = 0;
+        for (; k < cap && k < n; ++k)
         {
-            ms[k] = s->kernelMs[k];
-            if (names) names[k] = s->kernelNames[k].c_str();
+            ms[k] = s->timer.kernelMs[k];
+            if (names) names[k] = kKernelNames[k];
         }
         return k;
     }
@@ -1691,10 +1568,10 @@ extern "C"
     int sx_sim_stage_times(sx_sim* s, float* ms, int cap, const char** names)
     {
         int k = 0;
-        for (; k < cap && k < (int)s->stageMs.size(); ++k)
+        for (; k < cap && k < kNumStages; ++k)
         {
-            ms[k] = s->stageMs[k];
-            if (names) names[k] = s->stageNames[k].c_str();
+            ms[k] = s->timer.stageMs[k];
+            if (names) names[k] = kStageNames[k];
         }
         return k;
     }

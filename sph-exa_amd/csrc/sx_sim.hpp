@@ -1,12 +1,14 @@
 /*! @file sx_sim.hpp
  * @brief the device-resident simulation object behind sx_sim_* (sx_sim.cpp: HydroVeProp / HydroProp steps;
  *        sx_sim_domain.cpp: the SFC domain; sx_sim_gravity.cpp: self-gravity; sx_sim_skin.cpp: skin lists;
- *        sx_bdt.cpp: HydroVeBdtProp substeps on the same domain; sx_sim_nbody.cpp: the gravity-only NbodyProp step)
+ *        sx_bdt.cpp: HydroVeBdtProp substeps on the same domain; sx_sim_nbody.cpp: the gravity-only NbodyProp step).
+ *        Every step driver times its stages and hot kernels through the sim's StepTimer (sx_step_timer.hpp).
  */
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <initializer_list>
 #include <string>
 #include <utility>
@@ -16,6 +18,7 @@
 #include "sx_comm.hpp"
 #include "sx_hydro.hpp"
 #include "sx_map.hpp"
+#include "sx_step_timer.hpp"
 #include "sx_tree.hpp"
 
 namespace sx::turb
@@ -37,6 +40,14 @@ struct Scalars
     unsigned long long maxAccSqBits; // max |a|^2 of the locals (bit image of a non-negative double)
     unsigned gravErr;
 };
+
+//! the scalars of a state that has not stepped: the time-steps given, ttot 0, the step's accumulators at their start
+//! values (resetStepScalars)
+inline Scalars freshScalars(double minDt = 1e-6, double minDt_m1 = 1e-6)
+{
+    return Scalars{.minDt = minDt, .minDt_m1 = minDt_m1, .ttot = 0.0, .minDtCourant = INFINITY, .minDtRho = INFINITY,
+                   .dtCand = 0.0, .courant = 1e10f, .maxDivvU = 0u, .egrav = 0.0, .maxAccSqBits = 0ull, .gravErr = 0u};
+}
 
 //! the conserved fields that travel with a particle in the SFC exchange (rung: ve-bdt only, else nullptr)
 struct Fields
@@ -245,12 +256,7 @@ struct sx_sim
     uint32_t*   clsHost{nullptr}; // pinned copy of clsCount
     uint32_t    nInterior{0}, nBoundary{0};
 
-    std::vector<hipEvent_t>  ev;
-    std::vector<std::string> stageNames;
-    std::vector<hipEvent_t>  kev; // begin/end pairs around the hot kernels alone
-    std::vector<std::string> kernelNames;
-    std::vector<float>       kernelMs;
-    std::vector<float>       stageMs;
+    sx::sim::StepTimer       timer; // stage and kernel times of the last step
     sx_nbstats               lastStats{};
     int                      haloRetries{0};
     uint64_t                 gravHalos{0};    // gravity halos of the last multi-rank step

@@ -1,7 +1,9 @@
 /*! @file sx_sim_internal.hpp
  * @brief what the translation units of the step driver share beyond sx_sim.hpp: sx_sim.cpp (C API, step orchestrator),
  *        sx_sim_domain.cpp (SFC domain), sx_sim_gravity.cpp (self-gravity), sx_sim_skin.cpp (skin-list driver),
- *        sx_sim_nbody.cpp (gravity-only step)
+ *        sx_sim_nbody.cpp (gravity-only step), sx_bdt.cpp (ve-bdt substeps).  simFields is the one place that lists
+ *        the sim's arrays as a field view; kernel arguments are built from that view (sx_args.hpp).  Step times go
+ *        through s->timer (sx_step_timer.hpp): marks by stage and kernel name, one collect() at the end of the step.
  */
 #pragma once
 
@@ -18,6 +20,7 @@
 #include <vector>
 
 #include "../../include/sphexa_hip.h"
+#include "sx_args.hpp"
 #include "sx_comm.hpp"
 #include "sx_gravity.hpp"
 #include "sx_hydro.hpp"
@@ -61,6 +64,30 @@ struct __attribute__((aligned(16))) ReqBox
 };
 
 static inline unsigned grid(size_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
+
+/*! sphexa::ParticlesData fields of the simulation from particle `offset` on (0: every particle, halos included).  A
+ *  field the propagator does not keep stays NULL under an offset (the gravity-only propagator: every thermal and hydro
+ *  field).  n is the caller's to set. */
+inline sx_fields simFields(const sx_sim* s, size_t offset = 0)
+{
+    auto at = [offset](auto* p) { return p ? p + offset : nullptr; };
+    sx_fields f{};
+    f.x = at(s->x), f.y = at(s->y), f.z = at(s->z);
+    f.x_m1 = at(s->xm1), f.y_m1 = at(s->ym1), f.z_m1 = at(s->zm1);
+    f.vx = at(s->vx), f.vy = at(s->vy), f.vz = at(s->vz);
+    f.rho = at(s->rho), f.p = at(s->pres), f.prho = at(s->prho);
+    f.h = at(s->h), f.m = at(s->m), f.c = at(s->c);
+    f.ax = at(s->ax), f.ay = at(s->ay), f.az = at(s->az);
+    f.du = at(s->du), f.du_m1 = at(s->dum1), f.temp = at(s->temp);
+    f.c11 = at(s->c11), f.c12 = at(s->c12), f.c13 = at(s->c13);
+    f.c22 = at(s->c22), f.c23 = at(s->c23), f.c33 = at(s->c33);
+    f.xm = at(s->xm), f.kx = at(s->kx), f.gradh = at(s->gradh);
+    f.divv = at(s->divv), f.curlv = at(s->curlv), f.alpha = at(s->alpha);
+    f.keys = at(s->keys), f.nc = at(s->nc), f.rung = at(s->rung);
+    f.dV11 = at(s->dV[0]), f.dV12 = at(s->dV[1]), f.dV13 = at(s->dV[2]);
+    f.dV22 = at(s->dV[3]), f.dV23 = at(s->dV[4]), f.dV33 = at(s->dV[5]);
+    return f;
+}
 
 // ---- sx_sim.cpp ---------------------------------------------------------------------------------------------------
 

@@ -12,8 +12,9 @@
  * are what distributedGravity classifies near and far cells against, and with h a softening length the halos are few.
  * The halo masses are not overwritten with m[first] (nbody.hpp:127-129): gravity halos carry their own mass.
  *
- * Stage times keep the VE step's names and order (consumers index by position): "sync", "Gravity" and
- * "UpdateQuantities" are timed, the hydro stages read 0.
+ * Times (sx_step_timer.hpp): the step marks the stages sync, Gravity and UpdateQuantities and the kernels gravity and
+ * nbodyIntegrate.  The names and their order are the VE step's (consumers index by position); the hydro stages and
+ * kernels are not marked and read 0.
  */
 #include "sx_sim_internal.hpp"
 
@@ -27,17 +28,12 @@ int stepNbody(sx_sim* s)
 {
     hipStream_t st   = (hipStream_t)sx_ctx_stream_internal(s->ctx);
     const bool  dist = s->comm && s->comm->size() > 1;
-    // stage events: [0] start, [1] after the sync, [2 .. 8] the hydro stages (empty), [9] after gravity, [10] the end
-    const size_t nStages = s->stageNames.size();
-    SIM_HIP(hipEventRecord(s->ev[0], st));
-    // kernel events: every hot kernel of the VE step but gravity is an empty interval
-    for (size_t k = 0; k < 12; ++k)
-        SIM_HIP(hipEventRecord(s->kev[k], st));
+    StepTimer&  T    = s->timer;
+    SIM_HIP(T.start(st));
 
     // ---- sync: keys, sort, tree (nbody.hpp:118)
     if (int e = dist ? distributedSync(s, st, kHaloMargin) : localSync(s, st)) return e;
-    for (size_t k = 1; k + 1 < nStages; ++k)
-        SIM_HIP(hipEventRecord(s->ev[k], st));
+    SIM_HIP(T.stageEnd(Stage::sync, st));
 
     // ---- computeForces: a = 0 for the locals, then upsweep and walk add G acc (nbody.hpp:131-138)
     resetStepScalars(s, st);
@@ -48,37 +44,27 @@ int stepNbody(sx_sim* s)
         SIM_HIP(hipMemsetAsync(s->ay + s->first, 0, nl * sizeof(float), st));
         SIM_HIP(hipMemsetAsync(s->az + s->first, 0, nl * sizeof(float), st));
     }
-    SIM_HIP(hipEventRecord(s->kev[12], st));
+    SIM_HIP(T.begin(Kernel::gravity, st));
     if (int e = gravityStage(s, st, dist, false)) return e;
-    SIM_HIP(hipEventRecord(s->kev[13], st));
-    SIM_HIP(hipEventRecord(s->ev[nStages - 1], st));
+    SIM_HIP(T.end(Kernel::gravity, st));
+    SIM_HIP(T.stageEnd(Stage::Gravity, st));
 
     // ---- integrate: minDtCourant = INFINITY, computeTimestep, computePositions (nbody.hpp:152-163)
     if (int e = globalTimestep(s, dist, st)) return e;
-    NbodyPosArgs qa{};
-    qa.first = (uint32_t)s->first, qa.last = (uint32_t)s->last;
-    qa.dtPtr = &s->sc->minDt;
-    qa.box   = s->dbox;
-    qa.x = s->x, qa.y = s->y, qa.z = s->z;
-    qa.x_m1 = s->xm1, qa.y_m1 = s->ym1, qa.z_m1 = s->zm1;
-    qa.vx = s->vx, qa.vy = s->vy, qa.vz = s->vz;
-    qa.ax = s->ax, qa.ay = s->ay, qa.az = s->az;
-    qa.h  = s->h;
+    NbodyPosArgs qa = nbodyPosArgs((uint32_t)s->first, (uint32_t)s->last, simFields(s), s->dbox);
+    qa.dtPtr        = &s->sc->minDt;
     // one rank: the next localSync's keys come from this pass (the coordinates are in registers here)
     qa.keys = dist ? nullptr : s->keys;
-    SIM_HIP(hipEventRecord(s->kev[14], st));
+    SIM_HIP(T.begin(Kernel::nbodyIntegrate, st));
     SIM_HIP(nbodyIntegrate(qa, st));
-    SIM_HIP(hipEventRecord(s->kev[15], st));
+    SIM_HIP(T.end(Kernel::nbodyIntegrate, st));
     s->keysFresh = qa.keys != nullptr;
-    SIM_HIP(hipEventRecord(s->ev[nStages], st));
+    SIM_HIP(T.stageEnd(Stage::UpdateQuantities, st));
 
     // ---- the end of the step: wait for it, stage and kernel times, the walk's error flag
     SIM_HIP(hipGetLastError());
     SIM_HIP(hipStreamSynchronize(st));
-    for (size_t k = 0; k < s->stageMs.size(); ++k)
-        (void)hipEventElapsedTime(&s->stageMs[k], s->ev[k], s->ev[k + 1]);
-    for (size_t k = 0; k < s->kernelMs.size(); ++k)
-        (void)hipEventElapsedTime(&s->kernelMs[k], s->kev[2 * k], s->kev[2 * k + 1]);
+    T.collect();
     SIM_HIP(hipMemcpy(s->scHost, s->sc, sizeof(Scalars), hipMemcpyDeviceToHost));
     if (s->scHost->gravErr)
     {
