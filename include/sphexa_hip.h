@@ -464,6 +464,82 @@ int sx_map_stats(sx_ctx* ctx, uint64_t out[4]);
 int sx_set_map_timing(sx_ctx* ctx, int on);
 int sx_map_times(sx_ctx* ctx, double out[4]);
 
+/* ---- power spectra: mesh deposit, 3-D FFT, shell sums (sph-exa_amd/csrc/sx_spectrum.hpp) ----------------------
+ * The reference carries an SPH_EXA_WITH_FFTW switch (CMakeLists.txt:84-89) that nothing in it uses; like the maps this
+ * is a counterpart of our own design: the state reduced on the device, here to a few hundred numbers.
+ * Box and mesh.  The box must be periodic on all three axes and cubic, with edge L.  The mesh has n^3 cells,
+ *   n in {16, 32, 64, 128, 256}.  Cell size is D = L / n.  Cell (ix, iy, iz) has its centre at lim_lo + (i + 1/2) D per
+ *   axis.  Cells are stored [iz][iy][ix], x fastest.
+ * Deposit.  S0(c) = sum_j m_j K W(r_jc / he_j) / he_j^3, with W = sinc^6 (the pair kernels' kernelWt).  r is the
+ *   minimum-image distance to the cell centre.  he_j = max(h_j, D / 2): with this clamp every particle reaches at least
+ *   one centre, as the column maps clamp theirs.  Up to three further sums S1_a(c) = sum_j w_jc a_j use the same
+ *   weights, for three device columns a (float or double).  Neither rho nor a volume element is read, so the VE, std and
+ *   gravity-only layouts are served alike.  Each cell sums in float, FMA, in ascending particle index, and stores a
+ *   double.  A cell is exactly 0 where no support contains its centre.  There are no float atomics.  The result is
+ *   bit-identical from run to run and for every pair cap.
+ * Field that is transformed.  SX_SPEC_VELOCITY: W_a = S0^p S1_a / S0 for a = vx, vy, vz.  weight 0 means p = 0, the
+ *   mass-weighted mean velocity; weight 1 means p = 1/2, the kinetic-energy spectrum; weight 2 means p = 1/3.  The
+ *   prefactor is 1/2.  SX_SPEC_SCALAR: one column, or the mesh density S0 itself when no column is given.  weight must
+ *   be 0.  The prefactor is 1.  W = 0 where S0 = 0.  W is computed in double from the stored sums.
+ * Transform and shells.  What(n) = n^-3 sum_c W(c) exp(-2 pi i n.c / n), a complex-to-complex FFT in double.  Integer
+ *   wave vectors are n_i in [-n/2, n/2).  Shell index: s = floor(|n| + 1/2).  Shell count: numShells =
+ *   floor(sqrt(3) n / 2 + 1/2) + 1.  power[s] = prefactor sum_a sum_{n in s} |What_a(n)|^2.  modes[s] = the number of
+ *   wave vectors in shell s, a u64.  It follows that sum_s power[s] = prefactor <sum_a W_a^2> over the cells (Parseval).
+ *   The physical wave number of shell s is 2 pi s / L.  The shell sums have a fixed order: the same bits every run. */
+#define SX_SPEC_VELOCITY 0
+#define SX_SPEC_SCALAR 1
+typedef struct sx_spectrum
+{
+    int32_t  kind, weight; /* weight: the p of SX_SPEC_VELOCITY (0: 0, 1: 1/2, 2: 1/3) */
+    uint32_t n;            /* cells per axis */
+} sx_spectrum;
+/*! host only, needs no GPU: SX_OK, or SX_ERR_ARG with the reason in sx_last_error(NULL) (per thread).  Refused, each
+ *  with its own message: a NULL argument, an unknown kind, an unknown weight, a non-zero weight with SX_SPEC_SCALAR, an n
+ *  that is not one of the five sizes, a box with an open or fixed axis, a non-cubic box. */
+int sx_spectrum_check(const sx_spectrum* spec, const sx_box* box);
+/*! host only: floor(sqrt(3) n / 2 + 1/2) + 1, or 0 for an n that is not one of the five sizes */
+uint32_t sx_spectrum_num_shells(uint32_t n);
+/*! host only: the wave vectors per shell into modes[sx_spectrum_num_shells(n)]; SX_ERR_ARG for another n */
+int sx_spectrum_modes(uint32_t n, uint64_t* modes);
+/*! pairs (block, particle) the deposit produces and sorts at a time: it works through the mesh in bands of whole layers
+ *  of 8 x 8 x 4-cell blocks along z whose pairs stay within this cap; 0 = the default (2^27).  The mesh is bit-identical
+ *  for every cap.  A deposit in which one layer alone exceeds the cap (or 2^31 - 1 pairs) returns SX_ERR_ARG. */
+int sx_set_spectrum_pair_cap(sx_ctx* ctx, uint64_t pairs);
+/*! records the gather kernel stages through LDS at a time (tests place a block's list length around its multiples) */
+uint32_t sx_spectrum_chunk_records(void);
+/*! the deposit over the particles [first, last) of f onto the n^3 mesh: sum0 (n^3 doubles) and sum1 (numA meshes of n^3
+ *  doubles, one behind the other), device arrays, overwritten.  Reads x y z h m of f and K; a[0 .. numA): device columns
+ *  of length f->n, all float or all double (aIsDouble); numA in 0 .. 3 (0: a and sum1 may be NULL).  The box is checked
+ *  as by sx_spectrum_check.  Runs on the context stream and synchronises it once, after counting the pairs. */
+int sx_mesh_deposit(sx_ctx* ctx, const sx_fields* f, const sx_box* box, uint32_t first, uint32_t last, double K,
+                    uint32_t n, const void* const a[3], int numA, int aIsDouble, double* sum0, double* sum1);
+/*! in place, forward, scaled by n^-3: complexMesh holds n^3 interleaved complex doubles (device, 16-byte aligned).  A
+ *  kernel of our own (Stockham, radix 4 and 2, in LDS; the twiddle table is built once per n on the host in double and
+ *  kept in the context); the library links no FFT package. */
+int sx_fft3d(sx_ctx* ctx, double* complexMesh, uint32_t n);
+/*! power[s] = (accumulate ? power[s] : 0) + prefactor sum_{n in s} |complexMesh(n)|^2 over the transformed mesh, and
+ *  modes[s] (nullable); device arrays of sx_spectrum_num_shells(n) entries.  Fixed order of the sums: a mode permutation
+ *  grouped by shell (built once per n, kept in the context), leaves of 2048 modes reduced by a fixed tree, the leaves of
+ *  a shell added in ascending order. */
+int sx_shell_sums(sx_ctx* ctx, const double* complexMesh, uint32_t n, double prefactor, int accumulate, double* power,
+                  uint64_t* modes);
+/*! all stages: deposit, field, transform, shell sums; power and modes (nullable) are device arrays of
+ *  sx_spectrum_num_shells(spec->n) entries.  SX_SPEC_VELOCITY: a[0 .. 3) are the velocity columns, a NULL: f->vx, vy, vz
+ *  (float).  SX_SPEC_SCALAR: a[0] is the column, a or a[0] NULL: the mesh density.  The velocity kinds transform
+ *  W_x + i W_y as one complex field and W_z as another: every shell is symmetric under n -> -n, so the shell sums of
+ *  |FFT(W_x + i W_y)|^2 equal those of |What_x|^2 + |What_y|^2.  The meshes live in the context from the first call on:
+ *  (2 + 4 n^3) doubles of sums, one complex mesh of 2 n^3 doubles, the permutation of n^3 u32 -- 805 MB + 67 MB at
+ *  n = 256 -- and the deposit's pair scratch (24 B per pair).  Synchronises. */
+int sx_spectrum_compute(sx_ctx* ctx, const sx_fields* f, const sx_box* box, uint32_t first, uint32_t last, double K,
+                        const sx_spectrum* spec, const void* const a[3], int aIsDouble, double* power, uint64_t* modes);
+/*! the context's last deposit: {pairs, bands, longest block list, particles clamped to D / 2}; synchronises.
+ *  SX_ERR_ARG before the first deposit. */
+int sx_spectrum_stats(sx_ctx* ctx, uint64_t out[4]);
+/*! measurement: with on != 0 the following calls time their stages with HIP events (and synchronise after each);
+ *  sx_spectrum_times: {binning, sort, gather, fft, shells} in ms, summed since the last deposit began */
+int sx_set_spectrum_timing(sx_ctx* ctx, int on);
+int sx_spectrum_times(sx_ctx* ctx, double out[5]);
+
 /* ---- self-gravity: ryoanji MultipoleHolder seam (multipole_holder.cuh:40-66, gravity_wrapper.hpp:104-174) ----- */
 /*! expansion centers (mass centers, {x,y,z,mac^2}, numNodes x 4 doubles; mac = 2 max(node size)/theta + |com-geo|,
  *  setMac, source_center.hpp:130-143) and Cartesian quadrupoles (numNodes x 8 floats, Cqi order,
@@ -718,6 +794,20 @@ int    sx_sim_set_iteration(sx_sim* sim, uint64_t iteration);
 int    sx_sim_render(sx_sim* sim, const sx_map* map, int field, double* hostSum0, double* hostSum1);
 int    sx_sim_map_stats(sx_sim* sim, uint64_t out[4]);
 int    sx_sim_set_map_pair_cap(sx_sim* sim, uint64_t pairs);
+/*! sx_spectrum_compute of the current state over all ranks: each rank deposits its locals, one f64-sum reduction
+ *  (sx_comm_allreduce op 2) runs over the meshes when a communicator is set -- one leading double counts the ranks whose
+ *  own deposit was refused, so nobody waits in the reduction for a rank that left early: that rank returns its code,
+ *  every other rank SX_ERR_ARG --, every rank then transforms and sums redundantly, and power (numShells doubles) and
+ *  modes (numShells u64, nullable) reach the host arrays through a pinned buffer; synchronises.  SX_SPEC_VELOCITY reads
+ *  vx, vy, vz (field is ignored); SX_SPEC_SCALAR takes field, a code of sx_sim_render (SX_MAP_FIELD_NONE: the mesh
+ *  density itself); a field the layout does not keep is refused as sx_sim_render refuses it.  Every propagator; under
+ *  ve-bdt between any two substeps.  Nothing in sx_sim_step calls it and it changes no state.  The buffers live in the
+ *  sim's arena, are allocated by the first call and counted by sx_sim_memory from then on (what a 256^3 call keeps:
+ *  see sx_spectrum_compute).  sx_sim_spectrum_stats: sx_spectrum_stats of the sim's last call (this rank's figures);
+ *  sx_sim_set_spectrum_pair_cap: sx_set_spectrum_pair_cap. */
+int    sx_sim_spectrum(sx_sim* sim, const sx_spectrum* spec, int field, double* hostPower, uint64_t* hostModes);
+int    sx_sim_spectrum_stats(sx_sim* sim, uint64_t out[4]);
+int    sx_sim_set_spectrum_pair_cap(sx_sim* sim, uint64_t pairs);
 /*! device time (ms) of each hot kernel alone in the last step (HIP events on the launch stream, bracketing just the
  *  launch): findNeighbors, xmass, veDefGradh, iadDivvCurlv, avSwitches, momentumEnergy */
 int    sx_sim_kernel_times(sx_sim* sim, float* ms, int cap, const char** names);

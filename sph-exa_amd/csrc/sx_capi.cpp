@@ -21,6 +21,7 @@
 #include "sx_map.hpp"
 #include "sx_nbody.hpp"
 #include "sx_observables.hpp"
+#include "sx_spectrum.hpp"
 #include "sx_tree.hpp"
 #include "sx_timestep.hpp"
 #include "sx_turb.hpp"
@@ -125,6 +126,7 @@ struct sx_ctx
     uint32_t    directTargetsPerLane{sx::direct::kDefaultTargetsPerLane}; // fast direct sum (A/B: DESIGN.md 7f)
     Arena       arena;
     sx::map::MapBuffers mapBuf;          // pair scratch and figures of sx_map_render
+    sx::spectrum::SpecBuffers specBuf;   // scratch, per-n tables, meshes and figures of the spectra
     float2*     wh{nullptr};
     float2*     whd{nullptr};
     double      K{0};
@@ -267,6 +269,7 @@ extern "C"
         if (!c) return;
         (void)hipDeviceSynchronize();
         sx::map::release(c->mapBuf);
+        sx::spectrum::release(c->specBuf);
         c->arena.release();
         if (c->own) (void)hipStreamDestroy(c->own);
         delete c;
@@ -1445,6 +1448,116 @@ extern "C"
         const int rc = sx::map::stats(c->mapBuf, c->stream, out);
         if (rc == sx::map::kStatsMismatch) return fail(c, SX_ERR_HIP, std::string("sx_map_stats: ") + sx::map::kStatsMismatchText);
         return rc == SX_OK ? SX_OK : fail(c, rc, rc == SX_ERR_ARG ? "sx_map_stats: nothing has been rendered" : "sx_map_stats: copy failed");
+    }
+
+    // ---- power spectra ------------------------------------------------------------------------------------------
+
+    int sx_spectrum_check(const sx_spectrum* sp, const sx_box* box)
+    {
+        if (const char* why = sx::spectrum::checkSpec(sp, box)) return fail(nullptr, SX_ERR_ARG, why);
+        return SX_OK;
+    }
+
+    uint32_t sx_spectrum_num_shells(uint32_t n) { return sx::spectrum::numShells(n); }
+
+    int sx_spectrum_modes(uint32_t n, uint64_t* modes)
+    {
+        if (!modes || !sx::spectrum::validN(n)) return fail(nullptr, SX_ERR_ARG, "sx_spectrum_modes: modes and n of 16, 32, 64, 128 or 256");
+        sx::spectrum::shellModes(n, modes);
+        return SX_OK;
+    }
+
+    uint32_t sx_spectrum_chunk_records(void) { return sx::spectrum::kChunk; }
+
+    int sx_set_spectrum_pair_cap(sx_ctx* c, uint64_t pairs)
+    {
+        if (!c) return SX_ERR_ARG;
+        c->specBuf.pairCap = pairs;
+        return SX_OK;
+    }
+
+    int sx_set_spectrum_timing(sx_ctx* c, int on)
+    {
+        if (!c) return SX_ERR_ARG;
+        c->specBuf.timing = on != 0;
+        return SX_OK;
+    }
+
+    int sx_spectrum_times(sx_ctx* c, double out[5])
+    {
+        if (!c || !out) return SX_ERR_ARG;
+        for (int k = 0; k < 5; ++k)
+            out[k] = c->specBuf.ms[k];
+        return SX_OK;
+    }
+
+    int sx_mesh_deposit(sx_ctx* c, const sx_fields* f, const sx_box* box, uint32_t first, uint32_t last, double K,
+                        uint32_t n, const void* const a[3], int numA, int aIsDouble, double* sum0, double* sum1)
+    {
+        if (!c) return SX_ERR_ARG;
+        if (!f || !box || !sum0) return fail(c, SX_ERR_ARG, "sx_mesh_deposit: null fields, box or sum0");
+        if (!f->x || !f->y || !f->z || !f->h || !f->m) return fail(c, SX_ERR_ARG, "sx_mesh_deposit: x, y, z, h and m are required");
+        if (first > last || last > f->n) return fail(c, SX_ERR_ARG, "sx_mesh_deposit: [first, last) is not a range of f");
+        if (numA < 0 || numA > 3) return fail(c, SX_ERR_ARG, "sx_mesh_deposit: numA must be 0 .. 3");
+        if (numA && (!a || !sum1)) return fail(c, SX_ERR_ARG, "sx_mesh_deposit: columns need a and sum1");
+        for (int k = 0; k < numA; ++k)
+            if (!a[k]) return fail(c, SX_ERR_ARG, "sx_mesh_deposit: a null column among the first numA");
+        sx::spectrum::DepositArgs args{*box, f->x, f->y, f->z, f->h, f->m, {nullptr, nullptr, nullptr}, numA, aIsDouble,
+                                       first, last, K, n, sum0, sum1};
+        for (int k = 0; k < numA; ++k)
+            args.a[k] = a[k];
+        std::string err;
+        const int   rc = sx::spectrum::deposit(c->arena, c->specBuf, args, c->stream, err);
+        return rc == SX_OK ? SX_OK : fail(c, rc, err);
+    }
+
+    int sx_fft3d(sx_ctx* c, double* complexMesh, uint32_t n)
+    {
+        if (!c) return SX_ERR_ARG;
+        std::string err;
+        const int   rc = sx::spectrum::fft3d(c->arena, c->specBuf, complexMesh, n, c->stream, err);
+        return rc == SX_OK ? SX_OK : fail(c, rc, err);
+    }
+
+    int sx_shell_sums(sx_ctx* c, const double* complexMesh, uint32_t n, double prefactor, int accumulate, double* power,
+                      uint64_t* modes)
+    {
+        if (!c) return SX_ERR_ARG;
+        std::string err;
+        const int   rc = sx::spectrum::shellSums(c->arena, c->specBuf, complexMesh, n, prefactor, accumulate, power, modes,
+                                                 c->stream, err);
+        return rc == SX_OK ? SX_OK : fail(c, rc, err);
+    }
+
+    int sx_spectrum_compute(sx_ctx* c, const sx_fields* f, const sx_box* box, uint32_t first, uint32_t last, double K,
+                            const sx_spectrum* sp, const void* const a[3], int aIsDouble, double* power, uint64_t* modes)
+    {
+        if (!c) return SX_ERR_ARG;
+        if (!f || !box || !sp || !power) return fail(c, SX_ERR_ARG, "sx_spectrum_compute: null fields, box, spectrum or power");
+        if (!f->x || !f->y || !f->z || !f->h || !f->m) return fail(c, SX_ERR_ARG, "sx_spectrum_compute: x, y, z, h and m are required");
+        if (first > last || last > f->n) return fail(c, SX_ERR_ARG, "sx_spectrum_compute: [first, last) is not a range of f");
+        sx::spectrum::DepositArgs args{*box, f->x, f->y, f->z, f->h, f->m, {nullptr, nullptr, nullptr}, 0, aIsDouble,
+                                       first, last, K, sp->n, nullptr, nullptr};
+        if (sp->kind == SX_SPEC_VELOCITY)
+        {
+            args.numA = 3;
+            if (a) args.a[0] = a[0], args.a[1] = a[1], args.a[2] = a[2];
+            else args.a[0] = f->vx, args.a[1] = f->vy, args.a[2] = f->vz, args.aIsDouble = 0;
+            if (!args.a[0] || !args.a[1] || !args.a[2]) return fail(c, SX_ERR_ARG, "sx_spectrum_compute: three velocity columns are required");
+        }
+        else if (a && a[0]) args.numA = 1, args.a[0] = a[0];
+        std::string err;
+        const int   rc = sx::spectrum::compute(c->arena, c->specBuf, *sp, args, power, modes, nullptr, c->stream, err);
+        return rc == SX_OK ? SX_OK : fail(c, rc, err);
+    }
+
+    int sx_spectrum_stats(sx_ctx* c, uint64_t out[4])
+    {
+        if (!c || !out) return SX_ERR_ARG;
+        const int rc = sx::spectrum::stats(c->specBuf, c->stream, out);
+        if (rc == sx::spectrum::kStatsMismatch)
+            return fail(c, SX_ERR_HIP, std::string("sx_spectrum_stats: ") + sx::spectrum::kStatsMismatchText);
+        return rc == SX_OK ? SX_OK : fail(c, rc, rc == SX_ERR_ARG ? "sx_spectrum_stats: nothing has been deposited" : "sx_spectrum_stats: copy failed");
     }
 
     int sx_set_direct_splits(sx_ctx* c, uint32_t splits)

@@ -1027,6 +1027,7 @@ extern "C"
         if (s->auxStream) (void)hipStreamDestroy(s->auxStream);
         turbDestroy(s->turb);
         sx::map::release(s->mapBuf);
+        sx::spectrum::release(s->specBuf);
         delete s;
     }
 

@@ -216,6 +216,48 @@ def map_chunk_records():
     return int(lib().sx_map_chunk_records())
 
 
+class SxSpectrum(C.Structure):
+    """sx_spectrum: kind ("velocity" or "scalar"), weight (the p of W = S0^p S1 / S0: 0, 1 for 1/2, 2 for 1/3; "mean",
+    "energy", "third") and the cells per axis n"""
+    _fields_ = [("kind", C.c_int32), ("weight", C.c_int32), ("n", C.c_uint32)]
+
+    def __init__(self, kind="velocity", weight=0, n=128):
+        super().__init__(SPEC_KINDS.get(kind, kind), SPEC_WEIGHTS.get(weight, weight), int(n))
+
+    @property
+    def prefactor(self):
+        return 0.5 if self.kind == 0 else 1.0
+
+
+SPEC_KINDS = {"velocity": 0, "scalar": 1}
+SPEC_WEIGHTS = {None: 0, "mean": 0, "energy": 1, "third": 2}
+SPEC_SIZES = (16, 32, 64, 128, 256)
+
+
+def spectrum_check(spec, box):
+    """sx_spectrum_check: raises SxError with the reason for a specification a call would refuse.  Needs no GPU."""
+    if lib().sx_spectrum_check(C.byref(spec), C.byref(box)) != SX_OK:
+        raise SxError(lib().sx_last_error(None).decode())
+
+
+def spectrum_num_shells(n):
+    """floor(sqrt(3) n / 2 + 1/2) + 1 (sx_spectrum_num_shells; 0 for an n that is not a mesh size).  Needs no GPU."""
+    return int(lib().sx_spectrum_num_shells(int(n)))
+
+
+def spectrum_modes(n):
+    """wave vectors per shell (sx_spectrum_modes), uint64.  Needs no GPU."""
+    out = np.zeros(max(1, spectrum_num_shells(n)), np.uint64)
+    if lib().sx_spectrum_modes(int(n), out.ctypes.data) != SX_OK:
+        raise SxError(lib().sx_last_error(None).decode())
+    return out
+
+
+def spectrum_chunk_records():
+    """records per LDS chunk of the mesh gather (sx_spectrum_chunk_records)"""
+    return int(lib().sx_spectrum_chunk_records())
+
+
 class SxOctree(C.Structure):
     _fields_ = [("prefixes", _P), ("childOffsets", _P), ("parents", _P), ("levelRange", _P),
                 ("internalToLeaf", _P), ("leafToInternal", _P)]
@@ -423,6 +465,23 @@ def lib():
         "sx_sim_render": (C.c_int, [vp, C.POINTER(SxMap), C.c_int, vp, vp]),
         "sx_sim_map_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         "sx_sim_set_map_pair_cap": (C.c_int, [vp, C.c_uint64]),
+        "sx_spectrum_check": (C.c_int, [C.POINTER(SxSpectrum), C.POINTER(SxBox)]),
+        "sx_spectrum_num_shells": (u32, [u32]),
+        "sx_spectrum_modes": (C.c_int, [u32, vp]),
+        "sx_spectrum_chunk_records": (u32, []),
+        "sx_set_spectrum_pair_cap": (C.c_int, [vp, C.c_uint64]),
+        "sx_mesh_deposit": (C.c_int, [vp, C.POINTER(SxFields), C.POINTER(SxBox), u32, u32, C.c_double, u32,
+                                      C.POINTER(vp), C.c_int, C.c_int, vp, vp]),
+        "sx_fft3d": (C.c_int, [vp, vp, u32]),
+        "sx_shell_sums": (C.c_int, [vp, vp, u32, C.c_double, C.c_int, vp, vp]),
+        "sx_spectrum_compute": (C.c_int, [vp, C.POINTER(SxFields), C.POINTER(SxBox), u32, u32, C.c_double,
+                                          C.POINTER(SxSpectrum), C.POINTER(vp), C.c_int, vp, vp]),
+        "sx_spectrum_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        "sx_set_spectrum_timing": (C.c_int, [vp, C.c_int]),
+        "sx_spectrum_times": (C.c_int, [vp, C.POINTER(C.c_double)]),
+        "sx_sim_spectrum": (C.c_int, [vp, C.POINTER(SxSpectrum), C.c_int, vp, vp]),
+        "sx_sim_spectrum_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        "sx_sim_set_spectrum_pair_cap": (C.c_int, [vp, C.c_uint64]),
     }
     for name, (res, args) in sig.items():
         # a measurement build named by SPHEXA_AMD_LIB (an A/B against an older library) may predate an entry
@@ -747,6 +806,108 @@ class Context:
         out = (C.c_double * 4)()
         self.check(self.L.sx_map_times(self.h, out), "sx_map_times")
         return {"binning_ms": out[0], "sort_ms": out[1], "render_ms": out[2], "scratch_bytes": int(out[3])}
+
+    # ---- power spectra ----------------------------------------------------------------------------------------
+    def set_spectrum_pair_cap(self, pairs=0):
+        """(block, particle) pairs mesh_deposit produces and sorts at a time (sx_set_spectrum_pair_cap); 0: the default"""
+        self.check(self.L.sx_set_spectrum_pair_cap(self.h, int(pairs)), "sx_set_spectrum_pair_cap")
+
+    @staticmethod
+    def _columns(a):
+        """(pointer array, count, is double) of up to three DeviceArrays of one dtype"""
+        a = [] if a is None else list(a)
+        if len(a) > 3:
+            raise ValueError("at most three columns")
+        kinds = {c.dtype for c in a}
+        if len(kinds) > 1 or (kinds and kinds.pop() not in (np.dtype(np.float32), np.dtype(np.float64))):
+            raise TypeError("columns must be all float32 or all float64")
+        ptrs = (C.c_void_p * 3)(*([c.ptr for c in a] + [None] * (3 - len(a))))
+        return ptrs, len(a), int(bool(a) and a[0].dtype == np.dtype(np.float64))
+
+    def mesh_deposit(self, fields, box, n, a=None, first=0, last=None, K=None):
+        """the particles [first, last) of an SxFields deposited onto the n^3 mesh (sx_mesh_deposit): (S0, S1), arrays of
+        shape (n, n, n) [iz][iy][ix] and (len(a), n, n, n); a: up to three DeviceArrays of one dtype"""
+        ptrs, num, dbl = self._columns(a)
+        n3 = int(n) ** 3
+        last = fields.n if last is None else last
+        d0 = self.alloc(n3, np.float64)
+        d1 = self.alloc(max(1, num) * n3, np.float64)
+        try:
+            self.check(self.L.sx_mesh_deposit(self.h, C.byref(fields), C.byref(box), int(first), int(last),
+                                              float(self.L.sx_kernel_constant() if K is None else K), int(n), ptrs, num,
+                                              dbl, d0.ptr, d1.ptr), "sx_mesh_deposit")
+            return d0.get().reshape(n, n, n), d1.get()[: num * n3].reshape(num, n, n, n)
+        finally:
+            self.free(d0)
+            self.free(d1)
+
+    def fft3d(self, mesh):
+        """the forward transform of a complex (n, n, n) array scaled by n^-3 (sx_fft3d), or of a DeviceArray of 2 n^3
+        doubles in place (then n is taken from its size and nothing is returned)"""
+        if isinstance(mesh, DeviceArray):
+            n = round((mesh.n // 2) ** (1.0 / 3.0))
+            self.check(self.L.sx_fft3d(self.h, mesh.ptr, n), "sx_fft3d")
+            return None
+        mesh = np.ascontiguousarray(mesh, dtype=np.complex128)
+        n = mesh.shape[0]
+        d = self.upload(mesh.view(np.float64).ravel())
+        try:
+            self.check(self.L.sx_fft3d(self.h, d.ptr, n), "sx_fft3d")
+            return d.get().view(np.complex128).reshape(mesh.shape)
+        finally:
+            self.free(d)
+
+    def shell_sums(self, mesh, prefactor=1.0, power=None):
+        """(power, modes) of a transformed complex (n, n, n) array or DeviceArray of 2 n^3 doubles (sx_shell_sums);
+        power: an array of earlier sums to add to (accumulate = 1)"""
+        if isinstance(mesh, DeviceArray):
+            d, n, own = mesh, round((mesh.n // 2) ** (1.0 / 3.0)), False
+        else:
+            mesh = np.ascontiguousarray(mesh, dtype=np.complex128)
+            d, n, own = self.upload(mesh.view(np.float64).ravel()), mesh.shape[0], True
+        ns = spectrum_num_shells(n)
+        dp = self.upload(np.asarray(power, np.float64)) if power is not None else self.alloc(max(1, ns), np.float64)
+        dm = self.alloc(max(1, ns), np.uint64)
+        try:
+            self.check(self.L.sx_shell_sums(self.h, d.ptr, n, float(prefactor), int(power is not None), dp.ptr, dm.ptr),
+                       "sx_shell_sums")
+            return dp.get()[:ns], dm.get()[:ns]
+        finally:
+            self.free(dp)
+            self.free(dm)
+            if own:
+                self.free(d)
+
+    def spectrum(self, fields, box, spec, a=None, first=0, last=None, K=None):
+        """(power, modes) of the particles [first, last) of an SxFields (sx_spectrum_compute); a: the three velocity
+        columns (None: fields.vx, vy, vz) or [the scalar column] (None: the mesh density), DeviceArrays of one dtype"""
+        ptrs, num, dbl = self._columns(a)
+        ns = max(1, spectrum_num_shells(spec.n))
+        last = fields.n if last is None else last
+        dp, dm = self.alloc(ns, np.float64), self.alloc(ns, np.uint64)
+        try:
+            self.check(self.L.sx_spectrum_compute(self.h, C.byref(fields), C.byref(box), int(first), int(last),
+                                                  float(self.L.sx_kernel_constant() if K is None else K), C.byref(spec),
+                                                  ptrs if num else None, dbl, dp.ptr, dm.ptr), "sx_spectrum_compute")
+            return dp.get(), dm.get()
+        finally:
+            self.free(dp)
+            self.free(dm)
+
+    def spectrum_stats(self):
+        """the last deposit: {pairs, bands, longest (block list), clamped (particles with h below half a cell)}"""
+        out = (C.c_uint64 * 4)()
+        self.check(self.L.sx_spectrum_stats(self.h, out), "sx_spectrum_stats")
+        return dict(zip(["pairs", "bands", "longest", "clamped"], [int(v) for v in out]))
+
+    def set_spectrum_timing(self, on=True):
+        self.check(self.L.sx_set_spectrum_timing(self.h, 1 if on else 0), "sx_set_spectrum_timing")
+
+    def spectrum_times(self):
+        """{binning, sort, gather, fft, shells} in ms since the last deposit began (after set_spectrum_timing)"""
+        out = (C.c_double * 5)()
+        self.check(self.L.sx_spectrum_times(self.h, out), "sx_spectrum_times")
+        return dict(zip(["binning_ms", "sort_ms", "gather_ms", "fft_ms", "shells_ms"], list(out)))
 
     def observables(self, fields, kind, first=0, last=None, box=None, settings=None, mui=10.0, gamma=5.0 / 3.0,
                     cap=None):
@@ -1274,6 +1435,33 @@ class Sim:
 
     def set_map_pair_cap(self, pairs=0):
         self.ctx.check(self.L.sx_sim_set_map_pair_cap(self.h, int(pairs)), "sx_sim_set_map_pair_cap")
+
+    def spectrum(self, n=128, kind="velocity", weight=None, field=None):
+        """the power spectrum of the current state over all ranks (sx_sim_spectrum): (k, power, modes) per shell s with
+        k = 2 pi s / L.  kind "velocity": weight None / "mean" (p = 0), "energy" (p = 1/2: the kinetic-energy spectrum)
+        or "third" (p = 1/3).  kind "scalar": the mass-weighted mean of `field` (one of MAP_FIELDS) on the mesh, or
+        the mesh density without one."""
+        if field not in MAP_FIELDS:
+            raise ValueError(f"unknown spectrum field {field!r}: one of {sorted(k for k in MAP_FIELDS if k)}")
+        if kind not in SPEC_KINDS or weight not in SPEC_WEIGHTS:
+            raise ValueError(f"spectrum: kind one of {sorted(SPEC_KINDS)}, weight one of "
+                             f"{sorted(k for k in SPEC_WEIGHTS if k)} or None")
+        spec = SxSpectrum(kind, weight, n)
+        ns = max(1, spectrum_num_shells(n))
+        power, modes = np.zeros(ns), np.zeros(ns, np.uint64)
+        self.ctx.check(self.L.sx_sim_spectrum(self.h, C.byref(spec), MAP_FIELDS[field], power.ctypes.data,
+                                              modes.ctypes.data), "sx_sim_spectrum")
+        L = self.box.lim[1] - self.box.lim[0]
+        return 2.0 * np.pi * np.arange(ns) / L, power, modes
+
+    def spectrum_stats(self):
+        """this rank's figures of the last spectrum(): {pairs, bands, longest, clamped}"""
+        out = (C.c_uint64 * 4)()
+        self.ctx.check(self.L.sx_sim_spectrum_stats(self.h, out), "sx_sim_spectrum_stats")
+        return dict(zip(["pairs", "bands", "longest", "clamped"], [int(v) for v in out]))
+
+    def set_spectrum_pair_cap(self, pairs=0):
+        self.ctx.check(self.L.sx_sim_set_spectrum_pair_cap(self.h, int(pairs)), "sx_sim_set_spectrum_pair_cap")
 
     def write_constants(self, fileobj):
         """append the row of observe() to a constants.txt (format_constants_row); returns the row"""
