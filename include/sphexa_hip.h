@@ -540,6 +540,141 @@ int sx_spectrum_stats(sx_ctx* ctx, uint64_t out[4]);
 int sx_set_spectrum_timing(sx_ctx* ctx, int on);
 int sx_spectrum_times(sx_ctx* ctx, double out[5]);
 
+/* ---- binned profiles and analytic L1 with exact sums (sph-exa_amd/csrc/sx_profile.hpp) -------------------------
+ * The device-side counterpart of main/src/analytical_solutions/compare_solutions.py:85-89 (computeL1Error) and
+ * compare_noh.py:141-148, which run on HDF5 dumps: a binned reduction over the particles that returns a few numbers per
+ * bin.  The bin coordinate is a radius, an axis coordinate or a quantity (the last gives PDFs).
+ * Arithmetic rule.  All per-particle arithmetic below is IEEE double unless it says float; every operation is rounded
+ *   on its own (no FMA contraction); sqrt and / are correctly rounded.  (a op b) op c is written with its brackets.
+ * Displacement.  d_a = x_a - center_a; on a periodic axis of length L_a = lim_hi - lim_lo then
+ *   d_a <- d_a - L_a * rint(d_a / L_a), rint to nearest, ties to even.  Open and fixed axes are plain.
+ * Coordinate c.  SX_PROF_RADIUS: r = sqrt((dx*dx + dy*dy) + dz*dz).  SX_PROF_X, _Y, _Z: d_a.  SX_PROF_QUANTITY: the
+ *   value of the quantity coordQ below.
+ * Bins.  edges[nbins + 1], a host array, finite and strictly ascending; 1 <= nbins <= 4096.  A particle is in bin b iff
+ *   edges[b] <= c < edges[b + 1].  Every array of the result has nbins + 2 entries per row: entry nbins holds the
+ *   particles with c < edges[0] (underflow), entry nbins + 1 those with c >= edges[nbins] (overflow); all moments are
+ *   kept for these two as for any bin.
+ * Quantities q[k], k < nq <= SX_PROF_MAX_Q.  cv = (double)(float)((double)(8.317e7f / muiConst) / (gamma - 1.0)), the
+ *   EOS kernels' constant; gm1 = gamma - 1.0.
+ *     SX_PROF_RHO    VE, ve-bdt (std = 0): the float (kx * m) / xm; std: the float column rho.  Then widened.
+ *     SX_PROF_P      (float)((double)rho * ((cv * temp) * gm1)) with rho as above, then widened.
+ *     SX_PROF_U      cv * temp.          SX_PROF_TEMP   temp.
+ *     SX_PROF_VEL    sqrt((vx*vx + vy*vy) + vz*vz), the float velocities widened first.
+ *     SX_PROF_VRAD   ((dx*vx + dy*vy) + dz*vz) / r, and 0 where r = 0.
+ *     SX_PROF_C, _H, _DIVV, _CURLV, _ALPHA   the float column, widened.
+ *   A quantity whose columns are NULL in sx_fields is refused with a reason.
+ * Weight.  w = 1.0 (SX_PROF_NUMBER) or (double)m (SX_PROF_MASS).
+ * Solution sol[k] of quantity slot k, evaluated at xi = c * rscale.
+ *     SX_PROF_SOL_NONE   no solution; the series D of the slot is zero.
+ *     SX_PROF_SOL_TABLE  host arrays r[nt], y[nt], r ascending (equal neighbours allowed), 2 <= nt <= 2^20; numpy.interp:
+ *                        xi < r[0]: y[0]; xi >= r[nt-1]: y[nt-1]; else with j the last index with r[j] <= xi: y[j] if
+ *                        xi == r[j], otherwise ((y[j+1] - y[j]) / (r[j+1] - r[j])) * (xi - r[j]) + y[j].  A Sedov table
+ *                        of time t_sol serves time t with rscale = (t_sol / t)^0.4.
+ *     SX_PROF_SOL_NOH_RHO  compare_noh.py:49-60 with (gamma, rho0, vel0, time, xgeom in 1..3): r2 = ((0.5 * (gamma - 1))
+ *                        * |vel0|) * time; xi > r2: rho0 * b^(xgeom-1) with b = 1.0 - (vel0 * time) / max(xi, 1e-300)
+ *                        and the power 1.0, b or b * b; otherwise rho0 * pow((gamma + 1) / (gamma - 1), xgeom), computed
+ *                        once on the host with the C library's pow.
+ * Series.  1 + 3 nq series of terms per particle: W: w; per slot S1 = w * q, S2 = (w * q) * q, D = w * |q - s(c)|.
+ *   count[b] (u64) is the number of particles of the bin, min and max of q per bin are exact; an empty bin has count 0,
+ *   sums 0, min +inf, max -inf.  A particle whose coordinate, any requested quantity, solution value or term is not
+ *   finite enters no bin and is counted in `nonfinite` instead.
+ * The exact sum of a series.  M = the largest |term| of the series over all finite particles of all ranks; E = the
+ *   smallest integer with M < 2^E (M = 2^k gives E = k + 1; M = 0: every sum is 0).  fixed(t) = sign(t) *
+ *   floor(|t| * 2^(96 - E)), formed by shifting the mantissa, so bits below 2^(E - 96) are dropped.  Each bin
+ *   accumulates sum fixed(t) in a 128-bit two's-complement integer, which cannot overflow below 2^31 particles (more are
+ *   refused).  The stored result is the double nearest (ties to even) to sum * 2^(E - 96), subnormals included.
+ *   It follows that a sum differs from the exact real sum by less than count * 2^(E - 96) plus one final rounding, and
+ *   that it does not depend on the order, the launch shape, any internal capacity or the number of ranks.
+ * Derived by the caller, sums in ascending index: mean_k[b] = S1_k[b] / W[b]; l1_k = (sum over all nbins + 2 entries of
+ *   D_k) / (sum of W): with SX_PROF_NUMBER the reference's mean |solution - q| over all particles, whatever the edges. */
+#define SX_PROF_RADIUS 0
+#define SX_PROF_X 1
+#define SX_PROF_Y 2
+#define SX_PROF_Z 3
+#define SX_PROF_QUANTITY 4
+#define SX_PROF_RHO 0
+#define SX_PROF_P 1
+#define SX_PROF_U 2
+#define SX_PROF_TEMP 3
+#define SX_PROF_VEL 4
+#define SX_PROF_VRAD 5
+#define SX_PROF_C 6
+#define SX_PROF_H 7
+#define SX_PROF_DIVV 8
+#define SX_PROF_CURLV 9
+#define SX_PROF_ALPHA 10
+#define SX_PROF_NUMBER 0
+#define SX_PROF_MASS 1
+#define SX_PROF_SOL_NONE 0
+#define SX_PROF_SOL_TABLE 1
+#define SX_PROF_SOL_NOH_RHO 2
+#define SX_PROF_MAX_Q 4
+typedef struct sx_profile_solution
+{
+    int32_t       kind;
+    uint32_t      nt;     /* table: entries of r and y */
+    const double *r, *y;  /* table: host arrays */
+    double        rscale; /* xi = c * rscale */
+    double        gamma, rho0, vel0, time; /* Noh */
+    int32_t       xgeom;                   /* Noh: 1 planar, 2 cylindrical, 3 spherical */
+} sx_profile_solution;
+typedef struct sx_profile
+{
+    int32_t             coord, coordQ, weight; /* coordQ: the quantity of SX_PROF_QUANTITY */
+    double              center[3];
+    uint32_t            nbins;
+    const double*       edges; /* host, nbins + 1 */
+    uint32_t            nq;
+    int32_t             q[SX_PROF_MAX_Q];
+    sx_profile_solution sol[SX_PROF_MAX_Q];
+} sx_profile;
+/*! every pointer nullable (then not written); device pointers for sx_profile_compute, host pointers for sx_sim_profile */
+typedef struct sx_profile_result
+{
+    uint64_t* count;     /* [nbins + 2] */
+    uint64_t* nonfinite; /* one */
+    double*   W;         /* [nbins + 2] */
+    double *  S1, *S2, *D, *min, *max; /* [nq][nbins + 2] */
+} sx_profile_result;
+/*! host only, needs no GPU: SX_OK, or SX_ERR_ARG with the reason in sx_last_error(NULL) (per thread).  Refused, each
+ *  with its own message: a NULL argument, an unknown coord, quantity, weight or solution kind, nbins of 0 or above 4096,
+ *  edges that are not finite or not strictly ascending, nq above SX_PROF_MAX_Q, a table with nt below 2 or above 2^20 or
+ *  without its arrays, a table whose r descends or is not finite, an xgeom outside 1..3, a solution on a slot >= nq. */
+int sx_profile_check(const sx_profile* prof, const sx_box* box);
+/*! host only, the number format of the exact sums: *E = the window of n terms (the smallest E with max |t| < 2^E, and
+ *  -1074 where every term is 0); SX_ERR_ARG for a term that is not finite */
+int sx_profile_window(const double* t, size_t n, int32_t* E);
+/*! host only: fixed(t[i]) of window E as two words, lohi[2 i] the low and lohi[2 i + 1] the high half of the 128-bit
+ *  two's-complement integer; SX_ERR_ARG for a term that is not finite or not below 2^E in magnitude */
+int sx_profile_to_fixed(const double* t, size_t n, int32_t E, uint64_t* lohi);
+/*! host only: acc (low, high) += the n integers of lohi, modulo 2^128 */
+int sx_profile_add_fixed(uint64_t acc[2], const uint64_t* lohi, size_t n);
+/*! host only: *out = the double nearest (ties to even) to acc * 2^(E - 96), subnormals included */
+int sx_profile_from_fixed(const uint64_t acc[2], int32_t E, double* out);
+/*! the largest nbins for which the bins of nq quantities fit one block-private LDS tile (64 KB less 128 bytes per
+ *  workgroup, so that two workgroups stay resident per CU; 24 + 64 nq bytes per bin, nbins + 2 bins); above it the bins
+ *  are split into ceil((nbins + 2) / (that + 2)) tiles and pass 2 runs once per tile.  The result has the same bits
+ *  either way.  0 for an nq outside 0 .. 4. */
+uint32_t sx_profile_lds_bins(int nq);
+/*! measurement and tests: on = 0 makes the following sx_profile_compute calls of the context add straight into the
+ *  global array with global atomics (one pass 2, no tiles: the same bits, far slower), 1 (the default) in LDS */
+int sx_set_profile_lds(sx_ctx* ctx, int on);
+/*! the profile of the particles [first, last) of f (at most 2^31 - 1) into the device arrays of deviceOut.  gamma and
+ *  muiConst are read from params; std != 0 reads the rho column.  Two passes over the particles (the windows, then the
+ *  integer sums; 64-bit integer atomics in LDS and in global memory) and one conversion kernel.  The accumulators and
+ *  the uploaded edges and tables live in the context.  SX_ERR_ARG: whatever sx_profile_check refuses, a quantity whose
+ *  columns are NULL, first > last or last > f->n.  Synchronises. */
+int sx_profile_compute(sx_ctx* ctx, const sx_fields* f, const sx_box* box, uint32_t first, uint32_t last,
+                       const sx_params* params, int std, const sx_profile* prof, sx_profile_result* deviceOut);
+/*! the context's last profile: {particles read, 1 if the bins were in LDS, passes over the particles (1 + tiles),
+ *  nonfinite};
+ *  SX_ERR_ARG before the first */
+int sx_profile_stats(sx_ctx* ctx, uint64_t out[4]);
+/*! measurement: with on != 0 the following calls time their kernels with HIP events; sx_profile_times: {pass 1, pass 2,
+ *  conversion} in ms of the last call and out[3] = the bytes one pass reads */
+int sx_set_profile_timing(sx_ctx* ctx, int on);
+int sx_profile_times(sx_ctx* ctx, double out[4]);
+
 /* ---- self-gravity: ryoanji MultipoleHolder seam (multipole_holder.cuh:40-66, gravity_wrapper.hpp:104-174) ----- */
 /*! expansion centers (mass centers, {x,y,z,mac^2}, numNodes x 4 doubles; mac = 2 max(node size)/theta + |com-geo|,
  *  setMac, source_center.hpp:130-143) and Cartesian quadrupoles (numNodes x 8 floats, Cqi order,
@@ -808,6 +943,22 @@ int    sx_sim_set_map_pair_cap(sx_sim* sim, uint64_t pairs);
 int    sx_sim_spectrum(sx_sim* sim, const sx_spectrum* spec, int field, double* hostPower, uint64_t* hostModes);
 int    sx_sim_spectrum_stats(sx_sim* sim, uint64_t out[4]);
 int    sx_sim_set_spectrum_pair_cap(sx_sim* sim, uint64_t pairs);
+/*! sx_profile_compute of the current state over all ranks: each rank reads its locals; the windows agree through one
+ *  u32-max reduction (sx_comm_allreduce op 4) of 14 words whatever the specification -- the first word counts a rank
+ *  that must refuse (whatever sx_profile_check refuses for it, a quantity its layout does not keep), so nobody waits in
+ *  a reduction for a rank that left early: that rank returns its code, every other rank SX_ERR_ARG --; the integer
+ *  accumulators and counts travel as 16-bit limbs through one u32-sum reduction (exact for up to 2^16 ranks) and the
+ *  carries are propagated afterwards; min and max through one f64-min reduction (max as -min(-x)).  Every rank receives
+ *  the whole result, bit-identical to the profile of the merged particles on one rank, in the host arrays of hostOut
+ *  through a pinned buffer; synchronises.  gamma and muiConst are the sim's; rho is the rho column under the std
+ *  propagator and (kx * m) / xm otherwise.  Every propagator (under the gravity-only one only VEL, VRAD and H exist);
+ *  under ve-bdt between any two substeps.  Nothing in sx_sim_step calls it and it changes no state.  The dependent
+ *  fields (kx, xm, rho, c, divv, curlv) are those of the last force stage.  The buffers live in the sim's arena under
+ *  the tags prof.*, are allocated by the first call and counted by sx_sim_memory from then on.  More than 2^31 - 1
+ *  particles over all ranks are refused.  sx_sim_profile_stats: sx_profile_stats of the sim's last call (this rank's
+ *  particles; nonfinite over all ranks). */
+int    sx_sim_profile(sx_sim* sim, const sx_profile* prof, sx_profile_result* hostOut);
+int    sx_sim_profile_stats(sx_sim* sim, uint64_t out[4]);
 /*! device time (ms) of each hot kernel alone in the last step (HIP events on the launch stream, bracketing just the
  *  launch): findNeighbors, xmass, veDefGradh, iadDivvCurlv, avSwitches, momentumEnergy */
 int    sx_sim_kernel_times(sx_sim* sim, float* ms, int cap, const char** names);

@@ -21,6 +21,7 @@
 #include "sx_map.hpp"
 #include "sx_nbody.hpp"
 #include "sx_observables.hpp"
+#include "sx_profile.hpp"
 #include "sx_spectrum.hpp"
 #include "sx_tree.hpp"
 #include "sx_timestep.hpp"
@@ -127,6 +128,7 @@ struct sx_ctx
     Arena       arena;
     sx::map::MapBuffers mapBuf;          // pair scratch and figures of sx_map_render
     sx::spectrum::SpecBuffers specBuf;   // scratch, per-n tables, meshes and figures of the spectra
+    sx::profile::ProfBuffers profBuf;    // accumulators, uploaded edges and tables and figures of the profiles
     float2*     wh{nullptr};
     float2*     whd{nullptr};
     double      K{0};
@@ -270,6 +272,7 @@ extern "C"
         (void)hipDeviceSynchronize();
         sx::map::release(c->mapBuf);
         sx::spectrum::release(c->specBuf);
+        sx::profile::release(c->profBuf);
         c->arena.release();
         if (c->own) (void)hipStreamDestroy(c->own);
         delete c;
@@ -1558,6 +1561,108 @@ extern "C"
         if (rc == sx::spectrum::kStatsMismatch)
             return fail(c, SX_ERR_HIP, std::string("sx_spectrum_stats: ") + sx::spectrum::kStatsMismatchText);
         return rc == SX_OK ? SX_OK : fail(c, rc, rc == SX_ERR_ARG ? "sx_spectrum_stats: nothing has been deposited" : "sx_spectrum_stats: copy failed");
+    }
+
+    // ---- binned profiles with exact sums (sx_profile.hpp) ----------------------------------------------------------
+    int sx_profile_check(const sx_profile* p, const sx_box* box)
+    {
+        if (const char* why = sx::profile::checkSpec(p, box)) return fail(nullptr, SX_ERR_ARG, why);
+        return SX_OK;
+    }
+
+    int sx_profile_window(const double* t, size_t n, int32_t* E)
+    {
+        if ((!t && n) || !E) return fail(nullptr, SX_ERR_ARG, "sx_profile_window: null terms or E");
+        uint32_t key = 0;
+        for (size_t i = 0; i < n; ++i)
+        {
+            if (!std::isfinite(t[i])) return fail(nullptr, SX_ERR_ARG, "sx_profile_window: a term is not finite");
+            key = std::max(key, sx::profile::windowKey(t[i]));
+        }
+        *E = sx::profile::windowOfKey(key);
+        return SX_OK;
+    }
+
+    int sx_profile_to_fixed(const double* t, size_t n, int32_t E, uint64_t* lohi)
+    {
+        if ((!t || !lohi) && n) return fail(nullptr, SX_ERR_ARG, "sx_profile_to_fixed: null terms or output");
+        for (size_t i = 0; i < n; ++i)
+        {
+            if (!std::isfinite(t[i]) || sx::profile::windowOfKey(sx::profile::windowKey(t[i])) > E)
+                return fail(nullptr, SX_ERR_ARG, "sx_profile_to_fixed: a term is not finite or not below 2^E");
+            const sx::profile::U128 v = sx::profile::toFixed(t[i], E);
+            lohi[2 * i] = v.lo, lohi[2 * i + 1] = v.hi;
+        }
+        return SX_OK;
+    }
+
+    int sx_profile_add_fixed(uint64_t acc[2], const uint64_t* lohi, size_t n)
+    {
+        if (!acc || (!lohi && n)) return fail(nullptr, SX_ERR_ARG, "sx_profile_add_fixed: null accumulator or terms");
+        sx::profile::U128 a{acc[0], acc[1]};
+        for (size_t i = 0; i < n; ++i)
+            sx::profile::addFixed(a, sx::profile::U128{lohi[2 * i], lohi[2 * i + 1]});
+        acc[0] = a.lo, acc[1] = a.hi;
+        return SX_OK;
+    }
+
+    int sx_profile_from_fixed(const uint64_t acc[2], int32_t E, double* out)
+    {
+        if (!acc || !out) return fail(nullptr, SX_ERR_ARG, "sx_profile_from_fixed: null accumulator or output");
+        *out = sx::profile::fromFixed(sx::profile::U128{acc[0], acc[1]}, E);
+        return SX_OK;
+    }
+
+    uint32_t sx_profile_lds_bins(int nq) { return nq < 0 || nq > sx::profile::kMaxQ ? 0 : sx::profile::ldsBins(nq); }
+
+    int sx_set_profile_lds(sx_ctx* c, int on)
+    {
+        if (!c) return SX_ERR_ARG;
+        c->profBuf.useLds = on != 0;
+        return SX_OK;
+    }
+
+    int sx_set_profile_timing(sx_ctx* c, int on)
+    {
+        if (!c) return SX_ERR_ARG;
+        c->profBuf.timing = on != 0;
+        return SX_OK;
+    }
+
+    int sx_profile_times(sx_ctx* c, double out[4])
+    {
+        if (!c || !out) return SX_ERR_ARG;
+        for (int k = 0; k < 3; ++k)
+            out[k] = c->profBuf.ms[k];
+        out[3] = c->profBuf.passBytes;
+        return SX_OK;
+    }
+
+    int sx_profile_stats(sx_ctx* c, uint64_t out[4])
+    {
+        if (!c || !out) return SX_ERR_ARG;
+        if (!c->profBuf.done) return fail(c, SX_ERR_ARG, "sx_profile_stats: no profile has been computed");
+        std::copy(c->profBuf.stats, c->profBuf.stats + 4, out);
+        return SX_OK;
+    }
+
+    int sx_profile_compute(sx_ctx* c, const sx_fields* f, const sx_box* box, uint32_t first, uint32_t last,
+                           const sx_params* params, int std, const sx_profile* p, sx_profile_result* res)
+    {
+        if (!c) return SX_ERR_ARG;
+        if (!f || !box || !params || !p || !res) return fail(c, SX_ERR_ARG, "sx_profile_compute: null fields, box, params, profile or result");
+        if (first > last || last > f->n) return fail(c, SX_ERR_ARG, "sx_profile_compute: [first, last) is not a range of f");
+        if (const char* why = sx::profile::whyRefused(p, box, *f, std, last - first)) return fail(c, SX_ERR_ARG, why);
+        std::string err;
+        const int   rc = sx::profile::compute(c->arena, c->profBuf, *p, *f, *box, first, last, params->muiConst,
+                                              params->gamma, std, nullptr, sx::profile::Reduce{}, c->stream, err);
+        if (rc != SX_OK) return fail(c, rc, err);
+        sx::profile::Piece pc[8];
+        const int          np = sx::profile::pieces(p->nbins, p->nq, *res, pc);
+        for (int k = 0; k < np; ++k)
+            SX_HIP(c, hipMemcpyAsync(pc[k].dst, c->profBuf.out + pc[k].off, pc[k].words * 8, hipMemcpyDeviceToDevice, c->stream));
+        SX_HIP(c, hipStreamSynchronize(c->stream));
+        return SX_OK;
     }
 
     int sx_set_direct_splits(sx_ctx* c, uint32_t splits)

@@ -1028,6 +1028,7 @@ extern "C"
         turbDestroy(s->turb);
         sx::map::release(s->mapBuf);
         sx::spectrum::release(s->specBuf);
+        sx::profile::release(s->profBuf);
         delete s;
     }
 

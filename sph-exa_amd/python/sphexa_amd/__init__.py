@@ -258,6 +258,151 @@ def spectrum_chunk_records():
     return int(lib().sx_spectrum_chunk_records())
 
 
+PROF_COORDS = {"radius": 0, "x": 1, "y": 2, "z": 3, "quantity": 4}
+PROF_QUANTITIES = {"rho": 0, "p": 1, "u": 2, "temp": 3, "vel": 4, "vrad": 5, "c": 6, "h": 7, "divv": 8, "curlv": 9,
+                   "alpha": 10}
+PROF_WEIGHTS = {"number": 0, "mass": 1}
+PROF_SOLUTIONS = {"none": 0, "table": 1, "noh": 2}
+PROF_MAX_Q = 4
+
+
+class SxProfileSolution(C.Structure):
+    """sx_profile_solution: "table" (r, y ascending in r, evaluated as numpy.interp at c * rscale) or "noh" (the closed
+    form of the Noh density with gamma, rho0, vel0, time, xgeom)"""
+    _fields_ = [("kind", C.c_int32), ("nt", C.c_uint32), ("r", C.c_void_p), ("y", C.c_void_p), ("rscale", C.c_double),
+                ("gamma", C.c_double), ("rho0", C.c_double), ("vel0", C.c_double), ("time", C.c_double),
+                ("xgeom", C.c_int32)]
+
+
+class SxProfile(C.Structure):
+    """sx_profile: the bin coordinate ("radius", "x", "y", "z", or a quantity name: then coord is "quantity"), the
+    weight ("number" or "mass"), the centre, the edges (nbins + 1, ascending), up to four quantities (names of
+    PROF_QUANTITIES) and per quantity a solution: None, ("table", r, y[, rscale]) or ("noh", dict(time=, gamma=5/3,
+    rho0=1, vel0=-1, xgeom=3, rscale=1)).  The arrays are kept alive by the object."""
+    _fields_ = [("coord", C.c_int32), ("coordQ", C.c_int32), ("weight", C.c_int32), ("center", C.c_double * 3),
+                ("nbins", C.c_uint32), ("edges", C.c_void_p), ("nq", C.c_uint32), ("q", C.c_int32 * PROF_MAX_Q),
+                ("sol", SxProfileSolution * PROF_MAX_Q)]
+
+    def __init__(self, edges=(0.0, 1.0), quantities=("rho",), coord="radius", center=(0.0, 0.0, 0.0), weight="number",
+                 solutions=None):
+        super().__init__()
+        if coord in PROF_QUANTITIES:
+            self.coord, self.coordQ = PROF_COORDS["quantity"], PROF_QUANTITIES[coord]
+        else:
+            self.coord = PROF_COORDS.get(coord, coord)
+        self.weight = PROF_WEIGHTS.get(weight, weight)
+        for k in range(3):
+            self.center[k] = float(center[k])
+        self._keep = [np.ascontiguousarray(edges, dtype=np.float64)]
+        self.nbins = max(0, self._keep[0].size - 1)
+        self.edges = self._keep[0].ctypes.data
+        self.names = [q if isinstance(q, str) else PROF_QUANTITIES_BY_CODE.get(q, str(q)) for q in quantities]
+        self.nq = len(quantities)
+        for k, q in enumerate(list(quantities)[:PROF_MAX_Q]):
+            self.q[k] = PROF_QUANTITIES.get(q, q)
+        for name, sol in (solutions or {}).items():
+            self.set_solution(self.names.index(name) if isinstance(name, str) else int(name), sol)
+
+    def set_solution(self, slot, sol):
+        s = self.sol[slot]
+        if sol is None:
+            s.kind = 0
+        elif sol[0] == "table":
+            r, y = (np.ascontiguousarray(v, dtype=np.float64) for v in sol[1:3])
+            if r.size != y.size:
+                raise ValueError("a table's r and y differ in length")
+            self._keep += [r, y]
+            s.kind, s.nt, s.r, s.y = 1, r.size, r.ctypes.data, y.ctypes.data
+            s.rscale = float(sol[3]) if len(sol) > 3 else 1.0
+        elif sol[0] == "noh":
+            kw = dict(gamma=5.0 / 3.0, rho0=1.0, vel0=-1.0, xgeom=3, rscale=1.0)
+            kw.update(sol[1])
+            s.kind, s.rscale, s.gamma, s.rho0, s.vel0 = 2, kw["rscale"], kw["gamma"], kw["rho0"], kw["vel0"]
+            s.time, s.xgeom = kw["time"], kw["xgeom"]
+        else:
+            raise ValueError(f"unknown solution {sol[0]!r}: 'table' or 'noh'")
+
+
+PROF_QUANTITIES_BY_CODE = {v: k for k, v in PROF_QUANTITIES.items()}
+
+
+class SxProfileResult(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("count", "nonfinite", "W", "S1", "S2", "D", "min", "max")]
+
+
+def profile_check(spec, box):
+    """sx_profile_check: raises SxError with the reason for a specification a call would refuse.  Needs no GPU."""
+    if lib().sx_profile_check(C.byref(spec) if spec is not None else None, C.byref(box) if box is not None else None) != SX_OK:
+        raise SxError(lib().sx_last_error(None).decode())
+
+
+def profile_lds_bins(nq):
+    """the largest nbins whose bins of nq quantities are accumulated in LDS (sx_profile_lds_bins)"""
+    return int(lib().sx_profile_lds_bins(int(nq)))
+
+
+def profile_window(t):
+    """the window E of the terms t: the smallest E with max |t| < 2^E, -1074 for zeros (sx_profile_window)"""
+    t = np.ascontiguousarray(t, dtype=np.float64)
+    E = C.c_int32()
+    if lib().sx_profile_window(t.ctypes.data, t.size, C.byref(E)) != SX_OK:
+        raise SxError(lib().sx_last_error(None).decode())
+    return E.value
+
+
+def profile_to_fixed(t, E):
+    """fixed(t) of window E as (n, 2) uint64: low and high word of the 128-bit integer (sx_profile_to_fixed)"""
+    t = np.ascontiguousarray(t, dtype=np.float64)
+    out = np.zeros((t.size, 2), np.uint64)
+    if lib().sx_profile_to_fixed(t.ctypes.data, t.size, int(E), out.ctypes.data) != SX_OK:
+        raise SxError(lib().sx_last_error(None).decode())
+    return out
+
+
+def profile_add_fixed(lohi, acc=(0, 0)):
+    """acc + the integers of lohi modulo 2^128, as (low, high) Python ints (sx_profile_add_fixed)"""
+    lohi = np.ascontiguousarray(lohi, dtype=np.uint64)
+    a = (C.c_uint64 * 2)(int(acc[0]), int(acc[1]))
+    if lib().sx_profile_add_fixed(a, lohi.ctypes.data, lohi.size // 2) != SX_OK:
+        raise SxError(lib().sx_last_error(None).decode())
+    return int(a[0]), int(a[1])
+
+
+def profile_from_fixed(acc, E):
+    """the double nearest to acc 2^(E - 96), acc = (low, high) (sx_profile_from_fixed)"""
+    a = (C.c_uint64 * 2)(int(acc[0]), int(acc[1]))
+    out = C.c_double()
+    if lib().sx_profile_from_fixed(a, int(E), C.byref(out)) != SX_OK:
+        raise SxError(lib().sx_last_error(None).decode())
+    return out.value
+
+
+def profile_dict(spec, res):
+    """the packed arrays of a profile call as the dict Sim.profile returns"""
+    nb, nq = int(spec.nbins), int(spec.nq)
+    out = {"edges": spec._keep[0].copy(), "count": res["count"][:nb], "under": int(res["count"][nb]),
+           "over": int(res["count"][nb + 1]), "nonfinite": int(res["nonfinite"][0]), "W": res["W"][:nb],
+           "raw": res}
+    wsum = 0.0
+    for w in res["W"]:
+        wsum += float(w)
+    for key in ("mean", "sum", "sum2", "min", "max", "dev", "l1"):
+        out[key] = {}
+    for k, name in enumerate(spec.names):
+        s1 = res["S1"][k]
+        out["sum"][name], out["sum2"][name] = s1[:nb], res["S2"][k][:nb]
+        out["min"][name], out["max"][name] = res["min"][k][:nb], res["max"][k][:nb]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["mean"][name] = s1[:nb] / res["W"][:nb]
+        if spec.sol[k].kind:
+            out["dev"][name] = res["D"][k][:nb]
+            d = 0.0
+            for v in res["D"][k]:
+                d += float(v)
+            out["l1"][name] = d / wsum if wsum else float("nan")
+    return out
+
+
 class SxOctree(C.Structure):
     _fields_ = [("prefixes", _P), ("childOffsets", _P), ("parents", _P), ("levelRange", _P),
                 ("internalToLeaf", _P), ("leafToInternal", _P)]
@@ -482,6 +627,20 @@ def lib():
         "sx_sim_spectrum": (C.c_int, [vp, C.POINTER(SxSpectrum), C.c_int, vp, vp]),
         "sx_sim_spectrum_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         "sx_sim_set_spectrum_pair_cap": (C.c_int, [vp, C.c_uint64]),
+        "sx_profile_check": (C.c_int, [C.POINTER(SxProfile), C.POINTER(SxBox)]),
+        "sx_profile_window": (C.c_int, [vp, sz, C.POINTER(i32)]),
+        "sx_profile_to_fixed": (C.c_int, [vp, sz, i32, vp]),
+        "sx_profile_add_fixed": (C.c_int, [C.POINTER(C.c_uint64), vp, sz]),
+        "sx_profile_from_fixed": (C.c_int, [C.POINTER(C.c_uint64), i32, C.POINTER(C.c_double)]),
+        "sx_profile_lds_bins": (u32, [C.c_int]),
+        "sx_set_profile_lds": (C.c_int, [vp, C.c_int]),
+        "sx_profile_compute": (C.c_int, [vp, C.POINTER(SxFields), C.POINTER(SxBox), u32, u32, C.POINTER(SxParams),
+                                         C.c_int, C.POINTER(SxProfile), C.POINTER(SxProfileResult)]),
+        "sx_profile_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        "sx_set_profile_timing": (C.c_int, [vp, C.c_int]),
+        "sx_profile_times": (C.c_int, [vp, C.POINTER(C.c_double)]),
+        "sx_sim_profile": (C.c_int, [vp, C.POINTER(SxProfile), C.POINTER(SxProfileResult)]),
+        "sx_sim_profile_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     }
     for name, (res, args) in sig.items():
         # a measurement build named by SPHEXA_AMD_LIB (an A/B against an older library) may predate an entry
@@ -908,6 +1067,48 @@ class Context:
         out = (C.c_double * 5)()
         self.check(self.L.sx_spectrum_times(self.h, out), "sx_spectrum_times")
         return dict(zip(["binning_ms", "sort_ms", "gather_ms", "fft_ms", "shells_ms"], list(out)))
+
+    # ---- binned profiles with exact sums ---------------------------------------------------------------------
+    def profile(self, fields, box, spec, first=0, last=None, params=None, std=False):
+        """the profile `spec` (an SxProfile) of the particles [first, last) of an SxFields (sx_profile_compute): a dict
+        of arrays with nbins + 2 entries per row (the last two: underflow, overflow): count (uint64), nonfinite, W, and
+        S1, S2, D, min, max of shape (nq, nbins + 2).  params: gamma and muiConst (default_params())."""
+        # a spec beyond the limits is refused by the call before it writes: the arrays need not hold it
+        nb2, nq = min(int(spec.nbins), 4096) + 2, min(int(spec.nq), PROF_MAX_Q)
+        last = fields.n if last is None else last
+        params = params if params is not None else default_params()
+        shapes = {"count": (nb2,), "nonfinite": (1,), "W": (nb2,)}
+        shapes.update({k: (nq, nb2) for k in ("S1", "S2", "D", "min", "max")})
+        dev = {k: self.alloc(max(1, int(np.prod(s))), np.uint64 if k in ("count", "nonfinite") else np.float64)
+               for k, s in shapes.items()}
+        res = SxProfileResult(**{k: d.ptr for k, d in dev.items()})
+        try:
+            self.check(self.L.sx_profile_compute(self.h, C.byref(fields), C.byref(box), int(first), int(last),
+                                                 C.byref(params), int(bool(std)), C.byref(spec), C.byref(res)),
+                       "sx_profile_compute")
+            return {k: dev[k].get()[: int(np.prod(s))].reshape(s) for k, s in shapes.items()}
+        finally:
+            for d in dev.values():
+                self.free(d)
+
+    def set_profile_lds(self, on=True):
+        """False: the following profiles accumulate in the global array whatever nbins (sx_set_profile_lds)"""
+        self.check(self.L.sx_set_profile_lds(self.h, 1 if on else 0), "sx_set_profile_lds")
+
+    def profile_stats(self):
+        """the last profile: {particles, lds (1: the bins were in LDS), passes, nonfinite}"""
+        out = (C.c_uint64 * 4)()
+        self.check(self.L.sx_profile_stats(self.h, out), "sx_profile_stats")
+        return dict(zip(["particles", "lds", "passes", "nonfinite"], [int(v) for v in out]))
+
+    def set_profile_timing(self, on=True):
+        self.check(self.L.sx_set_profile_timing(self.h, 1 if on else 0), "sx_set_profile_timing")
+
+    def profile_times(self):
+        """{pass 1, pass 2, conversion} in ms of the last profile (after set_profile_timing) and the bytes a pass reads"""
+        out = (C.c_double * 4)()
+        self.check(self.L.sx_profile_times(self.h, out), "sx_profile_times")
+        return {"pass1_ms": out[0], "pass2_ms": out[1], "final_ms": out[2], "pass_bytes": out[3]}
 
     def observables(self, fields, kind, first=0, last=None, box=None, settings=None, mui=10.0, gamma=5.0 / 3.0,
                     cap=None):
@@ -1462,6 +1663,35 @@ class Sim:
 
     def set_spectrum_pair_cap(self, pairs=0):
         self.ctx.check(self.L.sx_sim_set_spectrum_pair_cap(self.h, int(pairs)), "sx_sim_set_spectrum_pair_cap")
+
+    def profile_spec(self, edges, quantities=("rho", "p", "vel", "u"), coord="radius", center=None, weight="number",
+                     solutions=None):
+        """the SxProfile of profile(): center defaults to the box centre"""
+        if center is None:
+            center = [0.5 * (self.box.lim[2 * k] + self.box.lim[2 * k + 1]) for k in range(3)]
+        return SxProfile(edges, quantities, coord, center, weight, solutions)
+
+    def profile(self, edges, quantities=("rho", "p", "vel", "u"), coord="radius", center=None, weight="number",
+                solutions=None, spec=None):
+        """binned moments of the current state over all ranks with exact, order-independent sums (sx_sim_profile).
+        coord: "radius", "x", "y", "z" or a quantity name (a PDF of it); quantities: up to four names of
+        PROF_QUANTITIES; weight "number" or "mass"; center: the box centre by default; solutions: {quantity: ("table",
+        r, y[, rscale]) or ("noh", dict(time=..., rho0=..., ...))}.  Returns a dict: edges, count, under, over,
+        nonfinite, W, and per quantity name mean, sum, sum2, min, max, plus dev and l1 (the mean |q - solution| over all
+        particles) where a solution was given; raw holds the arrays with the underflow and overflow entries."""
+        spec = spec if spec is not None else self.profile_spec(edges, quantities, coord, center, weight, solutions)
+        nb2, nq = int(spec.nbins) + 2, int(spec.nq)
+        res = {"count": np.zeros(nb2, np.uint64), "nonfinite": np.zeros(1, np.uint64), "W": np.zeros(nb2)}
+        res.update({k: np.zeros((min(nq, PROF_MAX_Q), nb2)) for k in ("S1", "S2", "D", "min", "max")})
+        out = SxProfileResult(**{k: v.ctypes.data for k, v in res.items()})
+        self.ctx.check(self.L.sx_sim_profile(self.h, C.byref(spec), C.byref(out)), "sx_sim_profile")
+        return profile_dict(spec, res)
+
+    def profile_stats(self):
+        """this rank's figures of the last profile(): {particles, lds, passes, nonfinite}"""
+        out = (C.c_uint64 * 4)()
+        self.ctx.check(self.L.sx_sim_profile_stats(self.h, out), "sx_sim_profile_stats")
+        return dict(zip(["particles", "lds", "passes", "nonfinite"], [int(v) for v in out]))
 
     def write_constants(self, fileobj):
         """append the row of observe() to a constants.txt (format_constants_row); returns the row"""
