@@ -24,8 +24,11 @@ SOURCES = {
     "sx_tree": ("csrc/sx_tree.hip", ["-ffp-contract=off"]),
     "sx_timestep": ("csrc/sx_timestep.hip", ["-ffp-contract=off"]),
     "sx_skin": ("csrc/sx_skin.hip", ["-ffp-contract=off"]),
+    "sx_pairbin": ("csrc/sx_pairbin.hip", ["-ffp-contract=off"]),
+    "sx_map": ("csrc/sx_map.hip", ["-ffp-contract=fast"]),
+    "sx_spectrum": ("csrc/sx_spectrum.hip", ["-ffp-contract=fast"]),
 }
-KEYS = {"VGPRs": "vgpr", "AGPRs": "agpr", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occ",
+KEYS = {"TotalSGPRs": "sgpr", "VGPRs": "vgpr", "AGPRs": "agpr", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occ",
         "SGPRs Spill": "sspill", "VGPRs Spill": "vspill", "LDS Size [bytes/block]": "lds"}
 
 
@@ -45,7 +48,7 @@ def run(name, src, flags, extra):
     print(f"== {name}")
     for r in rows:
         flag = " <-- spills" if r.get("vspill", "0") != "0" or r.get("scratch", "0") != "0" else ""
-        print(f"  {r['kernel'][:78]:78s} vgpr {r.get('vgpr', '?'):>3} occ {r.get('occ', '?'):>2} "
+        print(f"  {r['kernel'][:78]:78s} vgpr {r.get('vgpr', '?'):>3} sgpr {r.get('sgpr', '?'):>3} occ {r.get('occ', '?'):>2} "
               f"scratch {r.get('scratch', '?'):>4} vspill {r.get('vspill', '?'):>3} lds {r.get('lds', '?'):>6}{flag}")
 
 

@@ -270,8 +270,8 @@ extern "C"
     {
         if (!c) return;
         (void)hipDeviceSynchronize();
-        sx::map::release(c->mapBuf);
-        sx::spectrum::release(c->specBuf);
+        sx::pairbin::release(c->mapBuf.bin);
+        sx::pairbin::release(c->specBuf.bin);
         sx::profile::release(c->profBuf);
         c->arena.release();
         if (c->own) (void)hipStreamDestroy(c->own);
@@ -1411,14 +1411,14 @@ extern "C"
     int sx_set_map_pair_cap(sx_ctx* c, uint64_t pairs)
     {
         if (!c) return SX_ERR_ARG;
-        c->mapBuf.pairCap = pairs;
+        c->mapBuf.bin.pairCap = pairs;
         return SX_OK;
     }
 
     int sx_set_map_timing(sx_ctx* c, int on)
     {
         if (!c) return SX_ERR_ARG;
-        c->mapBuf.timing = on != 0;
+        c->mapBuf.bin.timing = on != 0;
         return SX_OK;
     }
 
@@ -1426,8 +1426,8 @@ extern "C"
     {
         if (!c || !out) return SX_ERR_ARG;
         for (int k = 0; k < 3; ++k)
-            out[k] = c->mapBuf.ms[k];
-        out[3] = (double)c->mapBuf.scratchBytes;
+            out[k] = c->mapBuf.bin.ms[k];
+        out[3] = (double)c->mapBuf.bin.scratchBytes;
         return SX_OK;
     }
 
@@ -1448,9 +1448,24 @@ extern "C"
     int sx_map_stats(sx_ctx* c, uint64_t out[4])
     {
         if (!c || !out) return SX_ERR_ARG;
-        const int rc = sx::map::stats(c->mapBuf, c->stream, out);
-        if (rc == sx::map::kStatsMismatch) return fail(c, SX_ERR_HIP, std::string("sx_map_stats: ") + sx::map::kStatsMismatchText);
-        return rc == SX_OK ? SX_OK : fail(c, rc, rc == SX_ERR_ARG ? "sx_map_stats: nothing has been rendered" : "sx_map_stats: copy failed");
+        std::string why;
+        const int   rc = sx::pairbin::statsCode(sx::pairbin::stats(c->mapBuf.bin, c->stream, out), "sx_map_stats", sx::map::kNames, why);
+        return rc == SX_OK ? SX_OK : fail(c, rc, why);
+    }
+
+    /*! host only, not in the public header: the engine's band plan (sx_pairbin.hpp) for `rows` row counts under `cap`
+     *  (0: the default), with the maps' words.  r0r1 receives 2 * *numBands ints, at most 2 * rows.  The planner's code;
+     *  the reason for a refusal is in sx_last_error(NULL). */
+    int sx_pair_bands_internal(const uint64_t* rowCounts, int rows, uint64_t cap, int* r0r1, int* numBands)
+    {
+        if ((!rowCounts && rows) || rows < 0 || !r0r1 || !numBands) return fail(nullptr, SX_ERR_ARG, "sx_pair_bands_internal: null argument");
+        sx::pairbin::BandPlan plan;
+        std::string           err;
+        if (int rc = sx::pairbin::planBands(rowCounts, rows, cap, sx::map::kNames, plan, err)) return fail(nullptr, rc, err);
+        *numBands = (int)plan.bands.size();
+        for (size_t k = 0; k < plan.bands.size(); ++k)
+            r0r1[2 * k] = plan.bands[k].r0, r0r1[2 * k + 1] = plan.bands[k].r1;
+        return SX_OK;
     }
 
     // ---- power spectra ------------------------------------------------------------------------------------------
@@ -1475,22 +1490,23 @@ extern "C"
     int sx_set_spectrum_pair_cap(sx_ctx* c, uint64_t pairs)
     {
         if (!c) return SX_ERR_ARG;
-        c->specBuf.pairCap = pairs;
+        c->specBuf.bin.pairCap = pairs;
         return SX_OK;
     }
 
     int sx_set_spectrum_timing(sx_ctx* c, int on)
     {
         if (!c) return SX_ERR_ARG;
-        c->specBuf.timing = on != 0;
+        c->specBuf.bin.timing = on != 0;
         return SX_OK;
     }
 
     int sx_spectrum_times(sx_ctx* c, double out[5])
     {
         if (!c || !out) return SX_ERR_ARG;
-        for (int k = 0; k < 5; ++k)
-            out[k] = c->specBuf.ms[k];
+        for (int k = 0; k < 3; ++k)
+            out[k] = c->specBuf.bin.ms[k];
+        out[3] = c->specBuf.msFft, out[4] = c->specBuf.msShells;
         return SX_OK;
     }
 
@@ -1557,10 +1573,10 @@ extern "C"
     int sx_spectrum_stats(sx_ctx* c, uint64_t out[4])
     {
         if (!c || !out) return SX_ERR_ARG;
-        const int rc = sx::spectrum::stats(c->specBuf, c->stream, out);
-        if (rc == sx::spectrum::kStatsMismatch)
-            return fail(c, SX_ERR_HIP, std::string("sx_spectrum_stats: ") + sx::spectrum::kStatsMismatchText);
-        return rc == SX_OK ? SX_OK : fail(c, rc, rc == SX_ERR_ARG ? "sx_spectrum_stats: nothing has been deposited" : "sx_spectrum_stats: copy failed");
+        std::string why;
+        const int   rc = sx::pairbin::statsCode(sx::pairbin::stats(c->specBuf.bin, c->stream, out), "sx_spectrum_stats",
+                                                sx::spectrum::kNames, why);
+        return rc == SX_OK ? SX_OK : fail(c, rc, why);
     }
 
     // ---- binned profiles with exact sums (sx_profile.hpp) ----------------------------------------------------------

@@ -1,6 +1,7 @@
 /*! @file sx_map.hip
  * @brief Column-density and slice maps (sx_map.hpp): footprint binning into 16 x 16-pixel tiles, a radix sort of the
- *        (tile, particle) pairs, and one workgroup per tile that gathers its list through LDS in list order.
+ *        (tile, particle) pairs (both the pair-binning engine's, sx_pairbin.hpp), and one workgroup per tile that
+ *        gathers its list through LDS in list order.
  *
  * Geometry.  Pixel (i, j) has its centre at window coordinates (i + 0.5, j + 0.5) in pixel units.  A particle with
  * in-plane reach R (2 he for a column, sqrt(4 h^2 - dn^2) for a slice) touches the pixels whose centres lie within R
@@ -13,8 +14,6 @@
  * The kernel value is exactly 0 beyond the support (mapKernelY, kernelWt), so the binning and the per-wave cull may be
  * conservative without changing a bit of the image.
  */
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -73,25 +72,27 @@ struct Particles
     int           aIsDouble;
 };
 
-//! tile intervals [lo, hi] along one axis: the pixels whose centres lie within r of an image of f (pixel units)
+/*! tile intervals [lo, hi] along one axis, one slot per image -L, 0, +L of f: the pixels whose centres lie within r of
+ *  that image (pixel units), less the tiles of an earlier slot; an unused slot is empty (lo > hi).  The slots are walked
+ *  by unrolled loops, so a Span lives in registers. */
 struct Span
 {
-    int lo[3], hi[3], n;
+    int lo[3]{0, 0, 0}, hi[3]{-1, -1, -1};
 };
 
 __device__ inline void tileSpan(double f, double r, double Lpix, int npix, Span& s)
 {
-    s.n            = 0;
-    int       prev = -1;
-    const int k0 = Lpix > 0.0 ? -1 : 0, k1 = Lpix > 0.0 ? 1 : 0;
-    for (int k = k0; k <= k1; ++k)
+    int prev = -1;
+#pragma unroll
+    for (int k = -1; k <= 1; ++k)
     {
+        if (k != 0 && !(Lpix > 0.0)) continue;
         const double c  = f + k * Lpix;
         const double lo = fmax(ceil(c - r - 0.5 - 1e-6), 0.0), hi = fmin(floor(c + r - 0.5 + 1e-6), (double)(npix - 1));
         if (!(lo <= hi)) continue;
         const int tlo = std::max((int)lo / kTile, prev + 1), thi = (int)hi / kTile;
         if (tlo > thi) continue;
-        s.lo[s.n] = tlo, s.hi[s.n] = thi, ++s.n;
+        s.lo[k + 1] = tlo, s.hi[k + 1] = thi;
         prev = thi;
     }
 }
@@ -124,119 +125,54 @@ __device__ inline bool reach(const Plan& p, const Particles& q, uint32_t i, doub
 __device__ inline int spanTiles(const Span& s)
 {
     int n = 0;
-    for (int k = 0; k < s.n; ++k)
-        n += s.hi[k] - s.lo[k] + 1;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        n += std::max(s.hi[k] - s.lo[k] + 1, 0);
     return n;
 }
 
-/*! counts[0] += particles with a footprint, counts[2 + ty] += pairs of tile row ty.  Integer atomics: the same totals
- *  on every run. */
-__global__ __launch_bounds__(256) void countKernel(Plan p, Particles q, uint32_t first, uint32_t last,
-                                                   unsigned long long* counts)
+/*! the engine's geometry (sx_pairbin.hpp): rows are tile rows, units the tiles of one; counts[0] tallies the particles
+ *  with a footprint in the window */
+struct Geom
 {
-    __shared__ uint32_t rows[kMaxPix / kTile];
-    __shared__ uint32_t feet;
-    for (int k = threadIdx.x; k < p.nty; k += 256)
-        rows[k] = 0;
-    if (threadIdx.x == 0) feet = 0;
-    __syncthreads();
-    const uint64_t i = (uint64_t)first + (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < last)
+    static constexpr int kMaxRows = kMaxPix / kTile;
+    struct Foot
     {
-        double fu, fv, R;
-        if (reach(p, q, (uint32_t)i, fu, fv, R))
-        {
-            Span su, sv;
-            tileSpan(fu, R * p.idu, p.Lu * p.idu, p.nx, su);
-            tileSpan(fv, R * p.idv, p.Lv * p.idv, p.ny, sv);
-            const uint32_t nu = (uint32_t)spanTiles(su);
-            if (nu && sv.n)
-            {
-                atomicAdd(&feet, 1u);
-                for (int k = 0; k < sv.n; ++k)
-                    for (int ty = sv.lo[k]; ty <= sv.hi[k]; ++ty)
-                        atomicAdd(&rows[ty], nu);
-            }
-        }
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < p.nty; k += 256)
-        if (rows[k]) atomicAdd(&counts[2 + k], (unsigned long long)rows[k]);
-    if (threadIdx.x == 0 && feet) atomicAdd(&counts[0], (unsigned long long)feet);
-}
+        Span su, sv;
+    };
+    Plan      p;
+    Particles q;
 
-/*! the pairs of tile rows [r0, r1): (band-local tile) << 32 | particle, at positions taken from a cursor (one atomic
- *  per wave).  The positions differ from run to run, the set of keys does not, and the keys are distinct. */
-__global__ __launch_bounds__(256) void emitKernel(Plan p, Particles q, uint32_t first, uint32_t last, int r0, int r1,
-                                                  uint32_t* cursor, uint64_t* pairs, uint32_t capacity)
-{
-    const uint64_t i    = (uint64_t)first + (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const int      lane = threadIdx.x & 63;
-    Span           su, sv;
-    su.n = sv.n = 0;
-    uint32_t n  = 0;
-    if (i < last)
+    __host__ __device__ int      rows() const { return p.nty; }
+    __host__ __device__ uint32_t unitsPerRow() const { return (uint32_t)p.ntx; }
+
+    __device__ void foot(uint32_t i, Foot& ft) const
     {
         double fu, fv, R;
-        if (reach(p, q, (uint32_t)i, fu, fv, R))
-        {
-            tileSpan(fu, R * p.idu, p.Lu * p.idu, p.nx, su);
-            tileSpan(fv, R * p.idv, p.Lv * p.idv, p.ny, sv);
-            uint32_t rowsIn = 0;
-            for (int k = 0; k < sv.n; ++k)
-            {
-                sv.lo[k] = std::max(sv.lo[k], r0);
-                sv.hi[k] = std::min(sv.hi[k], r1 - 1);
-                if (sv.lo[k] <= sv.hi[k]) rowsIn += sv.hi[k] - sv.lo[k] + 1;
-            }
-            n = rowsIn * (uint32_t)spanTiles(su);
-        }
+        if (!reach(p, q, i, fu, fv, R)) return;
+        tileSpan(fu, R * p.idu, p.Lu * p.idu, p.nx, ft.su);
+        tileSpan(fv, R * p.idv, p.Lv * p.idv, p.ny, ft.sv);
     }
-    // exclusive scan of n over the wave, one atomic for its total (every lane takes part)
-    uint32_t incl = n;
+    __device__ bool counted(const Foot& ft) const { return spanTiles(ft.su) && spanTiles(ft.sv); }
+    template<class F>
+    __device__ void forRows(const Foot& ft, F&& f) const
+    {
+        const uint32_t nu = (uint32_t)spanTiles(ft.su);
+        if (!nu) return;
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1)
-    {
-        const uint32_t up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += up;
+        for (int k = 0; k < 3; ++k)
+            for (int ty = ft.sv.lo[k]; ty <= ft.sv.hi[k]; ++ty)
+                f(ty, nu);
     }
-    const uint32_t total = __shfl(incl, 63, 64);
-    if (total == 0) return; // wave-uniform
-    uint32_t base = 0;
-    if (lane == 63) base = atomicAdd(cursor, total);
-    base         = __shfl(base, 63, 64);
-    uint32_t pos = base + incl - n;
-    if (n == 0) return;
-    for (int kv = 0; kv < sv.n; ++kv)
-        for (int ty = sv.lo[kv]; ty <= sv.hi[kv]; ++ty)
-            for (int ku = 0; ku < su.n; ++ku)
-                for (int tx = su.lo[ku]; tx <= su.hi[ku]; ++tx)
-                {
-                    // the count pass sized the buffer from the same arithmetic; the guard keeps a disagreement in bounds
-                    if (pos < capacity) pairs[pos] = ((uint64_t)((ty - r0) * p.ntx + tx) << 32) | (uint64_t)i;
-                    ++pos;
-                }
-}
-
-//! offsets[t] = first sorted pair of band-local tile t, t in [0, tiles]; *mismatch counts the bands in which the emit
-//! pass wrote another number of pairs than the count pass announced (the buffer was filled with keys beyond every tile
-//! before, so such a band loses pairs but reads no stale one; sx_map_stats reports it)
-__global__ void offsetsKernel(const uint64_t* sorted, uint32_t num, uint32_t tiles, uint32_t* offsets,
-                              const uint32_t* cursor, unsigned long long* mismatch)
-{
-    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
-    if (t == 0 && *cursor != num) atomicAdd(mismatch, 1ull);
-    if (t > tiles) return;
-    const uint64_t key = (uint64_t)t << 32;
-    uint32_t       lo = 0, hi = num;
-    while (lo < hi)
+    template<class F>
+    __device__ void forUnits(const Foot& ft, int, F&& f) const
     {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (sorted[mid] < key) lo = mid + 1;
-        else hi = mid;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            for (int tx = ft.su.lo[k]; tx <= ft.su.hi[k]; ++tx)
+                f((uint32_t)tx);
     }
-    offsets[t] = lo;
-}
+};
 
 /*! one workgroup per tile, one pixel per lane (lane t: pixel (t & 15, t >> 4) of the tile, so wave w owns the 16 x 4
  *  block of rows 4w .. 4w + 3).  The tile's list is staged through LDS kChunk records at a time, each lane building one
@@ -340,16 +276,6 @@ Plan makePlan(const Args& a)
 
 } // namespace
 
-#define MAP_HIP(call)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t e_ = (call);                                                                                        \
-        if (e_ != hipSuccess)                                                                                          \
-        {                                                                                                              \
-            err = std::string("sx_map_render: " #call ": ") + hipGetErrorString(e_);                                   \
-            return SX_ERR_HIP;                                                                                         \
-        }                                                                                                              \
-    } while (0)
-
 int render(Arena& arena, MapBuffers& b, const Args& a, hipStream_t s, std::string& err)
 {
     if (const char* why = checkSpec(&a.spec, &a.box))
@@ -360,137 +286,14 @@ int render(Arena& arena, MapBuffers& b, const Args& a, hipStream_t s, std::strin
     const Plan      p = makePlan(a);
     const double*   xyz[3] = {a.x, a.y, a.z};
     const Particles q{xyz[(a.spec.axis + 1) % 3], xyz[(a.spec.axis + 2) % 3], xyz[a.spec.axis], a.h, a.m, a.a, a.aIsDouble};
-    const uint32_t  np = a.last - a.first;
-    const unsigned  pblocks = (np + 255) / 256;
-    constexpr int   kRows = kMaxPix / kTile;
-
-    b.counts     = arena.get<unsigned long long>("map.counts", 3 + kRows);
-    b.countsHost = arena.pinned<unsigned long long>("map.countsHost", 3 + kRows);
-    if (!b.counts || !b.countsHost)
-    {
-        err = "sx_map_render: counters";
-        return SX_ERR_NOMEM;
-    }
-    if (b.timing)
-        for (auto& e : b.ev)
-            if (!e) MAP_HIP(hipEventCreate(&e));
-    b.ms[0] = b.ms[1] = b.ms[2] = 0.0f;
-    float ms = 0.0f;
-
-    // pairs per tile row
-    if (b.timing) MAP_HIP(hipEventRecord(b.ev[0], s));
-    MAP_HIP(hipMemsetAsync(b.counts, 0, (3 + kRows) * sizeof(unsigned long long), s));
-    if (np) countKernel<<<pblocks, 256, 0, s>>>(p, q, a.first, a.last, b.counts);
-    MAP_HIP(hipGetLastError());
-    if (b.timing) MAP_HIP(hipEventRecord(b.ev[1], s));
-    MAP_HIP(hipMemcpyAsync(b.countsHost, b.counts, (2 + p.nty) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    MAP_HIP(hipStreamSynchronize(s));
-    if (b.timing && hipEventElapsedTime(&ms, b.ev[0], b.ev[1]) == hipSuccess) b.ms[0] += ms;
-
-    // bands of whole tile rows within the cap
-    const uint64_t cap = std::min(b.pairCap ? b.pairCap : kDefaultPairCap, kMaxBandPairs);
-    struct Band
-    {
-        int      r0, r1;
-        uint64_t pairs;
-    };
-    std::vector<Band> bands;
-    uint64_t          total = 0, largest = 0;
-    for (int r = 0; r < p.nty; ++r)
-    {
-        const uint64_t c = b.countsHost[2 + r];
-        if (c > kMaxBandPairs)
-        {
-            err = "sx_map_render: one tile row holds more than 2^31 - 1 pairs (render a smaller window or fewer particles at a time)";
-            return SX_ERR_ARG;
-        }
-        if (c > cap)
-        {
-            err = "sx_map_render: one tile row holds " + std::to_string(c) + " pairs, more than the pair cap of " +
-                  std::to_string(cap) + " (sx_set_map_pair_cap)";
-            return SX_ERR_ARG;
-        }
-        if (bands.empty() || bands.back().pairs + c > cap) bands.push_back(Band{r, r + 1, c});
-        else bands.back().r1 = r + 1, bands.back().pairs += c;
-        total += c;
-    }
-    for (const Band& bd : bands)
-        largest = std::max(largest, bd.pairs);
-
-    int tileBits = 1;
-    while ((1u << tileBits) < (unsigned)(p.ntx * p.nty) + 1u)
-        ++tileBits;
-    size_t tmpBytes = 0;
-    if (largest)
-        MAP_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tmpBytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)largest,
-                                                  0, 32 + tileBits, s));
-    b.pairsIn  = arena.get<uint64_t>("map.pairsIn", largest);
-    b.pairsOut = arena.get<uint64_t>("map.pairsOut", largest);
-    b.sortTmp  = arena.get<char>("map.sortTmp", tmpBytes);
-    b.offsets  = arena.get<uint32_t>("map.offsets", (size_t)p.ntx * p.nty + 1);
-    b.cursor   = arena.get<uint32_t>("map.cursor", 1);
-    if (!b.pairsIn || !b.pairsOut || !b.sortTmp || !b.offsets || !b.cursor)
-    {
-        err = "sx_map_render: pair scratch (" + std::to_string(2 * largest * 8 + tmpBytes) + " bytes)";
-        return SX_ERR_NOMEM;
-    }
-    b.scratchBytes = 2 * largest * 8 + tmpBytes + ((size_t)p.ntx * p.nty + 2) * 4 + (2 + kRows) * 8;
-
-    for (const Band& bd : bands)
-    {
+    auto gather = [&](const pairbin::Band& bd, const uint64_t* pairs, const uint32_t* offsets, unsigned long long* counts) {
         const uint32_t tiles = (uint32_t)(bd.r1 - bd.r0) * p.ntx;
-        const uint32_t num   = (uint32_t)bd.pairs;
-        if (b.timing) MAP_HIP(hipEventRecord(b.ev[0], s));
-        MAP_HIP(hipMemsetAsync(b.cursor, 0, 4, s));
-        if (num)
-        {
-            // keys beyond every tile: a slot the emit pass should leave unwritten sorts behind the last list
-            MAP_HIP(hipMemsetAsync(b.pairsIn, 0xff, (size_t)num * sizeof(uint64_t), s));
-            emitKernel<<<pblocks, 256, 0, s>>>(p, q, a.first, a.last, bd.r0, bd.r1, b.cursor, b.pairsIn, num);
-            MAP_HIP(hipGetLastError());
-        }
-        if (b.timing) MAP_HIP(hipEventRecord(b.ev[1], s));
-        if (num)
-            MAP_HIP(hipcub::DeviceRadixSort::SortKeys(b.sortTmp, tmpBytes, (const uint64_t*)b.pairsIn, b.pairsOut, (int)num, 0,
-                                                      32 + tileBits, s));
-        offsetsKernel<<<(tiles + 1 + 255) / 256, 256, 0, s>>>(b.pairsOut, num, tiles, b.offsets, b.cursor, b.counts + 2 + kRows);
-        MAP_HIP(hipGetLastError());
-        if (b.timing) MAP_HIP(hipEventRecord(b.ev[2], s));
         if (p.kind == SX_MAP_SLICE)
-            renderKernel<true><<<tiles, 256, 0, s>>>(p, q, b.pairsOut, b.offsets, bd.r0, a.last, a.sum0, a.a ? a.sum1 : nullptr, b.counts);
+            renderKernel<true><<<tiles, 256, 0, s>>>(p, q, pairs, offsets, bd.r0, a.last, a.sum0, a.a ? a.sum1 : nullptr, counts);
         else
-            renderKernel<false><<<tiles, 256, 0, s>>>(p, q, b.pairsOut, b.offsets, bd.r0, a.last, a.sum0, a.a ? a.sum1 : nullptr, b.counts);
-        MAP_HIP(hipGetLastError());
-        if (b.timing)
-        {
-            MAP_HIP(hipEventRecord(b.ev[3], s));
-            MAP_HIP(hipEventSynchronize(b.ev[3]));
-            for (int k = 0; k < 3; ++k)
-                if (hipEventElapsedTime(&ms, b.ev[k], b.ev[k + 1]) == hipSuccess) b.ms[k] += ms;
-        }
-    }
-    b.pairs    = total;
-    b.bands    = bands.size();
-    b.rendered = true;
-    return SX_OK;
-}
-
-int stats(MapBuffers& b, hipStream_t s, uint64_t out[4])
-{
-    if (!b.rendered) return SX_ERR_ARG;
-    constexpr int kRows = kMaxPix / kTile;
-    if (hipMemcpyAsync(b.countsHost, b.counts, (3 + kRows) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return SX_ERR_HIP;
-    if (b.countsHost[2 + kRows]) return kStatsMismatch;
-    out[0] = b.pairs, out[1] = b.bands, out[2] = b.countsHost[1], out[3] = b.countsHost[0];
-    return SX_OK;
-}
-
-void release(MapBuffers& b)
-{
-    for (auto& e : b.ev)
-        if (e) (void)hipEventDestroy(e), e = nullptr;
+            renderKernel<false><<<tiles, 256, 0, s>>>(p, q, pairs, offsets, bd.r0, a.last, a.sum0, a.a ? a.sum1 : nullptr, counts);
+    };
+    return pairbin::run(arena, b.bin, kNames, Geom{p, q}, a.first, a.last, gather, s, err);
 }
 
 } // namespace sx::map

@@ -1026,8 +1026,8 @@ extern "C"
         if (s->evAuxOut) (void)hipEventDestroy(s->evAuxOut);
         if (s->auxStream) (void)hipStreamDestroy(s->auxStream);
         turbDestroy(s->turb);
-        sx::map::release(s->mapBuf);
-        sx::spectrum::release(s->specBuf);
+        sx::pairbin::release(s->mapBuf.bin);
+        sx::pairbin::release(s->specBuf.bin);
         sx::profile::release(s->profBuf);
         delete s;
     }
@@ -1350,113 +1350,6 @@ extern "C"
     {
         if (!s) return SX_ERR_ARG;
         s->iteration = iteration;
-        return SX_OK;
-    }
-
-    int sx_sim_set_map_pair_cap(sx_sim* s, uint64_t pairs)
-    {
-        if (!s) return SX_ERR_ARG;
-        s->mapBuf.pairCap = pairs;
-        return SX_OK;
-    }
-
-    int sx_sim_map_stats(sx_sim* s, uint64_t out[4])
-    {
-        if (!s || !out) return SX_ERR_ARG;
-        const int rc = sx::map::stats(s->mapBuf, (hipStream_t)sx_ctx_stream_internal(s->ctx), out);
-        if (rc == SX_ERR_ARG) sx_ctx_set_error_internal(s->ctx, "sx_sim_map_stats: nothing has been rendered");
-        if (rc == sx::map::kStatsMismatch)
-        {
-            sx_ctx_set_error_internal(s->ctx, (std::string("sx_sim_map_stats: ") + sx::map::kStatsMismatchText).c_str());
-            return SX_ERR_HIP;
-        }
-        return rc;
-    }
-
-    int sx_sim_render(sx_sim* s, const sx_map* map, int field, double* hostSum0, double* hostSum1)
-    {
-        if (!s || !map || !hostSum0) return SX_ERR_ARG;
-        // the column a: {pointer, is double}; a field the propagator's layout does not keep is a null pointer
-        const void* a        = nullptr;
-        int         aDouble  = 0;
-        const char* name     = nullptr;
-        switch (field)
-        {
-            case SX_MAP_FIELD_NONE: break;
-            case SX_MAP_FIELD_TEMP: a = s->temp, aDouble = 1, name = "temp"; break;
-            case SX_MAP_FIELD_P: a = s->pres, name = "p"; break;
-            case SX_MAP_FIELD_C: a = s->c, name = "c"; break;
-            case SX_MAP_FIELD_VX: a = s->vx, name = "vx"; break;
-            case SX_MAP_FIELD_VY: a = s->vy, name = "vy"; break;
-            case SX_MAP_FIELD_VZ: a = s->vz, name = "vz"; break;
-            case SX_MAP_FIELD_DIVV: a = s->divv, name = "divv"; break;
-            case SX_MAP_FIELD_CURLV: a = s->curlv, name = "curlv"; break;
-            case SX_MAP_FIELD_ALPHA: a = s->alpha, name = "alpha"; break;
-            case SX_MAP_FIELD_H: a = s->h, name = "h"; break;
-            default: sx_ctx_set_error_internal(s->ctx, "sx_sim_render: unknown field"); return SX_ERR_ARG;
-        }
-        if (field != SX_MAP_FIELD_NONE && !a)
-        {
-            const std::string why =
-                std::string("sx_sim_render: the field ") + name + " is not kept by " +
-                (s->p.propagator == 3 ? "the gravity-only propagator (none, vx, vy, vz and h are supported)"
-                                      : "this propagator (p exists under the std propagator only: VE keeps p / rho)");
-            sx_ctx_set_error_internal(s->ctx, why.c_str());
-            return SX_ERR_ARG;
-        }
-        if (a && !hostSum1)
-        {
-            sx_ctx_set_error_internal(s->ctx, "sx_sim_render: a field needs hostSum1");
-            return SX_ERR_ARG;
-        }
-        if (const char* why = sx::map::checkSpec(map, &s->box))
-        {
-            sx_ctx_set_error_internal(s->ctx, why);
-            return SX_ERR_ARG;
-        }
-        hipStream_t  st   = (hipStream_t)sx_ctx_stream_internal(s->ctx);
-        const size_t npix = (size_t)map->npix[0] * map->npix[1];
-        const bool   dist = s->comm && s->comm->size() > 1;
-        // [refusals | sum0 | sum1]: the word in front travels with the images through the one reduction, so a rank whose
-        // render was refused (a tile row of ITS particles above the pair cap, no memory for ITS pairs) still takes part
-        // and every rank learns of it
-        s->mapBuf.img     = s->work.get<double>("map.img", 2 * npix + 1);
-        s->mapBuf.imgHost = s->work.pinned<double>("map.imgHost", 2 * npix + 1);
-        if (!s->mapBuf.img || !s->mapBuf.imgHost)
-        {
-            sx_ctx_set_error_internal(s->ctx, "sx_sim_render: image buffers");
-            return SX_ERR_NOMEM;
-        }
-        double *      d0 = s->mapBuf.img + 1, *d1 = d0 + npix;
-        sx::map::Args args{*map, s->box, s->x, s->y, s->z, s->h, s->m, a, aDouble, (uint32_t)s->first, (uint32_t)s->last,
-                           s->p.K, d0, d1};
-        std::string   err;
-        const int     rc = sx::map::render(s->work, s->mapBuf, args, st, err);
-        if (rc != SX_OK)
-        {
-            sx_ctx_set_error_internal(s->ctx, err.c_str());
-            if (!dist) return rc;
-        }
-        const size_t count = 1 + (a ? 2 * npix : npix);
-        if (dist)
-        {
-            // the images and the refusal count are adjacent: one f64 sum over the ranks serves all of it
-            const double refused = rc != SX_OK ? 1.0 : 0.0;
-            if (rc != SX_OK) SIM_HIP(hipMemsetAsync(s->mapBuf.img, 0, count * sizeof(double), st));
-            SIM_HIP(hipMemcpyAsync(s->mapBuf.img, &refused, sizeof(double), hipMemcpyHostToDevice, st));
-            SIM_COMM(s->comm->allreduceSumF64(s->mapBuf.img, count, st));
-        }
-        // through pinned memory: a copy into the caller's pageable arrays runs at a tenth of the link's rate
-        SIM_HIP(hipMemcpyAsync(s->mapBuf.imgHost, s->mapBuf.img, count * sizeof(double), hipMemcpyDeviceToHost, st));
-        SIM_HIP(hipStreamSynchronize(st));
-        if (rc != SX_OK) return rc;
-        if (dist && s->mapBuf.imgHost[0] != 0.0)
-        {
-            sx_ctx_set_error_internal(s->ctx, "sx_sim_render: refused on another rank (its sx_last_error has the reason)");
-            return SX_ERR_ARG;
-        }
-        std::memcpy(hostSum0, s->mapBuf.imgHost + 1, npix * sizeof(double));
-        if (a) std::memcpy(hostSum1, s->mapBuf.imgHost + 1 + npix, npix * sizeof(double));
         return SX_OK;
     }
 

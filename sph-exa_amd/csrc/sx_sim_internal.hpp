@@ -1,7 +1,8 @@
 /*! @file sx_sim_internal.hpp
  * @brief what the translation units of the step driver share beyond sx_sim.hpp: sx_sim.cpp (C API, step orchestrator),
  *        sx_sim_domain.cpp (SFC domain), sx_sim_gravity.cpp (self-gravity), sx_sim_skin.cpp (skin-list driver),
- *        sx_sim_nbody.cpp (gravity-only step), sx_bdt.cpp (ve-bdt substeps).  simFields is the one place that lists
+ *        sx_sim_nbody.cpp (gravity-only step), sx_bdt.cpp (ve-bdt substeps), and the analysis passes over the current
+ *        state (sx_sim_map.cpp, sx_sim_spectrum.cpp, sx_sim_profile.cpp).  simFields is the one place that lists
  *        the sim's arrays as a field view; kernel arguments are built from that view (sx_args.hpp).  Step times go
  *        through s->timer (sx_step_timer.hpp): marks by stage and kernel name, one collect() at the end of the step.
  */
@@ -87,6 +88,40 @@ inline sx_fields simFields(const sx_sim* s, size_t offset = 0)
     f.dV11 = at(s->dV[0]), f.dV12 = at(s->dV[1]), f.dV13 = at(s->dV[2]);
     f.dV22 = at(s->dV[3]), f.dV23 = at(s->dV[4]), f.dV33 = at(s->dV[5]);
     return f;
+}
+
+//! an SX_MAP_FIELD_* column of the sim (a null for SX_MAP_FIELD_NONE)
+struct MapField
+{
+    const void* a{nullptr};
+    int         isDouble{0};
+    const char* name{nullptr};
+};
+
+/*! the column `field` for sx_sim_render and sx_sim_spectrum.  False, with the refusal in `why` behind the caller's name
+ *  fn, for an unknown value and for a field the propagator's layout does not keep (a null pointer). */
+inline bool mapField(const sx_sim* s, int field, const char* fn, MapField& f, std::string& why)
+{
+    switch (field)
+    {
+        case SX_MAP_FIELD_NONE: return true;
+        case SX_MAP_FIELD_TEMP: f = {s->temp, 1, "temp"}; break;
+        case SX_MAP_FIELD_P: f = {s->pres, 0, "p"}; break;
+        case SX_MAP_FIELD_C: f = {s->c, 0, "c"}; break;
+        case SX_MAP_FIELD_VX: f = {s->vx, 0, "vx"}; break;
+        case SX_MAP_FIELD_VY: f = {s->vy, 0, "vy"}; break;
+        case SX_MAP_FIELD_VZ: f = {s->vz, 0, "vz"}; break;
+        case SX_MAP_FIELD_DIVV: f = {s->divv, 0, "divv"}; break;
+        case SX_MAP_FIELD_CURLV: f = {s->curlv, 0, "curlv"}; break;
+        case SX_MAP_FIELD_ALPHA: f = {s->alpha, 0, "alpha"}; break;
+        case SX_MAP_FIELD_H: f = {s->h, 0, "h"}; break;
+        default: why = std::string(fn) + ": unknown field"; return false;
+    }
+    if (f.a) return true;
+    why = std::string(fn) + ": the field " + f.name + " is not kept by " +
+          (s->p.propagator == 3 ? "the gravity-only propagator (none, vx, vy, vz and h are supported)"
+                                : "this propagator (p exists under the std propagator only: VE keeps p / rho)");
+    return false;
 }
 
 // ---- sx_sim.cpp ---------------------------------------------------------------------------------------------------

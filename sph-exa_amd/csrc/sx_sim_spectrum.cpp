@@ -1,7 +1,8 @@
 /*! @file sx_sim_spectrum.cpp
  * @brief sx_sim_spectrum: the power spectrum of the current state over all ranks (sx_spectrum.hpp).  Each rank deposits
  *        its locals, one f64-sum reduction runs over the meshes, every rank transforms and sums redundantly.  The arena
- *        tags ("spec.*") are requested in sx_spectrum.hip, each at one site, and kept in s->specBuf.
+ *        tags ("spec.*") are requested in sx_spectrum.hip and, for the pair scratch, by the pair-binning engine
+ *        (sx_pairbin.hip), each at one site, and kept in s->specBuf.
  */
 #include "sx_sim_internal.hpp"
 
@@ -10,20 +11,17 @@ extern "C"
     int sx_sim_set_spectrum_pair_cap(sx_sim* s, uint64_t pairs)
     {
         if (!s) return SX_ERR_ARG;
-        s->specBuf.pairCap = pairs;
+        s->specBuf.bin.pairCap = pairs;
         return SX_OK;
     }
 
     int sx_sim_spectrum_stats(sx_sim* s, uint64_t out[4])
     {
         if (!s || !out) return SX_ERR_ARG;
-        const int rc = sx::spectrum::stats(s->specBuf, (hipStream_t)sx_ctx_stream_internal(s->ctx), out);
-        if (rc == SX_ERR_ARG) sx_ctx_set_error_internal(s->ctx, "sx_sim_spectrum_stats: nothing has been deposited");
-        if (rc == sx::spectrum::kStatsMismatch)
-        {
-            sx_ctx_set_error_internal(s->ctx, (std::string("sx_sim_spectrum_stats: ") + sx::spectrum::kStatsMismatchText).c_str());
-            return SX_ERR_HIP;
-        }
+        std::string why;
+        const int   rc = sx::pairbin::statsCode(sx::pairbin::stats(s->specBuf.bin, (hipStream_t)sx_ctx_stream_internal(s->ctx), out),
+                                                "sx_sim_spectrum_stats", sx::spectrum::kNames, why);
+        if (rc != SX_OK) sx_ctx_set_error_internal(s->ctx, why.c_str());
         return rc;
     }
 
@@ -44,34 +42,14 @@ extern "C"
         }
         else
         {
-            // the column: {pointer, is double}; a field the propagator's layout does not keep is a null pointer
-            const void* a    = nullptr;
-            const char* name = nullptr;
-            switch (field)
+            sx::sim::MapField f;
+            std::string       why;
+            if (!sx::sim::mapField(s, field, "sx_sim_spectrum", f, why))
             {
-                case SX_MAP_FIELD_NONE: break;
-                case SX_MAP_FIELD_TEMP: a = s->temp, args.aIsDouble = 1, name = "temp"; break;
-                case SX_MAP_FIELD_P: a = s->pres, name = "p"; break;
-                case SX_MAP_FIELD_C: a = s->c, name = "c"; break;
-                case SX_MAP_FIELD_VX: a = s->vx, name = "vx"; break;
-                case SX_MAP_FIELD_VY: a = s->vy, name = "vy"; break;
-                case SX_MAP_FIELD_VZ: a = s->vz, name = "vz"; break;
-                case SX_MAP_FIELD_DIVV: a = s->divv, name = "divv"; break;
-                case SX_MAP_FIELD_CURLV: a = s->curlv, name = "curlv"; break;
-                case SX_MAP_FIELD_ALPHA: a = s->alpha, name = "alpha"; break;
-                case SX_MAP_FIELD_H: a = s->h, name = "h"; break;
-                default: sx_ctx_set_error_internal(s->ctx, "sx_sim_spectrum: unknown field"); return SX_ERR_ARG;
-            }
-            if (field != SX_MAP_FIELD_NONE && !a)
-            {
-                const std::string why =
-                    std::string("sx_sim_spectrum: the field ") + name + " is not kept by " +
-                    (s->p.propagator == 3 ? "the gravity-only propagator (none, vx, vy, vz and h are supported)"
-                                          : "this propagator (p exists under the std propagator only: VE keeps p / rho)");
                 sx_ctx_set_error_internal(s->ctx, why.c_str());
                 return SX_ERR_ARG;
             }
-            if (a) args.numA = 1, args.a[0] = a;
+            if (f.a) args.numA = 1, args.a[0] = f.a, args.aIsDouble = f.isDouble;
         }
         hipStream_t st   = (hipStream_t)sx_ctx_stream_internal(s->ctx);
         const bool  dist = s->comm && s->comm->size() > 1;

@@ -1,6 +1,7 @@
 /*! @file sx_spectrum.hip
- * @brief Power spectra (sx_spectrum.hpp): the mesh deposit (binning into blocks of 8 x 8 x 4 cells, a radix sort of the
- *        (block, particle) pairs, one workgroup per block that gathers its list through LDS in list order), the field
+ * @brief Power spectra (sx_spectrum.hpp): the mesh deposit (binning into blocks of 8 x 8 x 4 cells and a radix sort of
+ *        the (block, particle) pairs, both the pair-binning engine's (sx_pairbin.hpp), then one workgroup per block that
+ *        gathers its list through LDS in list order), the field
  *        that is transformed, and the deterministic shell sums.  The transform itself is in sx_fft.hip.
  *
  * Geometry of the deposit, in cell units from the box corner: cell i has its centre at i + 0.5 and a particle at f with
@@ -12,8 +13,6 @@
  * minimum-image distance then too.  The kernel value is exactly 0 beyond the support (kernelWt), so the binning and the
  * cull may be conservative without changing a bit of the mesh.
  */
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -146,113 +145,49 @@ __device__ inline void place(const Plan& p, const Particles& q, uint32_t i, doub
     r              = 2.0 * fmax(h, p.hmin) * p.iD;
 }
 
-/*! counts[0] += particles clamped to D / 2, counts[2 + bz] += pairs of block layer bz.  Integer atomics: the same totals
- *  on every run. */
-__global__ __launch_bounds__(256) void countKernel(Plan p, Particles q, uint32_t first, uint32_t last,
-                                                   unsigned long long* counts)
+/*! the engine's geometry (sx_pairbin.hpp): rows are block layers along z, units the blocks of one; counts[0] tallies the
+ *  particles clamped to D / 2, whatever they touch */
+struct Geom
 {
-    __shared__ uint32_t layers[kMaxLayers];
-    __shared__ uint32_t clampedSum;
-    for (int k = threadIdx.x; k < kMaxLayers; k += 256)
-        layers[k] = 0;
-    if (threadIdx.x == 0) clampedSum = 0;
-    __syncthreads();
-    const uint64_t i = (uint64_t)first + (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < last)
+    static constexpr int kMaxRows = kMaxLayers;
+    struct Foot
+    {
+        Span sx{0, 0}, sy{0, 0}, sz{0, 0};
+        bool clamped{false};
+    };
+    Plan      p;
+    Particles q;
+
+    __host__ __device__ int      rows() const { return p.nbz; }
+    __host__ __device__ uint32_t unitsPerRow() const { return (uint32_t)(p.nbx * p.nby); }
+
+    __device__ void foot(uint32_t i, Foot& ft) const
     {
         double f[3], r;
-        bool   clamped;
-        place(p, q, (uint32_t)i, f, r, clamped);
-        const Span sx = blockSpan(f[0], r, p.n, kBx, p.nbx), sy = blockSpan(f[1], r, p.n, kBy, p.nby),
-                   sz = blockSpan(f[2], r, p.n, kBz, p.nbz);
-        if (clamped) atomicAdd(&clampedSum, 1u);
-        const uint32_t per = (uint32_t)(sx.count * sy.count);
-        if (per)
-            for (int k = 0; k < sz.count; ++k)
-                atomicAdd(&layers[(sz.start + k) % p.nbz], per);
+        place(p, q, i, f, r, ft.clamped);
+        ft.sx = blockSpan(f[0], r, p.n, kBx, p.nbx), ft.sy = blockSpan(f[1], r, p.n, kBy, p.nby);
+        ft.sz = blockSpan(f[2], r, p.n, kBz, p.nbz);
     }
-    __syncthreads();
-    for (int k = threadIdx.x; k < p.nbz; k += 256)
-        if (layers[k]) atomicAdd(&counts[2 + k], (unsigned long long)layers[k]);
-    if (threadIdx.x == 0 && clampedSum) atomicAdd(&counts[0], (unsigned long long)clampedSum);
-}
-
-/*! the pairs of block layers [r0, r1): (band-local block) << 32 | particle, at positions taken from a cursor (one atomic
- *  per wave).  The positions differ from run to run, the set of keys does not, and the keys are distinct. */
-__global__ __launch_bounds__(256) void emitKernel(Plan p, Particles q, uint32_t first, uint32_t last, int r0, int r1,
-                                                  uint32_t* cursor, uint64_t* pairs, uint32_t capacity)
-{
-    const uint64_t i    = (uint64_t)first + (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const int      lane = threadIdx.x & 63;
-    Span           sx{0, 0}, sy{0, 0}, sz{0, 0};
-    uint32_t       n = 0;
-    if (i < last)
+    __device__ bool counted(const Foot& ft) const { return ft.clamped; }
+    template<class F>
+    __device__ void forRows(const Foot& ft, F&& f) const
     {
-        double f[3], r;
-        bool   clamped;
-        place(p, q, (uint32_t)i, f, r, clamped);
-        sx = blockSpan(f[0], r, p.n, kBx, p.nbx), sy = blockSpan(f[1], r, p.n, kBy, p.nby);
-        sz = blockSpan(f[2], r, p.n, kBz, p.nbz);
-        uint32_t inBand = 0;
-        for (int k = 0; k < sz.count; ++k)
+        const uint32_t per = (uint32_t)(ft.sx.count * ft.sy.count);
+        if (!per) return;
+        for (int k = 0; k < ft.sz.count; ++k)
+            f((ft.sz.start + k) % p.nbz, per);
+    }
+    template<class F>
+    __device__ void forUnits(const Foot& ft, int, F&& f) const
+    {
+        for (int ky = 0; ky < ft.sy.count; ++ky)
         {
-            const int bz = (sz.start + k) % p.nbz;
-            inBand += (bz >= r0 && bz < r1) ? 1u : 0u;
-        }
-        n = inBand * (uint32_t)(sx.count * sy.count);
-    }
-    // exclusive scan of n over the wave, one atomic for its total (every lane takes part)
-    uint32_t incl = n;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1)
-    {
-        const uint32_t up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += up;
-    }
-    const uint32_t total = __shfl(incl, 63, 64);
-    if (total == 0) return; // wave-uniform
-    uint32_t base = 0;
-    if (lane == 63) base = atomicAdd(cursor, total);
-    base         = __shfl(base, 63, 64);
-    uint32_t pos = base + incl - n;
-    if (n == 0) return;
-    for (int kz = 0; kz < sz.count; ++kz)
-    {
-        const int bz = (sz.start + kz) % p.nbz;
-        if (bz < r0 || bz >= r1) continue;
-        for (int ky = 0; ky < sy.count; ++ky)
-        {
-            const int by = (sy.start + ky) % p.nby;
-            for (int kx = 0; kx < sx.count; ++kx)
-            {
-                const int bx = (sx.start + kx) % p.nbx;
-                // the count pass sized the buffer from the same arithmetic; the guard keeps a disagreement in bounds
-                if (pos < capacity) pairs[pos] = ((uint64_t)(((bz - r0) * p.nby + by) * p.nbx + bx) << 32) | (uint64_t)i;
-                ++pos;
-            }
+            const int by = (ft.sy.start + ky) % p.nby;
+            for (int kx = 0; kx < ft.sx.count; ++kx)
+                f((uint32_t)(by * p.nbx + (ft.sx.start + kx) % p.nbx));
         }
     }
-}
-
-//! offsets[t] = first sorted pair of band-local block t, t in [0, blocks]; *mismatch counts the bands in which the emit
-//! pass wrote another number of pairs than the count pass announced (the buffer was filled with keys beyond every block
-//! before, so such a band loses pairs but reads no stale one; sx_spectrum_stats reports it)
-__global__ void offsetsKernel(const uint64_t* sorted, uint32_t num, uint32_t blocks, uint32_t* offsets,
-                              const uint32_t* cursor, unsigned long long* mismatch)
-{
-    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
-    if (t == 0 && *cursor != num) atomicAdd(mismatch, 1ull);
-    if (t > blocks) return;
-    const uint64_t key = (uint64_t)t << 32;
-    uint32_t       lo = 0, hi = num;
-    while (lo < hi)
-    {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (sorted[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    offsets[t] = lo;
-}
+};
 
 /*! one workgroup per block, one cell per lane (lane t: cell (t & 7, (t >> 3) & 7, t >> 6) of the block, so wave w owns
  *  the 8 x 8 layer z = w).  The block's list is staged through LDS kChunk records at a time, each lane building one
@@ -430,14 +365,6 @@ bool reserveOut(Arena& arena, SpecBuffers& b)
         }                                                                                                              \
     } while (0)
 
-static int ensureEvents(SpecBuffers& b, std::string& err)
-{
-    if (b.timing)
-        for (auto& e : b.ev)
-            if (!e) SPEC_HIP(hipEventCreate(&e));
-    return SX_OK;
-}
-
 int deposit(Arena& arena, SpecBuffers& b, const DepositArgs& a, hipStream_t s, std::string& err)
 {
     if (!validN(a.n))
@@ -456,127 +383,21 @@ int deposit(Arena& arena, SpecBuffers& b, const DepositArgs& a, hipStream_t s, s
         err = "sx_mesh_deposit: numA must be 0 .. 3";
         return SX_ERR_ARG;
     }
-    const Plan     p = makePlan(a);
-    Particles      q{a.x, a.y, a.z, a.h, a.m, {a.a[0], a.a[1], a.a[2]}, a.numA, a.aIsDouble};
-    const uint32_t np      = a.last - a.first;
-    const unsigned pblocks = (np + 255) / 256;
-    constexpr int  kCounts = 3 + kMaxLayers;
-
-    b.counts     = arena.get<unsigned long long>("spec.counts", kCounts);
-    b.countsHost = arena.pinned<unsigned long long>("spec.countsHost", kCounts);
-    if (!b.counts || !b.countsHost)
-    {
-        err = "sx_mesh_deposit: counters";
-        return SX_ERR_NOMEM;
-    }
-    if (int rc = ensureEvents(b, err)) return rc;
-    for (float& v : b.ms)
-        v = 0.0f;
-    float ms = 0.0f;
-
-    // pairs per block layer
-    if (b.timing) SPEC_HIP(hipEventRecord(b.ev[0], s));
-    SPEC_HIP(hipMemsetAsync(b.counts, 0, kCounts * sizeof(unsigned long long), s));
-    if (np) countKernel<<<pblocks, 256, 0, s>>>(p, q, a.first, a.last, b.counts);
-    SPEC_HIP(hipGetLastError());
-    if (b.timing) SPEC_HIP(hipEventRecord(b.ev[1], s));
-    SPEC_HIP(hipMemcpyAsync(b.countsHost, b.counts, (2 + p.nbz) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    SPEC_HIP(hipStreamSynchronize(s));
-    if (b.timing && hipEventElapsedTime(&ms, b.ev[0], b.ev[1]) == hipSuccess) b.ms[0] += ms;
-
-    // bands of whole block layers within the cap
-    const uint64_t cap = std::min(b.pairCap ? b.pairCap : kDefaultPairCap, kMaxBandPairs);
-    struct Band
-    {
-        int      r0, r1;
-        uint64_t pairs;
-    };
-    std::vector<Band> bands;
-    uint64_t          total = 0, largest = 0;
-    for (int r = 0; r < p.nbz; ++r)
-    {
-        const uint64_t c = b.countsHost[2 + r];
-        if (c > kMaxBandPairs)
-        {
-            err = "sx_mesh_deposit: one block layer holds more than 2^31 - 1 pairs (deposit fewer particles at a time)";
-            return SX_ERR_ARG;
-        }
-        if (c > cap)
-        {
-            err = "sx_mesh_deposit: one block layer holds " + std::to_string(c) + " pairs, more than the pair cap of " +
-                  std::to_string(cap) + " (sx_set_spectrum_pair_cap)";
-            return SX_ERR_ARG;
-        }
-        if (bands.empty() || bands.back().pairs + c > cap) bands.push_back(Band{r, r + 1, c});
-        else bands.back().r1 = r + 1, bands.back().pairs += c;
-        total += c;
-    }
-    for (const Band& bd : bands)
-        largest = std::max(largest, bd.pairs);
-
-    const uint32_t perLayer  = (uint32_t)(p.nbx * p.nby);
-    const uint32_t allBlocks = perLayer * p.nbz;
-    int            blockBits = 1;
-    while ((1u << blockBits) < allBlocks + 1u)
-        ++blockBits;
-    size_t tmpBytes = 0;
-    if (largest)
-        SPEC_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tmpBytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                                   (int)largest, 0, 32 + blockBits, s));
-    b.pairsIn  = arena.get<uint64_t>("spec.pairsIn", largest);
-    b.pairsOut = arena.get<uint64_t>("spec.pairsOut", largest);
-    b.sortTmp  = arena.get<char>("spec.sortTmp", tmpBytes);
-    b.offsets  = arena.get<uint32_t>("spec.offsets", (size_t)allBlocks + 1);
-    b.cursor   = arena.get<uint32_t>("spec.cursor", 1);
-    if (!b.pairsIn || !b.pairsOut || !b.sortTmp || !b.offsets || !b.cursor)
-    {
-        err = "sx_mesh_deposit: pair scratch (" + std::to_string(2 * largest * 8 + tmpBytes) + " bytes)";
-        return SX_ERR_NOMEM;
-    }
-    b.scratchBytes = 2 * largest * 8 + tmpBytes + ((size_t)allBlocks + 2) * 4 + kCounts * 8;
-
-    for (const Band& bd : bands)
-    {
-        const uint32_t blocks = (uint32_t)(bd.r1 - bd.r0) * perLayer;
-        const uint32_t num    = (uint32_t)bd.pairs;
-        if (b.timing) SPEC_HIP(hipEventRecord(b.ev[0], s));
-        SPEC_HIP(hipMemsetAsync(b.cursor, 0, 4, s));
-        if (num)
-        {
-            // keys beyond every block: a slot the emit pass should leave unwritten sorts behind the last list
-            SPEC_HIP(hipMemsetAsync(b.pairsIn, 0xff, (size_t)num * sizeof(uint64_t), s));
-            emitKernel<<<pblocks, 256, 0, s>>>(p, q, a.first, a.last, bd.r0, bd.r1, b.cursor, b.pairsIn, num);
-            SPEC_HIP(hipGetLastError());
-        }
-        if (b.timing) SPEC_HIP(hipEventRecord(b.ev[1], s));
-        if (num)
-            SPEC_HIP(hipcub::DeviceRadixSort::SortKeys(b.sortTmp, tmpBytes, (const uint64_t*)b.pairsIn, b.pairsOut, (int)num,
-                                                       0, 32 + blockBits, s));
-        offsetsKernel<<<(blocks + 1 + 255) / 256, 256, 0, s>>>(b.pairsOut, num, blocks, b.offsets, b.cursor,
-                                                               b.counts + 2 + kMaxLayers);
-        SPEC_HIP(hipGetLastError());
-        if (b.timing) SPEC_HIP(hipEventRecord(b.ev[2], s));
+    const Plan      p = makePlan(a);
+    const Particles q{a.x, a.y, a.z, a.h, a.m, {a.a[0], a.a[1], a.a[2]}, a.numA, a.aIsDouble};
+    b.msFft = b.msShells = 0.0f;
+    auto gather = [&](const pairbin::Band& bd, const uint64_t* pairs, const uint32_t* offsets, unsigned long long* counts) {
+        const uint32_t blocks = (uint32_t)(bd.r1 - bd.r0) * p.nbx * p.nby;
         // a block without pairs reads no particle: last - 1 is never formed for an empty range
         switch (a.numA)
         {
-            case 0: gatherKernel<0><<<blocks, 256, 0, s>>>(p, q, b.pairsOut, b.offsets, bd.r0, a.last, a.sum0, a.sum1, b.counts); break;
-            case 1: gatherKernel<1><<<blocks, 256, 0, s>>>(p, q, b.pairsOut, b.offsets, bd.r0, a.last, a.sum0, a.sum1, b.counts); break;
-            case 2: gatherKernel<2><<<blocks, 256, 0, s>>>(p, q, b.pairsOut, b.offsets, bd.r0, a.last, a.sum0, a.sum1, b.counts); break;
-            default: gatherKernel<3><<<blocks, 256, 0, s>>>(p, q, b.pairsOut, b.offsets, bd.r0, a.last, a.sum0, a.sum1, b.counts); break;
+            case 0: gatherKernel<0><<<blocks, 256, 0, s>>>(p, q, pairs, offsets, bd.r0, a.last, a.sum0, a.sum1, counts); break;
+            case 1: gatherKernel<1><<<blocks, 256, 0, s>>>(p, q, pairs, offsets, bd.r0, a.last, a.sum0, a.sum1, counts); break;
+            case 2: gatherKernel<2><<<blocks, 256, 0, s>>>(p, q, pairs, offsets, bd.r0, a.last, a.sum0, a.sum1, counts); break;
+            default: gatherKernel<3><<<blocks, 256, 0, s>>>(p, q, pairs, offsets, bd.r0, a.last, a.sum0, a.sum1, counts); break;
         }
-        SPEC_HIP(hipGetLastError());
-        if (b.timing)
-        {
-            SPEC_HIP(hipEventRecord(b.ev[3], s));
-            SPEC_HIP(hipEventSynchronize(b.ev[3]));
-            for (int k = 0; k < 3; ++k)
-                if (hipEventElapsedTime(&ms, b.ev[k], b.ev[k + 1]) == hipSuccess) b.ms[k] += ms;
-        }
-    }
-    b.pairs     = total;
-    b.bands     = bands.size();
-    b.deposited = true;
-    return SX_OK;
+    };
+    return pairbin::run(arena, b.bin, kNames, Geom{p, q}, a.first, a.last, gather, s, err);
 }
 
 int fft3d(Arena& arena, SpecBuffers& b, double* complexMesh, uint32_t n, hipStream_t s, std::string& err)
@@ -605,15 +426,15 @@ int fft3d(Arena& arena, SpecBuffers& b, double* complexMesh, uint32_t n, hipStre
         SPEC_HIP(hipMemcpy(b.twiddle, t.data(), n * sizeof(double2), hipMemcpyHostToDevice));
         b.twiddleN = n;
     }
-    if (int rc = ensureEvents(b, err)) return rc;
-    if (b.timing) SPEC_HIP(hipEventRecord(b.ev[0], s));
+    SPEC_HIP(pairbin::ensureEvents(b.bin));
+    if (b.bin.timing) SPEC_HIP(hipEventRecord(b.bin.ev[0], s));
     SPEC_HIP(fftLaunch(reinterpret_cast<double2*>(complexMesh), n, b.twiddle, s));
-    if (b.timing)
+    if (b.bin.timing)
     {
         float ms = 0.0f;
-        SPEC_HIP(hipEventRecord(b.ev[1], s));
-        SPEC_HIP(hipEventSynchronize(b.ev[1]));
-        if (hipEventElapsedTime(&ms, b.ev[0], b.ev[1]) == hipSuccess) b.ms[3] += ms;
+        SPEC_HIP(hipEventRecord(b.bin.ev[1], s));
+        SPEC_HIP(hipEventSynchronize(b.bin.ev[1]));
+        if (hipEventElapsedTime(&ms, b.bin.ev[0], b.bin.ev[1]) == hipSuccess) b.msFft += ms;
     }
     return SX_OK;
 }
@@ -693,18 +514,18 @@ int shellSums(Arena& arena, SpecBuffers& b, const double* complexMesh, uint32_t 
         return SX_ERR_ARG;
     }
     if (int rc = ensurePerm(arena, b, n, s, err)) return rc;
-    if (int rc = ensureEvents(b, err)) return rc;
+    SPEC_HIP(pairbin::ensureEvents(b.bin));
     const uint32_t ns = numShells(n);
-    if (b.timing) SPEC_HIP(hipEventRecord(b.ev[0], s));
+    if (b.bin.timing) SPEC_HIP(hipEventRecord(b.bin.ev[0], s));
     leafKernel<<<b.numLeaves, 256, 0, s>>>(reinterpret_cast<const double2*>(complexMesh), b.perm, b.leafBeg, b.leafSum);
     shellKernel<<<(ns + 63) / 64, 64, 0, s>>>(b.leafSum, b.shellLeaf, b.shellBeg, ns, prefactor, accumulate, power, modes);
     SPEC_HIP(hipGetLastError());
-    if (b.timing)
+    if (b.bin.timing)
     {
         float ms = 0.0f;
-        SPEC_HIP(hipEventRecord(b.ev[1], s));
-        SPEC_HIP(hipEventSynchronize(b.ev[1]));
-        if (hipEventElapsedTime(&ms, b.ev[0], b.ev[1]) == hipSuccess) b.ms[4] += ms;
+        SPEC_HIP(hipEventRecord(b.bin.ev[1], s));
+        SPEC_HIP(hipEventSynchronize(b.bin.ev[1]));
+        if (hipEventElapsedTime(&ms, b.bin.ev[0], b.bin.ev[1]) == hipSuccess) b.msShells += ms;
     }
     return SX_OK;
 }
@@ -779,24 +600,6 @@ int compute(Arena& arena, SpecBuffers& b, const sx_spectrum& sp, DepositArgs a, 
     }
     SPEC_HIP(hipStreamSynchronize(s));
     return SX_OK;
-}
-
-int stats(SpecBuffers& b, hipStream_t s, uint64_t out[4])
-{
-    if (!b.deposited) return SX_ERR_ARG;
-    constexpr int kCounts = 3 + kMaxLayers;
-    if (hipMemcpyAsync(b.countsHost, b.counts, kCounts * sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return SX_ERR_HIP;
-    if (b.countsHost[2 + kMaxLayers]) return kStatsMismatch;
-    out[0] = b.pairs, out[1] = b.bands, out[2] = b.countsHost[1], out[3] = b.countsHost[0];
-    return SX_OK;
-}
-
-void release(SpecBuffers& b)
-{
-    for (auto& e : b.ev)
-        if (e) (void)hipEventDestroy(e), e = nullptr;
 }
 
 } // namespace sx::spectrum

@@ -10,8 +10,9 @@
  * further sums S1_a(c) = sum_j w_jc a_j use the same weights, for three device columns a (float or double).  Neither rho
  * nor a volume element is read.  Each cell sums in float, FMA, in ascending particle index, and stores a double; a cell
  * is exactly 0 where no support contains its centre; there are no float atomics: the result is bit-identical from run to
- * run and for every pair cap.  The scheme is the maps' (sx_map.hpp) in 3-D: pairs block << 32 | particle for blocks of
- * 8 x 8 x 4 cells, a radix sort, one workgroup per block, bands of whole block layers along z under a pair cap.
+ * run and for every pair cap.  One workgroup per block of 8 x 8 x 4 cells gathers the block's list; the pairs
+ * block << 32 | particle, their bands of whole block layers along z under a pair cap and their sort are the pair-binning
+ * engine's (sx_pairbin.hpp), as for the maps.
  *
  * Field.  SX_SPEC_VELOCITY: W_a = S0^p S1_a / S0 for a = vx, vy, vz; weight 0: p = 0, 1: p = 1/2, 2: p = 1/3; prefactor
  * 1/2.  SX_SPEC_SCALAR: one column (W = S1 / S0), or the mesh density S0 itself; weight 0; prefactor 1.  W = 0 where
@@ -33,18 +34,17 @@
 #include <vector>
 
 #include "../../include/sphexa_hip.h"
+#include "sx_pairbin.hpp"
 #include "sx_tree.hpp"
 
 namespace sx::spectrum
 {
 
 constexpr int      kBx = 8, kBy = 8, kBz = 4;   //!< cells per block: 256, one per lane; wave w owns the layer z = w
-constexpr uint32_t kChunk          = 256;       //!< records staged through LDS at a time (one per lane, 12 KB)
-constexpr uint32_t kMaxN           = 256;
-constexpr int      kMaxLayers      = kMaxN / kBz; //!< block layers along z: the unit of a band
-constexpr uint64_t kDefaultPairCap = 1ull << 27;
-constexpr uint64_t kMaxBandPairs   = 0x7fffffffu; //!< the sort counts its items in an int
-constexpr uint32_t kShellChunk     = 2048;      //!< modes per leaf of the shell sums' fixed tree
+constexpr uint32_t kChunk      = 256;         //!< records staged through LDS at a time (one per lane, 12 KB)
+constexpr uint32_t kMaxN       = 256;
+constexpr int      kMaxLayers  = kMaxN / kBz; //!< block layers along z: the unit of a band
+constexpr uint32_t kShellChunk = 2048;        //!< modes per leaf of the shell sums' fixed tree
 
 //! the reason sx_spectrum_check refuses, or nullptr
 const char* checkSpec(const sx_spectrum* sp, const sx_box* box);
@@ -70,15 +70,10 @@ struct DepositArgs
 };
 
 /*! the typed owner of the scratch, the cached tables and the last call's figures.  Every "spec.*" arena tag is requested
- *  at one site in sx_spectrum.hip, which stores the pointer here. */
+ *  at one site, the deposit's pair scratch by the engine (bin), the others in sx_spectrum.hip, which stores the pointer here. */
 struct SpecBuffers
 {
-    uint64_t            pairCap{0};
-    unsigned long long* counts{nullptr}; // device: clamped particles, longest list, pairs per block layer, mismatches
-    unsigned long long* countsHost{nullptr};
-    uint64_t *          pairsIn{nullptr}, *pairsOut{nullptr};
-    uint32_t *          offsets{nullptr}, *cursor{nullptr};
-    void*               sortTmp{nullptr};
+    pairbin::Buffers bin; // counts[0]: particles clamped to D / 2; rows: block layers.  Its events time fft and shells too
     // per-n tables, built by the first call that needs them
     double2* twiddle{nullptr}; // exp(-2 pi i k / n), k < n
     uint32_t twiddleN{0};
@@ -90,12 +85,7 @@ struct SpecBuffers
     uint32_t  permN{0}, numLeaves{0};
     // sx_spectrum_compute / sx_sim_spectrum: [2 leading doubles | S0 | S1 x 3], one complex mesh, power and modes
     double *sums{nullptr}, *cplx{nullptr}, *out{nullptr}, *outHost{nullptr};
-    // the last call
-    bool       deposited{false};
-    uint64_t   pairs{0}, bands{0}, scratchBytes{0};
-    bool       timing{false};
-    float      ms[5]{}; // binning, sort, gather, fft, shells
-    hipEvent_t ev[4]{};
+    float msFft{0.0f}, msShells{0.0f}; // since the last deposit (bin.timing)
 };
 
 int deposit(Arena& arena, SpecBuffers& b, const DepositArgs& a, hipStream_t s, std::string& err);
@@ -111,11 +101,16 @@ int shellSums(Arena& arena, SpecBuffers& b, const double* complexMesh, uint32_t 
 int compute(Arena& arena, SpecBuffers& b, const sx_spectrum& sp, DepositArgs a, double* power, uint64_t* modes,
             const std::function<bool(double*, size_t)>& reduce, hipStream_t s, std::string& err);
 
-constexpr int         kStatsMismatch     = -1;
-constexpr const char* kStatsMismatchText = "the last deposit's emit pass disagreed with its count pass: the mesh is incomplete";
-//! {pairs, bands, longest block list, particles clamped to D / 2} of the last deposit; synchronises
-int  stats(SpecBuffers& b, hipStream_t s, uint64_t out[4]);
-void release(SpecBuffers& b);
+//! the engine's words for the deposit; stats: {pairs, bands, longest block list, particles clamped to D / 2}
+//! (after a count / emit disagreement the mesh lacks contributions: SX_ERR_HIP with the last text)
+constexpr pairbin::Names kNames{"sx_mesh_deposit",
+                                "sx_spectrum",
+                                "block layer",
+                                "(deposit fewer particles at a time)",
+                                "sx_set_spectrum_pair_cap",
+                                "spec.",
+                                "nothing has been deposited",
+                                "the last deposit's emit pass disagreed with its count pass: the mesh is incomplete"};
 
 //! the twiddle table of n on the host: exp(-2 pi i k / n) from the first octant, each entry within 1 ulp
 void twiddleTable(uint32_t n, std::vector<double2>& t);

@@ -211,6 +211,19 @@ def map_kernel(t):
     return y
 
 
+def pair_bands(row_counts, cap=0):
+    """the bands [(r0, r1), ...] the maps and the mesh deposit make of rows with these pair counts under a pair cap
+    (0: the default): sx_pair_bands_internal, the planner on its own.  Raises SxError with the code and the refusal.
+    Needs no GPU."""
+    counts = np.ascontiguousarray(row_counts, dtype=np.uint64)
+    r0r1 = np.zeros(2 * max(counts.size, 1), np.int32)
+    nb = C.c_int()
+    rc = lib().sx_pair_bands_internal(counts.ctypes.data, counts.size, int(cap), r0r1.ctypes.data, C.byref(nb))
+    if rc != SX_OK:
+        raise SxError(f"sx_pair_bands_internal: code {rc}: {lib().sx_last_error(None).decode()}")
+    return [(int(r0r1[2 * k]), int(r0r1[2 * k + 1])) for k in range(nb.value)]
+
+
 def map_chunk_records():
     """records per LDS chunk of the render kernel (sx_map_chunk_records)"""
     return int(lib().sx_map_chunk_records())
@@ -601,6 +614,7 @@ def lib():
         "sx_map_check": (C.c_int, [C.POINTER(SxMap), C.POINTER(SxBox)]),
         "sx_map_kernel": (C.c_int, [vp, sz, vp]),
         "sx_map_chunk_records": (u32, []),
+        "sx_pair_bands_internal": (C.c_int, [vp, C.c_int, C.c_uint64, vp, C.POINTER(C.c_int)]),
         "sx_set_map_pair_cap": (C.c_int, [vp, C.c_uint64]),
         "sx_map_render": (C.c_int, [vp, C.POINTER(SxFields), C.POINTER(SxBox), u32, u32, C.c_double, C.POINTER(SxMap),
                                     vp, C.c_int, vp, vp]),

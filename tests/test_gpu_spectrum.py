@@ -256,6 +256,39 @@ def test_deposit_deterministic(ctx):
     assert np.array_equal(s0, t0) and np.array_equal(s1, t1)
 
 
+def test_render_and_deposit_on_one_context_keep_apart(ctx):
+    """the maps and the deposit run the same pair-binning engine, each with scratch and figures of its own: a banded
+    deposit between two renders changes neither the map's stats nor its image, and is itself what it is alone"""
+    c = case("random16")
+    fresh = sx.Context(0)
+    try:
+        pairs = c.gpu(fresh)[2]["pairs"]
+        # four block layers of about a quarter of the pairs each: no two fit under 0.3 of the total
+        cap = int(0.3 * pairs)
+        f0, f1, fst = c.gpu(fresh, cap=cap)
+    finally:
+        fresh.close()
+    assert fst["bands"] >= 2
+    spec = sx.SxMap("column", 2, (0.5, 0.5, 0.5), (1.0, 1.0), 0.0, (32, 32))
+    box = sx.make_box(UNIT, [1, 1, 1])
+    ds = sx.DeviceState(ctx, {"x": c.pos[:, 0], "y": c.pos[:, 1], "z": c.pos[:, 2], "h": c.h, "m": c.m})
+    try:
+        cols = [ctx.upload(np.ascontiguousarray(c.a[:, k])) for k in range(3)]
+        r0, r1 = ctx.render_map(ds.fields, box, spec, a=cols[0], K=K)
+        alone = ctx.map_stats()
+        assert alone["footprints"] == 2000 and alone["pairs"] > 0
+        ctx.set_spectrum_pair_cap(cap)
+        s0, s1 = ctx.mesh_deposit(ds.fields, box, c.n, a=cols, K=K)
+        assert ctx.map_stats() == alone
+        t0, t1 = ctx.render_map(ds.fields, box, spec, a=cols[0], K=K)
+        assert np.array_equal(r0, t0) and np.array_equal(r1, t1) and ctx.map_stats() == alone
+        assert ctx.spectrum_stats() == fst
+        assert np.array_equal(s0, f0) and np.array_equal(s1, f1)
+    finally:
+        ctx.set_spectrum_pair_cap(0)
+        ctx.free_all()
+
+
 # ---- transform ---------------------------------------------------------------------------------------------------
 
 def fft_bound(n):
