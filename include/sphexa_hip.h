@@ -675,6 +675,74 @@ int sx_profile_stats(sx_ctx* ctx, uint64_t out[4]);
 int sx_set_profile_timing(sx_ctx* ctx, int on);
 int sx_profile_times(sx_ctx* ctx, double out[4]);
 
+/* ---- friends-of-friends groups: cell grid, lock-free union-find, catalogue (sph-exa_amd/csrc/sx_fof.hpp) ---------
+ *
+ * Link.      Particles i != j of [first, last) are friends iff dx^2 + dy^2 + dz^2 < linking^2 (strict), in double, the
+ *            squares summed in this order.  d_a = a_i - a_j; on an axis with bnd == 1 it is the minimum image (L_a added
+ *            or subtracted once where |d_a| > L_a / 2), on open (0) and fixed (2) axes the plain difference.
+ * Groups.    The connected components of that relation.  Every particle belongs to exactly one; a particle without
+ *            friends is a group of one.  The partition is a property of the particle set, not of the algorithm.
+ * Label.     The smallest id among the members when an id column is given, else the smallest particle index (the index
+ *            in the columns of f, first included).  With ids the labels do not depend on the order of storage.
+ * Catalogue. The groups with at least minMembers members, ordered by member count descending, ties by label ascending:
+ *            label, count, mass M = sum m, centre of mass, mass-weighted mean velocity.
+ *            Centre of mass: x_ref + (sum m minimage(x - x_ref)) / M with x_ref the label particle's position, folded
+ *            back into [min, max) on periodic axes.  EXACT ONLY FOR A GROUP THAT SPANS LESS THAN HALF THE BOX on every
+ *            periodic axis: beyond that the minimum image of a member is not its image in the group.
+ *            Velocity: (sum m v) / M.  m, m * v and the sums are doubles (m * v of two floats is exact).
+ * Order.     The members of a catalogue group are summed in ascending id (or index) order: 256 partial sums, partial k
+ *            taking members k, k + 256, ... in turn, then a pairwise tree over the partials.  No floating-point atomic
+ *            anywhere, so the catalogue has the same bits on every run and, with ids, under any permutation of the input.
+ * One rank.  Components that cross rank boundaries need an iterated label exchange: sx_sim_fof refuses a sim with a
+ *            communicator of more than one rank. */
+typedef struct sx_fof
+{
+    double   linking;    /* the linking length, absolute */
+    uint32_t minMembers; /* the catalogue lists groups with at least this many members (0 counts as 1) */
+    uint32_t maxGroups;  /* capacity of the catalogue arrays */
+} sx_fof;
+/*! every pointer nullable (then not written); device pointers for sx_fof_compute, host pointers for sx_sim_fof */
+typedef struct sx_fof_result
+{
+    uint64_t* label;      /* [last - first], in the order of the columns */
+    uint64_t* groupLabel; /* [maxGroups] */
+    uint32_t* groupCount; /* [maxGroups] */
+    double*   groupMass;  /* [maxGroups] */
+    double*   groupCom;   /* [maxGroups][3] */
+    double*   groupVel;   /* [maxGroups][3] */
+    uint64_t* numGroups;  /* [0] groups with count >= minMembers (may exceed maxGroups: the first maxGroups are written),
+                             [1] all groups, singles included */
+} sx_fof_result;
+/*! host only, needs no GPU: SX_OK, or SX_ERR_ARG with the reason and its figures in sx_last_error(NULL) (per thread).
+ *  Refused: a NULL argument, a linking length that is not finite or not positive, one above a third of the box length on
+ *  a periodic axis (three distinct cells and an unambiguous minimum image need it). */
+int sx_fof_check(const sx_fof* fof, const sx_box* box);
+/*! host only: the cell grid a call on n particles uses.  Per axis floor(L_a / linking * (1 - 2^-20)) cells, at least 1
+ *  (3 on a periodic axis) and at most 1024, so that a cell's edge L_a / dims[a] exceeds the linking length and friends
+ *  lie in the same or in adjacent cells whatever the rounding of a cell coordinate; then, while the cells number more
+ *  than max(27, 2 n), the axis with the most cells (the first of equals) takes ceil(dims / 2), not below its minimum.
+ *  So the dense cell-start array stays below 8 bytes per particle.  SX_ERR_ARG: whatever sx_fof_check refuses. */
+int sx_fof_grid(const sx_fof* fof, const sx_box* box, uint64_t n, uint32_t dims[3]);
+/*! the groups of the particles [first, last) of f (x, y, z; m, vx, vy, vz for the catalogue's mass, centre and velocity:
+ *  no other column is read, so the gravity-only layout serves) into the device arrays of deviceOut.  id: device, f->n
+ *  entries, or NULL.  Particles outside [first, last) link nothing.  A particle outside an open box is binned into the
+ *  edge cell (clamping is monotone: friends stay in the same or in adjacent cells); on a periodic axis it is wrapped.
+ *  Stages: cell keys, count and sort (hipcub); link (one wave per 64 consecutive sorted targets, each unordered pair
+ *  tested once from its earlier member, union by compare-and-swap of the larger root under the smaller); compress, the
+ *  labels (64-bit integer minimum) and the member counts (integer adds); the catalogue (two stable sorts each for the
+ *  groups and for the members, one workgroup per group).  The scratch lives in the context under the tags fof.*, about
+ *  285 bytes per particle once a catalogue has been asked for.  SX_ERR_ARG: whatever sx_fof_check refuses, maxGroups == 0 with a catalogue pointer set,
+ *  missing columns, first > last or last > f->n, more than 2^31 - 1 particles.  Synchronises (twice). */
+int sx_fof_compute(sx_ctx* ctx, const sx_fields* f, const sx_box* box, uint32_t first, uint32_t last,
+                   const uint64_t* id, const sx_fof* fof, const sx_fof_result* deviceOut);
+/*! the context's last call: {pair tests, union retries (a compare-and-swap that lost against another wave), all groups,
+ *  groups with count >= minMembers}; SX_ERR_ARG before the first */
+int sx_fof_stats(sx_ctx* ctx, uint64_t out[4]);
+/*! measurement: with on != 0 the following calls time their stages with HIP events; sx_fof_times: {grid, link,
+ *  compress, catalogue} in ms of the last call */
+int sx_set_fof_timing(sx_ctx* ctx, int on);
+int sx_fof_times(sx_ctx* ctx, double out[4]);
+
 /* ---- self-gravity: ryoanji MultipoleHolder seam (multipole_holder.cuh:40-66, gravity_wrapper.hpp:104-174) ----- */
 /*! expansion centers (mass centers, {x,y,z,mac^2}, numNodes x 4 doubles; mac = 2 max(node size)/theta + |com-geo|,
  *  setMac, source_center.hpp:130-143) and Cartesian quadrupoles (numNodes x 8 floats, Cqi order,
@@ -959,6 +1027,15 @@ int    sx_sim_set_spectrum_pair_cap(sx_sim* sim, uint64_t pairs);
  *  particles; nonfinite over all ranks). */
 int    sx_sim_profile(sx_sim* sim, const sx_profile* prof, sx_profile_result* hostOut);
 int    sx_sim_profile_stats(sx_sim* sim, uint64_t out[4]);
+/*! sx_fof_compute of the locals of the current state with the sim's id column, into the host arrays of hostOut; labels
+ *  in the sim's current particle order (pair them with the id field).  Reads x, y, z, m, vx, vy, vz and id only: every
+ *  propagator, the gravity-only one included; nothing in sx_sim_step calls it and it changes no field and no scalar.
+ *  The buffers live in the sim's arena under the tags fof.*, are allocated by the first call and counted by
+ *  sx_sim_memory from then on.  A sim with a communicator of more than one rank is refused on every rank before any
+ *  collective (SX_ERR_ARG): groups that cross rank boundaries are not merged.  sx_sim_fof_stats: sx_fof_stats of the
+ *  sim's last call. */
+int    sx_sim_fof(sx_sim* sim, const sx_fof* fof, const sx_fof_result* hostOut);
+int    sx_sim_fof_stats(sx_sim* sim, uint64_t out[4]);
 /*! device time (ms) of each hot kernel alone in the last step (HIP events on the launch stream, bracketing just the
  *  launch): findNeighbors, xmass, veDefGradh, iadDivvCurlv, avSwitches, momentumEnergy */
 int    sx_sim_kernel_times(sx_sim* sim, float* ms, int cap, const char** names);

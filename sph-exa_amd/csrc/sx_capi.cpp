@@ -22,6 +22,7 @@
 #include "sx_nbody.hpp"
 #include "sx_observables.hpp"
 #include "sx_profile.hpp"
+#include "sx_fof.hpp"
 #include "sx_spectrum.hpp"
 #include "sx_tree.hpp"
 #include "sx_timestep.hpp"
@@ -129,6 +130,7 @@ struct sx_ctx
     sx::map::MapBuffers mapBuf;          // pair scratch and figures of sx_map_render
     sx::spectrum::SpecBuffers specBuf;   // scratch, per-n tables, meshes and figures of the spectra
     sx::profile::ProfBuffers profBuf;    // accumulators, uploaded edges and tables and figures of the profiles
+    sx::fof::FofBuffers fofBuf;          // grid, union-find and catalogue scratch and figures of the group finder
     float2*     wh{nullptr};
     float2*     whd{nullptr};
     double      K{0};
@@ -200,6 +202,7 @@ extern "C"
     const float*  sx_ctx_powtab_internal(sx_ctx* c, uint32_t ng0) { return ensurePowTab(c, ng0); }
     void          sx_ctx_set_error_internal(sx_ctx* c, const char* msg) { fail(c, SX_ERR_ARG, msg); }
     uint32_t      sx_ctx_pack12_max_internal(sx_ctx* c) { return c->packMax(); }
+    sx::fof::FofBuffers* sx_ctx_fof_buffers_internal(sx_ctx* c) { return &c->fofBuf; }
 
     int sx_set_pack12_max(sx_ctx* c, uint32_t maxUnion)
     {
@@ -273,6 +276,7 @@ extern "C"
         sx::pairbin::release(c->mapBuf.bin);
         sx::pairbin::release(c->specBuf.bin);
         sx::profile::release(c->profBuf);
+        sx::fof::release(c->fofBuf);
         c->arena.release();
         if (c->own) (void)hipStreamDestroy(c->own);
         delete c;
@@ -1678,6 +1682,54 @@ extern "C"
         for (int k = 0; k < np; ++k)
             SX_HIP(c, hipMemcpyAsync(pc[k].dst, c->profBuf.out + pc[k].off, pc[k].words * 8, hipMemcpyDeviceToDevice, c->stream));
         SX_HIP(c, hipStreamSynchronize(c->stream));
+        return SX_OK;
+    }
+
+    // ---- friends-of-friends groups (sx_fof.hpp) --------------------------------------------------------------------
+    int sx_fof_check(const sx_fof* p, const sx_box* box)
+    {
+        if (std::string why = sx::fof::checkSpec(p, box); !why.empty()) return fail(nullptr, SX_ERR_ARG, why);
+        return SX_OK;
+    }
+
+    int sx_fof_grid(const sx_fof* p, const sx_box* box, uint64_t n, uint32_t dims[3])
+    {
+        if (!dims) return fail(nullptr, SX_ERR_ARG, "sx_fof_grid: null dims");
+        if (std::string why = sx::fof::checkSpec(p, box); !why.empty()) return fail(nullptr, SX_ERR_ARG, why);
+        sx::fof::chooseGrid(*p, *box, n, dims);
+        return SX_OK;
+    }
+
+    int sx_fof_compute(sx_ctx* c, const sx_fields* f, const sx_box* box, uint32_t first, uint32_t last,
+                       const uint64_t* id, const sx_fof* p, const sx_fof_result* res)
+    {
+        if (!c) return SX_ERR_ARG;
+        if (std::string why = sx::fof::whyRefused(p, box, f, first, last, res); !why.empty()) return fail(c, SX_ERR_ARG, why);
+        std::string err;
+        const int   rc = sx::fof::compute(c->arena, c->fofBuf, *p, *f, *box, first, last, id, *res, false, c->stream, err);
+        return rc == SX_OK ? SX_OK : fail(c, rc, err);
+    }
+
+    int sx_fof_stats(sx_ctx* c, uint64_t out[4])
+    {
+        if (!c || !out) return SX_ERR_ARG;
+        if (!c->fofBuf.done) return fail(c, SX_ERR_ARG, "sx_fof_stats: no groups have been computed");
+        std::copy(c->fofBuf.stats, c->fofBuf.stats + 4, out);
+        return SX_OK;
+    }
+
+    int sx_set_fof_timing(sx_ctx* c, int on)
+    {
+        if (!c) return SX_ERR_ARG;
+        c->fofBuf.timing = on != 0;
+        return SX_OK;
+    }
+
+    int sx_fof_times(sx_ctx* c, double out[4])
+    {
+        if (!c || !out) return SX_ERR_ARG;
+        for (int k = 0; k < 4; ++k)
+            out[k] = c->fofBuf.ms[k];
         return SX_OK;
     }
 

@@ -1,0 +1,646 @@
+/*! @file sx_fof.hip
+ * @brief Friends-of-friends groups: cell grid, lock-free union-find, labels and the catalogue (sx_fof.hpp).
+ */
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+
+#include "sx_fof.hpp"
+
+namespace sx::fof
+{
+
+#define FOF_HIP(call)                                                                                                  \
+    do {                                                                                                               \
+        hipError_t e_ = (call);                                                                                        \
+        if (e_ != hipSuccess)                                                                                          \
+        {                                                                                                              \
+            err = std::string("sx_fof: " #call ": ") + hipGetErrorString(e_);                                          \
+            return SX_ERR_HIP;                                                                                         \
+        }                                                                                                              \
+    } while (0)
+
+// ---- host decisions ---------------------------------------------------------------------------------------------
+
+std::string checkSpec(const sx_fof* p, const sx_box* box)
+{
+    if (!p || !box) return "sx_fof_check: null specification or box";
+    char buf[256];
+    if (!std::isfinite(p->linking) || !(p->linking > 0.0))
+    {
+        std::snprintf(buf, sizeof buf, "sx_fof_check: the linking length must be finite and positive (got %g)", p->linking);
+        return buf;
+    }
+    for (int a = 0; a < 3; ++a)
+    {
+        const double L = box->lim[2 * a + 1] - box->lim[2 * a];
+        if (box->bnd[a] == 1 && !(p->linking <= L / 3.0))
+        {
+            std::snprintf(buf, sizeof buf,
+                          "sx_fof_check: the linking length %g exceeds a third of the periodic %c extent %g (%g): three "
+                          "distinct cells and an unambiguous minimum image need it",
+                          p->linking, "xyz"[a], L, L / 3.0);
+            return buf;
+        }
+    }
+    return {};
+}
+
+void chooseGrid(const sx_fof& p, const sx_box& box, uint64_t n, uint32_t dims[3])
+{
+    uint32_t lowest[3];
+    for (int a = 0; a < 3; ++a)
+    {
+        const double L = box.lim[2 * a + 1] - box.lim[2 * a];
+        const double q = std::floor(L / p.linking * (1.0 - 0x1p-20));
+        lowest[a]      = box.bnd[a] == 1 ? 3 : 1;
+        dims[a]        = q >= (double)kMaxDim ? kMaxDim : q >= (double)lowest[a] ? (uint32_t)q : lowest[a];
+    }
+    const uint64_t limit = std::max<uint64_t>(27, 2 * n);
+    while ((uint64_t)dims[0] * dims[1] * dims[2] > limit)
+    {
+        int a = 0;
+        for (int k = 1; k < 3; ++k)
+            if (dims[k] > dims[a]) a = k;
+        dims[a] = std::max(lowest[a], (dims[a] + 1) / 2);
+    }
+}
+
+std::string whyRefused(const sx_fof* p, const sx_box* box, const sx_fields* f, uint32_t first, uint32_t last,
+                       const sx_fof_result* res)
+{
+    if (std::string why = checkSpec(p, box); !why.empty()) return why;
+    if (!f || !res) return "sx_fof: null fields or result";
+    if (first > last || last > f->n) return "sx_fof: [first, last) is not a range of f";
+    if (!f->x || !f->y || !f->z) return "sx_fof: x, y and z are required";
+    if ((uint64_t)last - first > kMaxParticles) return "sx_fof: more than 2^31 - 1 particles";
+    const bool real = res->groupMass || res->groupCom || res->groupVel;
+    const bool cat  = real || res->groupLabel || res->groupCount;
+    if (cat && p->maxGroups == 0) return "sx_fof: maxGroups is 0 with a catalogue array set (capacity 0 for a catalogue that was asked for)";
+    if (real && (!f->m || !f->vx || !f->vy || !f->vz)) return "sx_fof: the catalogue's mass, centre and velocity need m, vx, vy and vz";
+    return {};
+}
+
+// ---- kernels -----------------------------------------------------------------------------------------------------
+
+namespace
+{
+
+struct Grid
+{
+    double   lo[3], hi[3], len[3], half[3], inv[3]; // inv: cells per unit length (0 on an axis without extent)
+    uint32_t dims[3];
+    int      pbc[3];
+    double   l2;
+};
+
+__device__ __forceinline__ uint32_t cellOf(double v, const Grid& g, int a)
+{
+    const double t = (v - g.lo[a]) * g.inv[a];
+    if (!(fabs(t) < 1e15)) return 0; // not a number, or far outside: any cell will do, it has no friends
+    long long       c = (long long)floor(t);
+    const long long d = g.dims[a];
+    if (g.pbc[a])
+    {
+        c %= d;
+        if (c < 0) c += d;
+    }
+    else c = c < 0 ? 0 : c > d - 1 ? d - 1 : c;
+    return (uint32_t)c;
+}
+
+__global__ __launch_bounds__(kBlock) void keyKernel(const double* __restrict__ x, const double* __restrict__ y,
+                                                    const double* __restrict__ z, uint32_t first, uint32_t n, Grid g,
+                                                    uint32_t* __restrict__ keys, uint32_t* __restrict__ idx,
+                                                    uint32_t* __restrict__ cellCount)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const size_t   p   = (size_t)first + i;
+    const uint32_t key = cellOf(x[p], g, 0) + g.dims[0] * (cellOf(y[p], g, 1) + g.dims[1] * cellOf(z[p], g, 2));
+    keys[i]            = key;
+    idx[i]             = i;
+    atomicAdd(cellCount + key, 1u);
+}
+
+__global__ __launch_bounds__(kBlock) void gatherKernel(const double* __restrict__ x, const double* __restrict__ y,
+                                                       const double* __restrict__ z, uint32_t first, uint32_t n,
+                                                       const uint32_t* __restrict__ order, double* __restrict__ xs,
+                                                       double* __restrict__ ys, double* __restrict__ zs,
+                                                       uint32_t* __restrict__ parent, uint32_t* __restrict__ count,
+                                                       unsigned long long* __restrict__ minId, uint32_t* __restrict__ rankOf)
+{
+    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n) return;
+    const size_t p = (size_t)first + order[s];
+    xs[s] = x[p], ys[s] = y[p], zs[s] = z[p];
+    parent[s] = s, count[s] = 0, minId[s] = ~0ull, rankOf[s] = kNoGroup;
+}
+
+//! a load that another compute unit's store reaches: the first-level cache is per compute unit and not coherent
+__device__ __forceinline__ uint32_t loadShared(const uint32_t* p)
+{
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+//! the root above x as seen now; on the way every visited node is lowered to its grandparent (an ancestor: no cycle)
+__device__ __forceinline__ uint32_t findRoot(uint32_t* parent, uint32_t x)
+{
+    uint32_t p = loadShared(parent + x);
+    while (p != x)
+    {
+        const uint32_t gp = loadShared(parent + p);
+        if (gp != p) atomicMin(parent + x, gp);
+        x = p;
+        p = gp;
+    }
+    return x;
+}
+
+//! joins the components of a and b; returns the root both are under now.  retries: compare-and-swaps lost
+__device__ __forceinline__ uint32_t unite(uint32_t* parent, uint32_t a, uint32_t b, unsigned long long& retries)
+{
+    for (;;)
+    {
+        a = findRoot(parent, a);
+        b = findRoot(parent, b);
+        if (a == b) return a;
+        const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
+        const uint32_t old = atomicCAS(parent + hi, hi, lo);
+        if (old == hi) return lo;
+        ++retries; // hi was hooked under old < hi meanwhile: go on from there
+        a = old, b = lo;
+    }
+}
+
+struct LinkArgs
+{
+    const double *  xs, *ys, *zs;
+    const uint32_t *keys, *cellStart;
+    uint32_t*       parent;
+    uint32_t        n;
+    Grid            g;
+    unsigned long long* counters;
+};
+
+__device__ __forceinline__ double minImage(double d, int pbc, double half, double len)
+{
+    if (pbc)
+    {
+        if (d > half) d -= len;
+        else if (d < -half) d += len;
+    }
+    return d;
+}
+
+/*! one wave per 64 consecutive sorted targets, a lane per target.  A target tests the particles behind it in the sorted
+ *  order that lie in the 27 cells around its own, so every unordered pair is tested once. */
+__global__ __launch_bounds__(kBlock) void linkKernel(LinkArgs a)
+{
+    const uint32_t     i     = blockIdx.x * kBlock + threadIdx.x;
+    unsigned long long tests = 0, retries = 0;
+    if (i < a.n)
+    {
+        const Grid&    g  = a.g;
+        const double   xi = a.xs[i], yi = a.ys[i], zi = a.zs[i];
+        const uint32_t key = a.keys[i];
+        const int      dx = (int)g.dims[0], dy = (int)g.dims[1], dz = (int)g.dims[2];
+        const int      cx = (int)(key % g.dims[0]), cy = (int)((key / g.dims[0]) % g.dims[1]);
+        const int      cz = (int)(key / (g.dims[0] * g.dims[1]));
+        uint32_t       ri = i;
+        auto scan = [&](uint32_t begin, uint32_t end)
+        {
+            for (uint32_t j = begin > i ? begin : i + 1; j < end; ++j)
+            {
+                const double ddx = minImage(xi - a.xs[j], g.pbc[0], g.half[0], g.len[0]);
+                const double ddy = minImage(yi - a.ys[j], g.pbc[1], g.half[1], g.len[1]);
+                const double ddz = minImage(zi - a.zs[j], g.pbc[2], g.half[2], g.len[2]);
+                ++tests;
+                if (ddx * ddx + ddy * ddy + ddz * ddz < g.l2) ri = unite(a.parent, ri, j, retries);
+            }
+        };
+        for (int oz = -1; oz <= 1; ++oz)
+        {
+            int zc = cz + oz;
+            if (zc < 0 || zc >= dz)
+            {
+                if (!g.pbc[2]) continue;
+                zc += zc < 0 ? dz : -dz;
+            }
+            for (int oy = -1; oy <= 1; ++oy)
+            {
+                int yc = cy + oy;
+                if (yc < 0 || yc >= dy)
+                {
+                    if (!g.pbc[1]) continue;
+                    yc += yc < 0 ? dy : -dy;
+                }
+                const uint32_t row = (uint32_t)dx * ((uint32_t)yc + (uint32_t)dy * (uint32_t)zc);
+                const int      xl = cx > 0 ? cx - 1 : 0, xh = cx < dx - 1 ? cx + 1 : dx - 1;
+                scan(a.cellStart[row + xl], a.cellStart[row + xh + 1]);
+                if (g.pbc[0]) // three cells or more: the far end is not in the run above
+                {
+                    if (cx == 0) scan(a.cellStart[row + dx - 1], a.cellStart[row + dx]);
+                    else if (cx == dx - 1) scan(a.cellStart[row], a.cellStart[row + 1]);
+                }
+            }
+        }
+    }
+    // the wave's counts in one add each; every lane of the wave arrives here
+    for (int o = 32; o > 0; o >>= 1)
+    {
+        tests += __shfl_xor(tests, o);
+        retries += __shfl_xor(retries, o);
+    }
+    if ((threadIdx.x & 63) == 0)
+    {
+        if (tests) atomicAdd(a.counters + 0, tests);
+        if (retries) atomicAdd(a.counters + 1, retries);
+    }
+}
+
+/*! pointer jumping to the end: root[s] is the root above s (nothing stores to parent[] here).  The label is the minimum
+ *  id per root, the member count an integer add: the same totals whatever the order. */
+__global__ __launch_bounds__(kBlock) void compressKernel(const uint32_t* __restrict__ parent, uint32_t n, uint32_t first,
+                                                         const uint32_t* __restrict__ order,
+                                                         const uint64_t* __restrict__ id, uint32_t* __restrict__ root,
+                                                         unsigned long long* __restrict__ minId,
+                                                         uint32_t* __restrict__ count, uint64_t* __restrict__ idKeys,
+                                                         uint32_t* __restrict__ mem)
+{
+    const uint32_t     s  = blockIdx.x * kBlock + threadIdx.x;
+    const bool         in = s < n;
+    uint32_t           r  = kNoGroup;
+    unsigned long long v  = ~0ull;
+    if (in)
+    {
+        uint32_t p = parent[s];
+        r          = s;
+        while (p != r)
+        {
+            r = p;
+            p = parent[r];
+        }
+        root[s]        = r;
+        const size_t q = (size_t)first + order[s];
+        v              = id ? id[q] : (uint64_t)q;
+        idKeys[s]      = v;
+        mem[s]         = s;
+    }
+    // neighbours in the sorted order mostly share their root: a wave that is of one root sends one minimum and one add
+    // (a halo of 10^5 members would otherwise queue that many atomics on two addresses)
+    const uint32_t r0 = __shfl(r, 0);
+    if (__all(in && r == r0))
+    {
+        for (int o = 32; o > 0; o >>= 1)
+        {
+            const unsigned long long w = __shfl_xor(v, o);
+            v                          = w < v ? w : v;
+        }
+        if ((threadIdx.x & 63) == 0)
+        {
+            atomicMin(minId + r0, v);
+            atomicAdd(count + r0, 64u);
+        }
+    }
+    else if (in)
+    {
+        atomicMin(minId + r, v);
+        atomicAdd(count + r, 1u);
+    }
+}
+
+//! the labels in the order of the columns; the roots counted, those with minMembers members or more appended
+__global__ __launch_bounds__(kBlock) void labelKernel(const uint32_t* __restrict__ root, uint32_t n,
+                                                      const uint32_t* __restrict__ order,
+                                                      const unsigned long long* __restrict__ minId,
+                                                      const uint32_t* __restrict__ count, uint32_t minMembers,
+                                                      uint64_t* __restrict__ label, uint64_t* __restrict__ selLabel,
+                                                      uint32_t* __restrict__ selRoot, unsigned long long* counters)
+{
+    const uint32_t s      = blockIdx.x * kBlock + threadIdx.x;
+    const bool     in     = s < n;
+    const uint32_t r      = in ? root[s] : 0;
+    const bool     isRoot = in && r == s;
+    if (in) label[order[s]] = minId[r];
+    const unsigned long long roots = __popcll(__ballot(isRoot));
+    if ((threadIdx.x & 63) == 0 && roots) atomicAdd(counters + 2, roots);
+    if (isRoot && count[s] >= minMembers)
+    {
+        const unsigned long long slot = atomicAdd(counters + 3, 1ull);
+        selLabel[slot] = minId[s];
+        selRoot[slot]  = s;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void selKeyKernel(const uint32_t* __restrict__ selRootSorted,
+                                                       const uint32_t* __restrict__ count, uint32_t G,
+                                                       uint32_t* __restrict__ selKey, uint32_t* __restrict__ selPos)
+{
+    const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= G) return;
+    selKey[k] = ~count[selRootSorted[k]]; // ascending in ~count: descending in count
+    selPos[k] = k;
+}
+
+//! the first Gc groups of the order (count descending, label ascending): their rank at the root, label and count out
+__global__ __launch_bounds__(kBlock) void rankKernel(const uint32_t* __restrict__ selPosSorted,
+                                                     const uint32_t* __restrict__ selRootSorted,
+                                                     const uint64_t* __restrict__ selLabelSorted,
+                                                     const uint32_t* __restrict__ count, uint32_t Gc,
+                                                     uint32_t* __restrict__ rankOf, uint64_t* __restrict__ outLabel,
+                                                     uint32_t* __restrict__ outCount, uint32_t* __restrict__ segCount)
+{
+    const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= Gc) return;
+    const uint32_t pos = selPosSorted[k], r = selRootSorted[pos];
+    rankOf[r]   = k;
+    outLabel[k] = selLabelSorted[pos];
+    outCount[k] = segCount[k] = count[r];
+}
+
+__global__ __launch_bounds__(kBlock) void memKeyKernel(const uint32_t* __restrict__ memById,
+                                                       const uint32_t* __restrict__ root,
+                                                       const uint32_t* __restrict__ rankOf, uint32_t n, uint32_t Gc,
+                                                       uint32_t* __restrict__ memKey)
+{
+    const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t g = rankOf[root[memById[k]]];
+    memKey[k]        = g < Gc ? g : Gc; // no catalogue group: behind them all
+}
+
+struct ReduceArgs
+{
+    const uint32_t *memSorted, *segStart, *outCount, *order;
+    const double *  xs, *ys, *zs;
+    const float *   m, *vx, *vy, *vz;
+    uint32_t        first, G;
+    Grid            g;
+    double*         outReal; // [mass G | com 3 G | vel 3 G]
+};
+
+/*! one workgroup per catalogue group.  Thread t sums the members t, t + 256, ... of the (id-ordered) segment in turn,
+ *  then the 256 partials are added pairwise in LDS: a fixed order, so the same bits on every run. */
+__global__ __launch_bounds__(kBlock) void reduceKernel(ReduceArgs a)
+{
+    __shared__ double part[7][kBlock];
+    const uint32_t g = blockIdx.x, t = threadIdx.x;
+    const uint32_t start = a.segStart[g], cnt = a.outCount[g];
+    const uint32_t sRef  = a.memSorted[start];
+    const double   ref[3] = {a.xs[sRef], a.ys[sRef], a.zs[sRef]};
+    double         sum[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (uint32_t k = t; k < cnt; k += kBlock)
+    {
+        const uint32_t s  = a.memSorted[start + k];
+        const size_t   p  = (size_t)a.first + a.order[s];
+        const double   mk = (double)a.m[p];
+        sum[0] += mk;
+        sum[1] += mk * minImage(a.xs[s] - ref[0], a.g.pbc[0], a.g.half[0], a.g.len[0]);
+        sum[2] += mk * minImage(a.ys[s] - ref[1], a.g.pbc[1], a.g.half[1], a.g.len[1]);
+        sum[3] += mk * minImage(a.zs[s] - ref[2], a.g.pbc[2], a.g.half[2], a.g.len[2]);
+        sum[4] += mk * (double)a.vx[p];
+        sum[5] += mk * (double)a.vy[p];
+        sum[6] += mk * (double)a.vz[p];
+    }
+    for (int q = 0; q < 7; ++q)
+        part[q][t] = sum[q];
+    __syncthreads();
+    for (int w = kBlock / 2; w > 0; w >>= 1)
+    {
+        if (t < (uint32_t)w)
+            for (int q = 0; q < 7; ++q)
+                part[q][t] += part[q][t + w];
+        __syncthreads();
+    }
+    if (t == 0)
+    {
+        const double M = part[0][0];
+        a.outReal[g]   = M;
+        for (int k = 0; k < 3; ++k)
+        {
+            double c = ref[k] + part[1 + k][0] / M;
+            if (a.g.pbc[k])
+            {
+                if (c < a.g.lo[k]) c += a.g.len[k];
+                else if (c >= a.g.hi[k]) c -= a.g.len[k];
+            }
+            a.outReal[(size_t)a.G + 3 * (size_t)g + k]     = c;
+            a.outReal[4 * (size_t)a.G + 3 * (size_t)g + k] = part[4 + k][0] / M;
+        }
+    }
+}
+
+unsigned blocks(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+
+int bitLength(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
+
+} // namespace
+
+// ---- the launcher ------------------------------------------------------------------------------------------------
+
+int compute(Arena& arena, FofBuffers& b, const sx_fof& p, const sx_fields& f, const sx_box& box, uint32_t first,
+            uint32_t last, const uint64_t* id, const sx_fof_result& res, bool toHost, hipStream_t s, std::string& err)
+{
+    const uint32_t n = last - first;
+    uint32_t       dims[3];
+    chooseGrid(p, box, n, dims);
+    const uint32_t cells      = dims[0] * dims[1] * dims[2];
+    const uint32_t minMembers = std::max(1u, p.minMembers);
+    const bool     wantReal   = res.groupMass || res.groupCom || res.groupVel;
+    const bool     wantCat    = wantReal || res.groupLabel || res.groupCount;
+    const uint32_t cap        = wantCat ? std::min(p.maxGroups, std::max(n, 1u)) : 0;
+    const auto     kind       = toHost ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+
+    b.counters     = arena.get<uint64_t>("fof.counters", 4);
+    b.countersHost = arena.pinned<uint64_t>("fof.countersHost", 4);
+    if (!b.counters || !b.countersHost)
+    {
+        err = "sx_fof: counter buffers";
+        return SX_ERR_NOMEM;
+    }
+    if (b.timing)
+        for (auto& e : b.ev)
+            if (!e) FOF_HIP(hipEventCreate(&e));
+    std::fill(b.ms, b.ms + 4, 0.f);
+    FOF_HIP(hipMemsetAsync(b.counters, 0, 4 * sizeof(uint64_t), s));
+    if (n == 0)
+    {
+        if (res.numGroups) FOF_HIP(hipMemcpyAsync(res.numGroups, b.counters, 2 * sizeof(uint64_t), kind, s));
+        FOF_HIP(hipStreamSynchronize(s));
+        std::fill(b.stats, b.stats + 4, 0ull);
+        b.done = true;
+        return SX_OK;
+    }
+
+    // the temporary storage of the largest sort or scan
+    size_t tmpBytes = 0;
+    {
+        size_t q = 0;
+        FOF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, q, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                                   (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 32, s));
+        tmpBytes = std::max(tmpBytes, q);
+        FOF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, q, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                                                   (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 64, s));
+        tmpBytes = std::max(tmpBytes, q);
+        FOF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, q, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                                 (int)std::max(cells + 1, n), s));
+        tmpBytes = std::max(tmpBytes, q);
+    }
+    b.keys       = arena.get<uint32_t>("fof.keys", n);
+    b.keysSorted = arena.get<uint32_t>("fof.keysSorted", n);
+    b.idx        = arena.get<uint32_t>("fof.idx", n);
+    b.order      = arena.get<uint32_t>("fof.order", n);
+    b.cellCount  = arena.get<uint32_t>("fof.cellCount", (size_t)cells + 1);
+    b.cellStart  = arena.get<uint32_t>("fof.cellStart", (size_t)cells + 1);
+    b.xs         = arena.get<double>("fof.xs", n);
+    b.ys         = arena.get<double>("fof.ys", n);
+    b.zs         = arena.get<double>("fof.zs", n);
+    b.sortTmp    = arena.get<char>("fof.sortTmp", tmpBytes);
+    b.parent     = arena.get<uint32_t>("fof.parent", n);
+    b.root       = arena.get<uint32_t>("fof.root", n);
+    b.count      = arena.get<uint32_t>("fof.count", n);
+    b.rankOf     = arena.get<uint32_t>("fof.rankOf", n);
+    b.minId      = arena.get<uint64_t>("fof.minId", n);
+    b.label      = arena.get<uint64_t>("fof.label", n);
+    b.selLabel   = arena.get<uint64_t>("fof.selLabel", n);
+    b.selRoot    = arena.get<uint32_t>("fof.selRoot", n);
+    b.idKeys     = arena.get<uint64_t>("fof.idKeys", n);
+    b.mem        = arena.get<uint32_t>("fof.mem", n);
+    if (!b.keys || !b.keysSorted || !b.idx || !b.order || !b.cellCount || !b.cellStart || !b.xs || !b.ys || !b.zs ||
+        !b.sortTmp || !b.parent || !b.root || !b.count || !b.rankOf || !b.minId || !b.label || !b.selLabel ||
+        !b.selRoot || !b.idKeys || !b.mem)
+    {
+        err = "sx_fof: scratch buffers";
+        return SX_ERR_NOMEM;
+    }
+
+    Grid g{};
+    for (int a = 0; a < 3; ++a)
+    {
+        g.lo[a] = box.lim[2 * a], g.hi[a] = box.lim[2 * a + 1];
+        g.len[a]  = g.hi[a] - g.lo[a];
+        g.half[a] = 0.5 * g.len[a];
+        g.dims[a] = dims[a];
+        g.inv[a]  = g.len[a] > 0.0 && std::isfinite(g.len[a]) ? dims[a] / g.len[a] : 0.0;
+        g.pbc[a]  = box.bnd[a] == 1;
+    }
+    g.l2 = p.linking * p.linking;
+    auto* counters = reinterpret_cast<unsigned long long*>(b.counters);
+    auto* minId    = reinterpret_cast<unsigned long long*>(b.minId);
+    const int keyBits = std::max(1, bitLength(cells - 1));
+
+    // ---- grid
+    if (b.timing) FOF_HIP(hipEventRecord(b.ev[0], s));
+    FOF_HIP(hipMemsetAsync(b.cellCount, 0, ((size_t)cells + 1) * sizeof(uint32_t), s));
+    keyKernel<<<blocks(n), kBlock, 0, s>>>(f.x, f.y, f.z, first, n, g, b.keys, b.idx, b.cellCount);
+    FOF_HIP(hipcub::DeviceRadixSort::SortPairs(b.sortTmp, tmpBytes, (const uint32_t*)b.keys, b.keysSorted,
+                                               (const uint32_t*)b.idx, b.order, (int)n, 0, keyBits, s));
+    FOF_HIP(hipcub::DeviceScan::ExclusiveSum(b.sortTmp, tmpBytes, (const uint32_t*)b.cellCount, b.cellStart,
+                                             (int)(cells + 1), s));
+    gatherKernel<<<blocks(n), kBlock, 0, s>>>(f.x, f.y, f.z, first, n, b.order, b.xs, b.ys, b.zs, b.parent, b.count,
+                                              minId, b.rankOf);
+    if (b.timing) FOF_HIP(hipEventRecord(b.ev[1], s));
+    // ---- link
+    LinkArgs la{b.xs, b.ys, b.zs, b.keysSorted, b.cellStart, b.parent, n, g, counters};
+    linkKernel<<<blocks(n), kBlock, 0, s>>>(la);
+    if (b.timing) FOF_HIP(hipEventRecord(b.ev[2], s));
+    // ---- compress, labels, counts
+    compressKernel<<<blocks(n), kBlock, 0, s>>>(b.parent, n, first, b.order, id, b.root, minId, b.count, b.idKeys, b.mem);
+    labelKernel<<<blocks(n), kBlock, 0, s>>>(b.root, n, b.order, minId, b.count, minMembers, b.label, b.selLabel,
+                                             b.selRoot, counters);
+    if (b.timing) FOF_HIP(hipEventRecord(b.ev[3], s));
+    FOF_HIP(hipGetLastError());
+    FOF_HIP(hipMemcpyAsync(b.countersHost, b.counters, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    FOF_HIP(hipStreamSynchronize(s));
+    const uint64_t numAll = b.countersHost[2], G = b.countersHost[3];
+    const uint32_t Gc     = (uint32_t)std::min<uint64_t>(G, cap);
+    if (res.label) FOF_HIP(hipMemcpyAsync(res.label, b.label, (size_t)n * sizeof(uint64_t), kind, s));
+    if (res.numGroups)
+    {
+        // [selected, all]: the counters hold them the other way round
+        FOF_HIP(hipMemcpyAsync(res.numGroups, b.counters + 3, sizeof(uint64_t), kind, s));
+        FOF_HIP(hipMemcpyAsync(res.numGroups + 1, b.counters + 2, sizeof(uint64_t), kind, s));
+    }
+
+    // ---- catalogue
+    if (Gc)
+    {
+        b.selLabelSorted = arena.get<uint64_t>("fof.selLabelSorted", n);
+        b.selRootSorted  = arena.get<uint32_t>("fof.selRootSorted", n);
+        b.selKey         = arena.get<uint32_t>("fof.selKey", n);
+        b.selKeySorted   = arena.get<uint32_t>("fof.selKeySorted", n);
+        b.selPos         = arena.get<uint32_t>("fof.selPos", n);
+        b.selPosSorted   = arena.get<uint32_t>("fof.selPosSorted", n);
+        b.segCount       = arena.get<uint32_t>("fof.segCount", n);
+        b.segStart       = arena.get<uint32_t>("fof.segStart", n);
+        b.outLabel       = arena.get<uint64_t>("fof.outLabel", n);
+        b.outCount       = arena.get<uint32_t>("fof.outCount", n);
+        if (!b.selLabelSorted || !b.selRootSorted || !b.selKey || !b.selKeySorted || !b.selPos || !b.selPosSorted ||
+            !b.segCount || !b.segStart || !b.outLabel || !b.outCount)
+        {
+            err = "sx_fof: catalogue buffers";
+            return SX_ERR_NOMEM;
+        }
+        // by label ascending, then (stable) by count descending
+        FOF_HIP(hipcub::DeviceRadixSort::SortPairs(b.sortTmp, tmpBytes, (const uint64_t*)b.selLabel, b.selLabelSorted,
+                                                   (const uint32_t*)b.selRoot, b.selRootSorted, (int)G, 0, 64, s));
+        selKeyKernel<<<blocks(G), kBlock, 0, s>>>(b.selRootSorted, b.count, (uint32_t)G, b.selKey, b.selPos);
+        FOF_HIP(hipcub::DeviceRadixSort::SortPairs(b.sortTmp, tmpBytes, (const uint32_t*)b.selKey, b.selKeySorted,
+                                                   (const uint32_t*)b.selPos, b.selPosSorted, (int)G, 0, 32, s));
+        rankKernel<<<blocks(Gc), kBlock, 0, s>>>(b.selPosSorted, b.selRootSorted, b.selLabelSorted, b.count, Gc, b.rankOf,
+                                                 b.outLabel, b.outCount, b.segCount);
+        if (res.groupLabel) FOF_HIP(hipMemcpyAsync(res.groupLabel, b.outLabel, (size_t)Gc * sizeof(uint64_t), kind, s));
+        if (res.groupCount) FOF_HIP(hipMemcpyAsync(res.groupCount, b.outCount, (size_t)Gc * sizeof(uint32_t), kind, s));
+        if (wantReal)
+        {
+            b.idKeysSorted = arena.get<uint64_t>("fof.idKeysSorted", n);
+            b.memById      = arena.get<uint32_t>("fof.memById", n);
+            b.memKey       = arena.get<uint32_t>("fof.memKey", n);
+            b.memKeySorted = arena.get<uint32_t>("fof.memKeySorted", n);
+            b.memSorted    = arena.get<uint32_t>("fof.memSorted", n);
+            b.outReal      = arena.get<double>("fof.outReal", 7 * (size_t)n);
+            if (!b.idKeysSorted || !b.memById || !b.memKey || !b.memKeySorted || !b.memSorted || !b.outReal)
+            {
+                err = "sx_fof: member buffers";
+                return SX_ERR_NOMEM;
+            }
+            FOF_HIP(hipcub::DeviceScan::ExclusiveSum(b.sortTmp, tmpBytes, (const uint32_t*)b.segCount, b.segStart,
+                                                     (int)Gc, s));
+            // the members by id ascending, then (stable) by group: the catalogue groups' segments lead
+            FOF_HIP(hipcub::DeviceRadixSort::SortPairs(b.sortTmp, tmpBytes, (const uint64_t*)b.idKeys, b.idKeysSorted,
+                                                       (const uint32_t*)b.mem, b.memById, (int)n, 0, 64, s));
+            memKeyKernel<<<blocks(n), kBlock, 0, s>>>(b.memById, b.root, b.rankOf, n, Gc, b.memKey);
+            FOF_HIP(hipcub::DeviceRadixSort::SortPairs(b.sortTmp, tmpBytes, (const uint32_t*)b.memKey, b.memKeySorted,
+                                                       (const uint32_t*)b.memById, b.memSorted, (int)n, 0,
+                                                       std::max(1, bitLength(Gc)), s));
+            ReduceArgs ra{b.memSorted, b.segStart, b.outCount, b.order, b.xs, b.ys, b.zs, f.m, f.vx, f.vy, f.vz, first, Gc, g,
+                          b.outReal};
+            reduceKernel<<<Gc, kBlock, 0, s>>>(ra);
+            if (res.groupMass) FOF_HIP(hipMemcpyAsync(res.groupMass, b.outReal, (size_t)Gc * sizeof(double), kind, s));
+            if (res.groupCom)
+                FOF_HIP(hipMemcpyAsync(res.groupCom, b.outReal + Gc, 3 * (size_t)Gc * sizeof(double), kind, s));
+            if (res.groupVel)
+                FOF_HIP(hipMemcpyAsync(res.groupVel, b.outReal + 4 * (size_t)Gc, 3 * (size_t)Gc * sizeof(double), kind, s));
+        }
+    }
+    if (b.timing) FOF_HIP(hipEventRecord(b.ev[4], s));
+    FOF_HIP(hipGetLastError());
+    FOF_HIP(hipStreamSynchronize(s));
+    if (b.timing)
+        for (int k = 0; k < 4; ++k)
+            if (hipEventElapsedTime(&b.ms[k], b.ev[k], b.ev[k + 1]) != hipSuccess) b.ms[k] = 0;
+    b.stats[0] = b.countersHost[0], b.stats[1] = b.countersHost[1], b.stats[2] = numAll, b.stats[3] = G;
+    b.done     = true;
+    return SX_OK;
+}
+
+void release(FofBuffers& b)
+{
+    for (auto& e : b.ev)
+        if (e) (void)hipEventDestroy(e), e = nullptr;
+}
+
+} // namespace sx::fof

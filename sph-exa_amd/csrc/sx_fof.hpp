@@ -1,0 +1,78 @@
+/*! @file sx_fof.hpp
+ * @brief Friends-of-friends groups of the particles (sx_fof.hip, sx_sim_fof.cpp).  The definitions -- link criterion,
+ *        groups, labels, catalogue, order of the sums -- are the header comment of the section in include/sphexa_hip.h;
+ *        this file holds the grid decision, shared by the host entry points and the launcher, and the typed owner of
+ *        the scratch.
+ *
+ * The grid.  Cells of edge > linking length, x-fastest key cx + dx (cy + dy cz), particles sorted by key: the 27 cells
+ * around a target are nine x-runs of up to three cells, each one contiguous range of the sorted particles (a run that
+ * wraps round a periodic x axis adds the cell at the far end as a range of its own).  The cell count is capped at
+ * max(27, 2 n), so a sparse set gets cells wider than the linking length instead of a start array larger than its columns.
+ *
+ * Union-find.  parent[] over the sorted indices, parent[i] <= i always.  A link hooks the larger root under the smaller
+ * with a compare-and-swap that expects the larger to be a root still; a loser starts again from what it found there.
+ * Every store to parent[] lowers it to an ancestor, so there is no cycle, a walk to the root ends, and nobody waits for
+ * another wave.  The root of a component is its smallest sorted index; the label is found afterwards.
+ */
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+
+#include "../../include/sphexa_hip.h"
+#include "sx_tree.hpp"
+
+namespace sx::fof
+{
+
+constexpr uint32_t kMaxDim       = 1024;          //!< cells per axis: keys stay below 2^30
+constexpr uint64_t kMaxParticles = 0x7fffffffull; //!< sorted indices and hipcub's item counts are ints
+constexpr int      kBlock        = 256;
+constexpr uint32_t kNoGroup      = 0xffffffffu;
+
+//! the reason sx_fof_check refuses, with its figures; empty: accepted
+std::string checkSpec(const sx_fof* p, const sx_box* box);
+//! the cell grid of sx_fof_grid; p and box have passed checkSpec
+void chooseGrid(const sx_fof& p, const sx_box& box, uint64_t n, uint32_t dims[3]);
+
+/*! the typed owner of the scratch and the last call's figures.  Every "fof.*" arena tag is requested at one site in
+ *  sx_fof.hip, which stores the pointer here. */
+struct FofBuffers
+{
+    // grid
+    uint32_t *keys{nullptr}, *keysSorted{nullptr}, *idx{nullptr}, *order{nullptr}; // order[s]: column index - first
+    uint32_t *cellCount{nullptr}, *cellStart{nullptr};                              // cells + 1
+    double *  xs{nullptr}, *ys{nullptr}, *zs{nullptr};                              // sorted coordinates
+    void*     sortTmp{nullptr};
+    // union-find and labels, by sorted index; count, minId and rankOf are read at the roots
+    uint32_t *parent{nullptr}, *root{nullptr}, *count{nullptr}, *rankOf{nullptr};
+    uint64_t *minId{nullptr}, *label{nullptr};
+    // catalogue: the selected roots, and the members by (group, id)
+    uint64_t *selLabel{nullptr}, *selLabelSorted{nullptr}, *idKeys{nullptr}, *idKeysSorted{nullptr};
+    uint32_t *selRoot{nullptr}, *selRootSorted{nullptr}, *selKey{nullptr}, *selKeySorted{nullptr}, *selPos{nullptr},
+        *selPosSorted{nullptr};
+    uint32_t *mem{nullptr}, *memById{nullptr}, *memKey{nullptr}, *memKeySorted{nullptr}, *memSorted{nullptr};
+    uint32_t *segCount{nullptr}, *segStart{nullptr};
+    uint64_t* outLabel{nullptr};
+    uint32_t* outCount{nullptr};
+    double*   outReal{nullptr}; // [mass G | com 3 G | vel 3 G]
+    uint64_t *counters{nullptr}, *countersHost{nullptr}; // pair tests, union retries, all groups, selected groups
+    bool       timing{false}, done{false};
+    float      ms[4]{};
+    uint64_t   stats[4]{};
+    hipEvent_t ev[5]{};
+};
+
+/*! all stages over [first, last) of f; the results go to the non-null arrays of res, device pointers (toHost false) or
+ *  host pointers (true).  Synchronises after the compress stage (the number of groups sizes the catalogue's sorts) and
+ *  at the end. */
+int compute(Arena& arena, FofBuffers& b, const sx_fof& p, const sx_fields& f, const sx_box& box, uint32_t first,
+            uint32_t last, const uint64_t* id, const sx_fof_result& res, bool toHost, hipStream_t s, std::string& err);
+//! the reason a call on [first, last) of f is refused, or empty: checkSpec, the columns, the range, the capacity
+std::string whyRefused(const sx_fof* p, const sx_box* box, const sx_fields* f, uint32_t first, uint32_t last,
+                       const sx_fof_result* res);
+void release(FofBuffers& b);
+
+} // namespace sx::fof

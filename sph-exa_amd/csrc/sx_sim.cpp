@@ -1029,6 +1029,7 @@ extern "C"
         sx::pairbin::release(s->mapBuf.bin);
         sx::pairbin::release(s->specBuf.bin);
         sx::profile::release(s->profBuf);
+        sx::fof::release(s->fofBuf);
         delete s;
     }
 

@@ -19,6 +19,7 @@
 #include "sx_hydro.hpp"
 #include "sx_map.hpp"
 #include "sx_profile.hpp"
+#include "sx_fof.hpp"
 #include "sx_spectrum.hpp"
 #include "sx_step_timer.hpp"
 #include "sx_tree.hpp"
@@ -273,6 +274,7 @@ struct sx_sim
     sx::map::MapBuffers  mapBuf; // sx_sim_render: the device images and the pair scratch (in `work`, from the first render on)
     sx::spectrum::SpecBuffers specBuf; // sx_sim_spectrum: meshes, tables and pair scratch (in `work`, from the first call on)
     sx::profile::ProfBuffers profBuf; // sx_sim_profile: accumulators, edges, tables and the pinned result (in `work`, from the first call on)
+    sx::fof::FofBuffers fofBuf; // sx_sim_fof: grid, union-find and catalogue scratch (in `work`, from the first call on)
     sx::turb::SimTurb* turb{nullptr}; // turbulence stirring (sx_sim_set_turbulence), VE propagator on one rank
 
     // the observable of sx_sim_observe (observablesFactory, main/src/observables/factory.hpp:46-69)

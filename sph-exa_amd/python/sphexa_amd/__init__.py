@@ -416,6 +416,57 @@ def profile_dict(spec, res):
     return out
 
 
+class SxFof(C.Structure):
+    """sx_fof: the absolute linking length, the smallest group the catalogue lists, the catalogue's capacity"""
+    _fields_ = [("linking", C.c_double), ("minMembers", C.c_uint32), ("maxGroups", C.c_uint32)]
+
+    def __init__(self, linking=0.0, min_members=20, max_groups=4096):
+        super().__init__(float(linking), int(min_members), int(max_groups))
+
+
+class SxFofResult(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("label", "groupLabel", "groupCount", "groupMass", "groupCom", "groupVel",
+                                          "numGroups")]
+
+
+def fof_check(spec, box):
+    """sx_fof_check: raises SxError with the reason for a specification a call would refuse.  Needs no GPU."""
+    if lib().sx_fof_check(C.byref(spec) if spec is not None else None, C.byref(box) if box is not None else None) != SX_OK:
+        raise SxError(lib().sx_last_error(None).decode())
+
+
+def fof_grid(spec, box, n):
+    """the cells per axis a call on n particles uses (sx_fof_grid).  Needs no GPU."""
+    dims = (C.c_uint32 * 3)()
+    if lib().sx_fof_grid(C.byref(spec) if spec is not None else None, C.byref(box) if box is not None else None,
+                         int(n), dims) != SX_OK:
+        raise SxError(lib().sx_last_error(None).decode())
+    return tuple(int(d) for d in dims)
+
+
+def _fof_arrays(n, cap, labels):
+    """host arrays of a group-finder call: name -> (array, sx_fof_result member)"""
+    out = {"group_label": (np.zeros(max(1, cap), np.uint64), "groupLabel"),
+           "count": (np.zeros(max(1, cap), np.uint32), "groupCount"),
+           "mass": (np.zeros(max(1, cap), np.float64), "groupMass"),
+           "com": (np.zeros((max(1, cap), 3), np.float64), "groupCom"),
+           "vel": (np.zeros((max(1, cap), 3), np.float64), "groupVel"),
+           "num": (np.zeros(2, np.uint64), "numGroups")}
+    if labels:
+        out["label"] = (np.zeros(max(1, n), np.uint64), "label")
+    return out
+
+
+def _fof_dict(arr, n, cap):
+    """the dict Context.fof and Sim.fof return from the filled arrays of _fof_arrays"""
+    num = arr["num"][0]
+    k = min(int(num[0]), int(cap))
+    out = {"num_groups": int(num[0]), "num_all": int(num[1]), "label": arr["label"][0][:n] if "label" in arr else None}
+    for key in ("group_label", "count", "mass", "com", "vel"):
+        out[key] = arr[key][0][:k]
+    return out
+
+
 class SxOctree(C.Structure):
     _fields_ = [("prefixes", _P), ("childOffsets", _P), ("parents", _P), ("levelRange", _P),
                 ("internalToLeaf", _P), ("leafToInternal", _P)]
@@ -655,6 +706,15 @@ def lib():
         "sx_profile_times": (C.c_int, [vp, C.POINTER(C.c_double)]),
         "sx_sim_profile": (C.c_int, [vp, C.POINTER(SxProfile), C.POINTER(SxProfileResult)]),
         "sx_sim_profile_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        "sx_fof_check": (C.c_int, [C.POINTER(SxFof), C.POINTER(SxBox)]),
+        "sx_fof_grid": (C.c_int, [C.POINTER(SxFof), C.POINTER(SxBox), C.c_uint64, C.POINTER(u32)]),
+        "sx_fof_compute": (C.c_int, [vp, C.POINTER(SxFields), C.POINTER(SxBox), u32, u32, vp, C.POINTER(SxFof),
+                                     C.POINTER(SxFofResult)]),
+        "sx_fof_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        "sx_set_fof_timing": (C.c_int, [vp, C.c_int]),
+        "sx_fof_times": (C.c_int, [vp, C.POINTER(C.c_double)]),
+        "sx_sim_fof": (C.c_int, [vp, C.POINTER(SxFof), C.POINTER(SxFofResult)]),
+        "sx_sim_fof_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     }
     for name, (res, args) in sig.items():
         # a measurement build named by SPHEXA_AMD_LIB (an A/B against an older library) may predate an entry
@@ -1123,6 +1183,46 @@ class Context:
         out = (C.c_double * 4)()
         self.check(self.L.sx_profile_times(self.h, out), "sx_profile_times")
         return {"pass1_ms": out[0], "pass2_ms": out[1], "final_ms": out[2], "pass_bytes": out[3]}
+
+    # ---- friends-of-friends groups ----------------------------------------------------------------------------
+    def fof(self, fields, box, spec, id=None, first=0, last=None, labels=True):
+        """the friends-of-friends groups `spec` (an SxFof) of the particles [first, last) of an SxFields
+        (sx_fof_compute).  id: a DeviceArray of uint64, one per particle of fields, or None (labels are indices then).
+        A dict: label (uint64 per particle of the range, None without labels), num_groups (groups of min_members or
+        more), num_all (all groups, singles included), and the catalogue cut to min(num_groups, maxGroups) entries,
+        ordered by count descending then label ascending: group_label, count, mass, com (k, 3), vel (k, 3)."""
+        last = fields.n if last is None else last
+        n, cap = max(0, int(last) - int(first)), int(spec.maxGroups)
+        if id is not None and id.dtype != np.dtype(np.uint64):
+            raise TypeError("fof: id must be uint64")
+        host = _fof_arrays(n, cap, labels)
+        dev = {k: self.alloc(a.size, a.dtype) for k, (a, _) in host.items()}
+        res = SxFofResult(**{host[k][1]: d.ptr for k, d in dev.items()})
+        try:
+            self.check(self.L.sx_fof_compute(self.h, C.byref(fields), C.byref(box), int(first), int(last),
+                                             id.ptr if id is not None else None, C.byref(spec), C.byref(res)),
+                       "sx_fof_compute")
+            got = {k: (dev[k].get().reshape(a.shape), m) for k, (a, m) in host.items()}
+            return _fof_dict(got, n, cap)
+        finally:
+            for d in dev.values():
+                self.free(d)
+
+    def fof_stats(self):
+        """the last fof(): {pair tests, union retries, all groups, groups of min_members or more}"""
+        out = (C.c_uint64 * 4)()
+        self.check(self.L.sx_fof_stats(self.h, out), "sx_fof_stats")
+        return dict(zip(["pair_tests", "union_retries", "num_all", "num_groups"], [int(v) for v in out]))
+
+    def set_fof_timing(self, on=True):
+        self.check(self.L.sx_set_fof_timing(self.h, 1 if on else 0), "sx_set_fof_timing")
+
+    def fof_times(self):
+        """{grid, link, compress, catalogue} in ms of the last fof() of the context or of a Sim on it (after
+        set_fof_timing); the catalogue's interval includes the host's read of the group count"""
+        out = (C.c_double * 4)()
+        self.check(self.L.sx_fof_times(self.h, out), "sx_fof_times")
+        return {"grid_ms": out[0], "link_ms": out[1], "compress_ms": out[2], "catalogue_ms": out[3]}
 
     def observables(self, fields, kind, first=0, last=None, box=None, settings=None, mui=10.0, gamma=5.0 / 3.0,
                     cap=None):
@@ -1706,6 +1806,32 @@ class Sim:
         out = (C.c_uint64 * 4)()
         self.ctx.check(self.L.sx_sim_profile_stats(self.h, out), "sx_sim_profile_stats")
         return dict(zip(["particles", "lds", "passes", "nonfinite"], [int(v) for v in out]))
+
+    def fof_spec(self, linking=0.2, length=None, min_members=20, max_groups=4096):
+        """the SxFof of fof(): linking in units of the mean interparticle spacing (V_box / N)^(1/3) of the locals,
+        or length, an absolute linking length that overrides it"""
+        if length is None:
+            lim = self.box.lim
+            vol = (lim[1] - lim[0]) * (lim[3] - lim[2]) * (lim[5] - lim[4])
+            length = float(linking) * (vol / max(1, self.size())) ** (1.0 / 3.0)
+        return SxFof(length, min_members, max_groups)
+
+    def fof(self, linking=0.2, length=None, min_members=20, max_groups=4096, labels=False, spec=None):
+        """the friends-of-friends groups of the current state (sx_sim_fof; one rank): the dict of Context.fof.  With
+        labels=True, label[k] belongs to the particle get(["id"])["id"][k]; labels are the smallest id of a group.  The
+        centre of mass is exact for groups narrower than half the box on a periodic axis.  Changes no state."""
+        spec = spec if spec is not None else self.fof_spec(linking, length, min_members, max_groups)
+        n, cap = self.size(), int(spec.maxGroups)
+        arr = _fof_arrays(n, cap, labels)
+        res = SxFofResult(**{m: a.ctypes.data for a, m in arr.values()})
+        self.ctx.check(self.L.sx_sim_fof(self.h, C.byref(spec), C.byref(res)), "sx_sim_fof")
+        return _fof_dict(arr, n, cap)
+
+    def fof_stats(self):
+        """the last fof(): {pair tests, union retries, all groups, groups of min_members or more}"""
+        out = (C.c_uint64 * 4)()
+        self.ctx.check(self.L.sx_sim_fof_stats(self.h, out), "sx_sim_fof_stats")
+        return dict(zip(["pair_tests", "union_retries", "num_all", "num_groups"], [int(v) for v in out]))
 
     def write_constants(self, fileobj):
         """append the row of observe() to a constants.txt (format_constants_row); returns the row"""
