@@ -17,7 +17,18 @@
  *                                         once).  The float sums of one tile and image are folded into double
  *                                         accumulators, so the rounding of the sum does not grow with n.  The origin
  *                                         belongs to the tile, not to the target block: what a target gets does not
- *                                         depend on the view it is part of.
+ *                                         depend on the view it is part of.  Rounding both coordinates relative to
+ *                                         the origin leaves a pair's displacement with an absolute error of up to
+ *                                         2^-24 (|s - o| + |t - o|) <= 2^-24 (2 |t - o| + R), so its force with a
+ *                                         relative error of up to 6.2 * 2^-24 (2 |t - o| / R_eff + 2) (1 for dX,
+ *                                         3 sqrt 3 for R_eff^-3).  Every target
+ *                                         keeps the smallest R_eff it met in the tile; where that is below
+ *                                         |t - o| / kOriginGuard it takes the tile again with displacements formed in
+ *                                         double and rounded once (same float arithmetic).  What stays on the packed
+ *                                         path is within 6.2 * 2^-23 * 17 = 1.3e-5 per pair if all three roundings
+ *                                         align and a third of that in the root mean square (measured: 5.0e-6 of a
+ *                                         target's sum of absolute terms at worst).  The decision belongs to
+ *                                         the target and the tile alone, so views keep their bits.
  *
  * Grid: (blocks of 256 targets per target-per-lane) x (source splits).  Every (block, split) writes its sums to a
  * slab; no atomics, no communication between workgroups.
@@ -173,6 +184,8 @@ hipError_t directCombine(const DirectArgs& a, hipStream_t s)
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 
+constexpr float kOriginGuard = 16.0f; //!< |t - o| / R_eff beyond which a target takes a tile in double (file comment)
+
 /*! NT targets per lane.  LDS per pair of sources P: s_A[P] = {x0, x1, y0, y1}, s_B[P] = {z0, z1, m0, m1},
  *  s_H[P] = {h0, h1}, coordinates relative to the tile's origin.  The padding of the last tile sits at the origin with
  *  m = 0, h = 1 and adds exact zeros. */
@@ -227,7 +240,8 @@ __global__ __launch_bounds__(256) void directFastKernel(DirectArgs a)
             for (int iy = -a.numShells; iy <= a.numShells; ++iy)
                 for (int ix = -a.numShells; ix <= a.numShells; ++ix)
                 {
-                    v2f tx[NT], ty[NT], tz[NT], f2[NT][4];
+                    v2f   tx[NT], ty[NT], tz[NT], f2[NT][4];
+                    float rmin[NT], far2[NT]; // smallest R_eff^2 met, (|t - o| / kOriginGuard)^2
 #pragma unroll
                     for (int t = 0; t < NT; ++t)
                     {
@@ -237,6 +251,8 @@ __global__ __launch_bounds__(256) void directFastKernel(DirectArgs a)
                         const float z = (float)((zi[t] + iz * a.boxL[2]) - oz);
                         tx[t] = v2f{x, x}, ty[t] = v2f{y, y}, tz[t] = v2f{z, z};
                         f2[t][0] = f2[t][1] = f2[t][2] = f2[t][3] = v2f{0.0f, 0.0f};
+                        rmin[t] = INFINITY;
+                        far2[t] = (x * x + y * y + z * z) * (1.0f / (kOriginGuard * kOriginGuard));
                     }
 #pragma unroll 4
                     for (uint32_t P = 0; P < pairs; ++P)
@@ -252,8 +268,9 @@ __global__ __launch_bounds__(256) void directFastKernel(DirectArgs a)
                                 __builtin_elementwise_fma(dx, dx, __builtin_elementwise_fma(dy, dy, dz * dz));
                             const v2f h_ij = th[t] + v2f{H.x, H.y};
                             const v2f hh   = h_ij * h_ij;
-                            const v2f invR = {__builtin_amdgcn_rsqf(fmaxf(R2.x, hh.x)),
-                                              __builtin_amdgcn_rsqf(fmaxf(R2.y, hh.y))};
+                            const v2f Re2  = {fmaxf(R2.x, hh.x), fmaxf(R2.y, hh.y)};
+                            const v2f invR = {__builtin_amdgcn_rsqf(Re2.x), __builtin_amdgcn_rsqf(Re2.y)};
+                            rmin[t]        = fminf(fminf(rmin[t], Re2.x), Re2.y); // one v_min3_f32
                             const v2f invR3m = v2f{B.z, B.w} * invR * invR * invR;
                             f2[t][0] = __builtin_elementwise_fma(-invR3m, R2, f2[t][0]);
                             f2[t][1] = __builtin_elementwise_fma(dx, invR3m, f2[t][1]);
@@ -263,9 +280,38 @@ __global__ __launch_bounds__(256) void directFastKernel(DirectArgs a)
                     }
 #pragma unroll
                     for (int t = 0; t < NT; ++t)
+                    {
+                        if (rmin[t] < far2[t])
+                        {
+                            // a source this close to a target this far from the origin: the tile again, displacements
+                            // formed in double and rounded once (the padding of the last tile is not visited)
+                            const double xt = xi[t] + ix * a.boxL[0], yt = yi[t] + iy * a.boxL[1];
+                            const double zt = zi[t] + iz * a.boxL[2];
+                            float        g[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                            for (uint32_t s = 0; s < cnt; ++s)
+                            {
+                                const float dx = (float)(a.x[j0 + s] - xt), dy = (float)(a.y[j0 + s] - yt);
+                                const float dz = (float)(a.z[j0 + s] - zt);
+                                const float R2   = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+                                const float h_ij = th[t].x + a.h[j0 + s];
+                                const float invR = __builtin_amdgcn_rsqf(fmaxf(R2, h_ij * h_ij));
+                                const float invR3m = a.m[j0 + s] * invR * invR * invR;
+                                g[0] = fmaf(-invR3m, R2, g[0]);
+                                g[1] = fmaf(dx, invR3m, g[1]);
+                                g[2] = fmaf(dy, invR3m, g[2]);
+                                g[3] = fmaf(dz, invR3m, g[3]);
+                            }
 #pragma unroll
-                        for (int c = 0; c < 4; ++c)
-                            acc[t][c] += (double)f2[t][c].x + (double)f2[t][c].y;
+                            for (int c = 0; c < 4; ++c)
+                                acc[t][c] += (double)g[c];
+                        }
+                        else
+                        {
+#pragma unroll
+                            for (int c = 0; c < 4; ++c)
+                                acc[t][c] += (double)f2[t][c].x + (double)f2[t][c].y;
+                        }
+                    }
                 }
     }
 #pragma unroll

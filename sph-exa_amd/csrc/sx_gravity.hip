@@ -18,6 +18,7 @@
  *             summation order differs from the reference's depth-first walk.
  */
 #include <type_traits>
+#include <utility>
 
 #include "sx_gravity.hpp"
 
@@ -29,6 +30,20 @@ namespace
 
 constexpr int kGStack = 320; //!< per-wave traversal stack (entries: node << 4 | quarter mask)
 constexpr int kGList  = 176; //!< per-wave M2P / P2P interaction lists (LDS: 31 KB per workgroup, five per CU)
+/*! the fast variant rounds coordinates to float relative to the wave's origin (lane 0's target) and subtracts: a
+ *  pair's displacement then carries an absolute error of up to d = 2^-23 W per component, W = max |coordinate -
+ *  origin| over the wave's targets and the source, and its force a relative error of up to (1 + 3 sqrt 3) d / R_eff
+ *  (a = m dX / R_eff^3: 1 for dX, 3 sqrt 3 for R_eff^-3).  R_eff of a source against any target of the wave is at
+ *  least h_i + h_j and at least the source's distance to the box around the wave's targets.  A staged chunk in which
+ *  some source has W > kOriginGuard max(h_min + h_j, that distance) is evaluated with displacements formed in double
+ *  and rounded once instead (same float arithmetic): what is left on the fast path is at most
+ *  6.2 * 2^-23 * 8 = 5.9e-6 per pair, inside the 1e-5 the variant is held to.  SFC-sorted inputs whose softening is of
+ *  the order of the spacing never trip it: a far leaf is about as far from the box as from the origin, a near one no
+ *  further from the origin than a few spacings. */
+#ifndef SX_ORIGIN_GUARD
+#define SX_ORIGIN_GUARD 8.0f
+#endif
+constexpr float kOriginGuard = SX_ORIGIN_GUARD;
 
 //! leaf index -> node index (the reference's leafToInternal + numInternalNodes)
 __global__ void leafToNodeKernel(const int32_t* childOffsets, const int32_t* internalToLeaf, int numNodes,
@@ -141,9 +156,19 @@ __device__ __forceinline__ double groupSumD(double v)
     return v;
 }
 
+//! the value of lane T of each 16-lane row, in every lane of the row (DPP row_newbcast: VALU, no LDS round trip)
+template<int T>
+__device__ __forceinline__ double rowShareD(double v)
+{
+    int2 p = *reinterpret_cast<int2*>(&v);
+    p.x    = __builtin_amdgcn_update_dpp(0, p.x, 0x150 + T, 0xF, 0xF, false);
+    p.y    = __builtin_amdgcn_update_dpp(0, p.y, 0x150 + T, 0xF, 0xF, false);
+    return *reinterpret_cast<double*>(&p);
+}
+
 //! fast variant of leafCentersKernel + leafP2MKernel in one launch: 16 lanes per leaf, its particles across them, the
-//! sums in double reduced over the group; the quadrupole's sums are rounded to float once instead of after every
-//! particle.  A thread per leaf walked its
+//! quadrupole's sums in double reduced over the group and rounded to float once instead of after every particle; the
+//! mass center in the reference's order (below).  A thread per leaf walked its
 //! particles with every lane on another leaf, so the loads never coalesced (Evrard 14.1M: 0.75 + 0.76 ms per step;
 //! 16 lanes per leaf in one launch: 0.16).  The leaves' multipoles need only their own centers, so they are formed before
 //! the inner nodes' centers and MAC radii.  Same moments to double / float rounding; the exact variant keeps the
@@ -157,17 +182,21 @@ __global__ __launch_bounds__(256) void leafMomentsWaveKernel(GravArgs a)
     const int t    = threadIdx.x & 15;
     const bool ok  = L < a.numLeaves;
     const uint32_t b = ok ? a.layout[L] : 0u, e = ok ? a.layout[L + 1] : 0u;
-    // mass center (massCenter<double>): the sums reach every lane of the group (xor reduction)
+    // mass center (massCenter<double>): sixteen particles are loaded at a time, their products w x handed round the
+    // group and added by every lane in the reference's order, particle by particle.  The center and with it the MAC
+    // radius are then the exact variant's bit for bit wherever the box lies (a re-ordered sum moves the center by a
+    // few ulp of the coordinate, and |com - geometric center| in setMac by as much in absolute terms)
     double c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-    for (uint32_t i = b + t; i < e; i += 16)
+    for (uint32_t base = b; base < e; base += 16)
     {
-        const double w = (double)a.m[i];
-        c0 += w * a.x[i];
-        c1 += w * a.y[i];
-        c2 += w * a.z[i];
-        c3 += w;
+        const uint32_t i  = base + t;
+        const bool     in = i < e;
+        const double   w  = in ? (double)a.m[i] : 0.0; // past the end: adds +0.0
+        const double   p0 = in ? w * a.x[i] : 0.0, p1 = in ? w * a.y[i] : 0.0, p2 = in ? w * a.z[i] : 0.0;
+        [&]<int... T>(std::integer_sequence<int, T...>) {
+            ((c0 += rowShareD<T>(p0), c1 += rowShareD<T>(p1), c2 += rowShareD<T>(p2), c3 += rowShareD<T>(w)), ...);
+        }(std::make_integer_sequence<int, 16>{});
     }
-    c0 = groupSumD(c0), c1 = groupSumD(c1), c2 = groupSumD(c2), c3 = groupSumD(c3);
     const double invM = (c3 != 0.0) ? 1.0 / c3 : 0.0;
     const double cx = c0 * invM, cy = c1 * invM, cz = c2 * invM;
     // quadrupole about it (P2M; the leaf's particles are read again, from cache)
@@ -372,6 +401,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SX_GRAV_WPE
     __shared__ float4 s_srcF[FAST ? 4 : 1][2][kWave]; // fast P2P: source x, y, z relative to the wave origin, m
     __shared__ __attribute__((aligned(16))) float s_hF[FAST ? 4 : 1][2][kWave];
     __shared__ float4  s_tgt[4][kWave]; // the wave's targets relative to its origin, h
+    __shared__ float4  s_gbox[FAST ? 4 : 1][2]; // fast P2P: the origin guard's target box, extent and softening
     __shared__ uint8_t s_idx[FAST ? 4 : 1][kWave]; // fast M2P: one quarter's accepted entries of the window
     __shared__ uint2   s_rng[FAST ? 4 : 1][FAST ? kGList : 1]; // fast P2P: particle range of each listed leaf
 
@@ -394,6 +424,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SX_GRAV_WPE
     // fast variant: coordinates relative to the wave's first target, formed in double and rounded once
     const double ox = readfirstlaneD(xi), oy = readfirstlaneD(yi), oz = readfirstlaneD(zi); // lane 0's target
     const float  txr = (float)(xi - ox), tyr = (float)(yi - oy), tzr = (float)(zi - oz);
+    // the origin guard's wave-uniform inputs (kOriginGuard): the box around the valid targets relative to the origin
+    // (center, half size), its largest |coordinate| and the targets' smallest softening, in LDS
+    if constexpr (FAST)
+    {
+        const float lx = waveMin(valid ? txr : INFINITY), ux = waveMax(valid ? txr : -INFINITY);
+        const float ly = waveMin(valid ? tyr : INFINITY), uy = waveMax(valid ? tyr : -INFINITY);
+        const float lz = waveMin(valid ? tzr : INFINITY), uz = waveMax(valid ? tzr : -INFINITY);
+        const float hT = waveMin(valid ? hi : INFINITY);
+        if (lane == 0)
+        {
+            const float wT  = fmaxf(fmaxf(fmaxf(-lx, ux), fmaxf(-ly, uy)), fmaxf(-lz, uz));
+            s_gbox[wave][0] = make_float4(0.5f * (ux + lx), 0.5f * (uy + ly), 0.5f * (uz + lz), wT);
+            s_gbox[wave][1] = make_float4(0.5f * (ux - lx), 0.5f * (uy - ly), 0.5f * (uz - lz), hT);
+        }
+    }
 
     // the quarters' target boxes (center, half size): wave-uniform, read by every node test; in LDS (broadcast reads)
     // -- as registers they did not stay scalar and were spilled to scratch inside the traversal loop
@@ -644,6 +689,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SX_GRAV_WPE
             const unsigned cm = jm;
             if constexpr (COUNT) numP2P += (unsigned long long)cn * targetsOf(cm);
             __builtin_amdgcn_wave_barrier();
+            const float rx = (float)(px - oxs), ry = (float)(py - oys), rz = (float)(pz - ozs);
+            // kOriginGuard: some source of the chunk is too far from the origin for its distance to the targets and
+            // the softening in play -- wave-uniform
+            const float4 gc = s_gbox[wave][0], ge = s_gbox[wave][1];
+            const float  gd = fmaxf(fmaxf(fabsf(rx - gc.x) - ge.x, fabsf(ry - gc.y) - ge.y), fabsf(rz - gc.z) - ge.z);
+            const float  gW = fmaxf(fmaxf(fabsf(rx), fabsf(ry)), fmaxf(fabsf(rz), gc.w));
+            const bool   slow = __ballot((uint32_t)lane < cn && gW > kOriginGuard * fmaxf(ge.w + ph, gd)) != 0ull;
+            if (__builtin_expect(slow, 0))
+            {
+                // the chunk in double, over both staging buffers (the other one's chunk has been evaluated)
+                if ((uint32_t)lane < cn) reinterpret_cast<GSrc*>(&s_srcF[wave][0][0])[lane] = GSrc{px, py, pz, pm, ph};
+            }
+            else
             {
                 // source l goes to pair P = 4 (l / 8) + l % 4 as half (l / 4) % 2: the lane of sub s evaluates sources
                 // s + 8j and s + 8j + 4 together; lanes [cn, roundup8(cn)) write massless far-away padding
@@ -653,8 +711,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SX_GRAV_WPE
                     const bool  in = (uint32_t)lane < cn;
                     const int   P = (lane >> 3) * 4 + (lane & 3), hf = (lane >> 2) & 1;
                     float*      d = reinterpret_cast<float*>(&s_srcF[wave][buf][0]) + P * 8 + hf;
-                    d[0] = in ? (float)(px - oxs) : 1e18f, d[2] = in ? (float)(py - oys) : 1e18f;
-                    d[4] = in ? (float)(pz - ozs) : 1e18f, d[6] = in ? pm : 0.0f;
+                    d[0] = in ? rx : 1e18f, d[2] = in ? ry : 1e18f;
+                    d[4] = in ? rz : 1e18f, d[6] = in ? pm : 0.0f;
                     s_hF[wave][buf][P * 2 + hf] = in ? ph : 0.0f;
                 }
             }
@@ -667,6 +725,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SX_GRAV_WPE
             {
                 if (!((cm >> qq) & 1u)) continue;
                 SX_LOAD_QUARTER(qq)
+                if (__builtin_expect(slow, 0))
+                {
+                    // the fast path's layout and float arithmetic, two differences: the quarter's targets are read
+                    // again in double, and a displacement is formed in double and rounded once
+                    if (qok)
+                    {
+                        const uint32_t it = i0 + (uint32_t)(16 * qq + tq);
+                        const double   xt = a.x[it] - (ox - oxs), yt = a.y[it] - (oy - oys), zt = a.z[it] - (oz - ozs);
+                        const GSrc*    sd = reinterpret_cast<const GSrc*>(&s_srcF[wave][0][0]);
+                        float          f[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                        for (uint32_t s = sub; s < cn; s += 4)
+                        {
+                            const GSrc  src = sd[s];
+                            const float dx = (float)(src.x - xt), dy = (float)(src.y - yt), dz = (float)(src.z - zt);
+                            const float R2     = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+                            const float h_ij   = qh + src.h;
+                            const float invR   = __builtin_amdgcn_rsqf(fmaxf(R2, h_ij * h_ij));
+                            const float invR3m = src.m * invR * invR * invR;
+                            f[0] = fmaf(-invR3m, R2, f[0]);
+                            f[1] = fmaf(dx, invR3m, f[1]);
+                            f[2] = fmaf(dy, invR3m, f[2]);
+                            f[3] = fmaf(dz, invR3m, f[3]);
+                        }
+#pragma unroll
+                        for (int c_ = 0; c_ < 4; ++c_)
+                            fq[qq][c_] += f[c_];
+                    }
+                    continue;
+                }
                 if (qok)
                 {
                     // two sources per iteration in packed FP32 (v_pk_add/mul/fma_f32), the padding adds exact zeros

@@ -6,8 +6,10 @@ bit-exact to the reference's ryoanji CPU functions (tests/test_oracle_gravity.py
 * accelerations: each target sees the reference's M2P/P2P set (16-target groups, per-quarter MAC), only the double
   summation order differs: |a - a_ref| <= 1e-6 |a_ref| + 1e-7 max|a|; egrav to 1e-10;
 * golden fixture evrard14 (the reference's own outputs) the same way;
-* the production (fast) traversal evaluates M2P/P2P in float with rsqrt (displacements formed in double, sums in
-  double): |a - a_ref| <= 1e-5 |a_ref| + 1e-6 max|a|, egrav to 1e-6.
+* the production (fast) traversal evaluates M2P/P2P in float with rsqrt.  Targets, sources and M2P centres are rounded
+  to float relative to the wave's origin (lane 0's target) and then subtracted in float; only a chunk that trips
+  kOriginGuard forms its displacements in double (the inputs that need it are in test_gpu_gravity_cases.py).
+  Sums in double: |a - a_ref| <= 1e-5 |a_ref| + 1e-6 max|a|, egrav to 1e-6.
 The exact traversal runs with sx_set_exact(1), like the exact hydro kernels.
 """
 import ctypes as C
