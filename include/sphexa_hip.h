@@ -743,6 +743,108 @@ int sx_fof_stats(sx_ctx* ctx, uint64_t out[4]);
 int sx_set_fof_timing(sx_ctx* ctx, int on);
 int sx_fof_times(sx_ctx* ctx, double out[4]);
 
+/* ---- two-point statistics: pair counts and velocity structure functions (sph-exa_amd/csrc/sx_twopoint.hpp) -------
+ *
+ * Arithmetic. Double precision, every operation rounded on its own (the file is built with -ffp-contract=off), brackets
+ *             as written.  Float columns (v, m) are converted to double first; that conversion is exact.
+ * Particles.  The range [first, last) of f.  A particle whose x, y, z, vx, vy or vz is not finite takes part in no pair
+ *             and is counted once in nonfinite; the same holds for a non-finite m where the mass series (WW) is asked
+ *             for.  The other particles are the finite ones, n_f in number.
+ * Targets.    stride >= 1, phase < stride.  A particle is a target iff key % stride == phase, key being its id where an
+ *             id column is given, else its index in the columns of f (first included, as the labels of sx_fof).
+ *             targets is the number of finite targets.
+ * Pairs.      Every unordered pair {i, j}, i != j, of finite particles with at least one target member enters once.  With
+ *             stride = 1 that is every pair.
+ * Separation. d_a = a_j - a_i; on an axis with bnd == 1 it is the minimum image exactly as sx_fof defines it (L_a added
+ *             or subtracted once where |d_a| > L_a / 2), on the other axes the plain difference.
+ *             r2 = (dx^2 + dy^2) + dz^2 and r = sqrt(r2).  A pair with r2 == 0 enters no bin and is counted in
+ *             coincident.
+ * Bins.       edges[0 .. nbins], finite, strictly ascending, edges[0] >= 0, nbins <= 256.  A pair belongs to bin b iff
+ *             edges[b] <= r < edges[b + 1]: the bin of np.searchsorted(edges, r, "right") - 1.  Pairs outside
+ *             [edges[0], edges[nbins]) enter nothing; there are no underflow and overflow bins, because pairs beyond
+ *             r_max = edges[nbins] are never enumerated.
+ * Pair terms. dv_a = v_a,j - v_a,i;  u = ((dvx dx + dvy dy) + dvz dz) / r, the longitudinal velocity difference.  It is
+ *             symmetric under i <-> j (both factors change sign, and IEEE products and sums are sign-symmetric), so
+ *             "unordered" is well defined.
+ * Series.     Per bin:  count = the number of pairs (u64, exact);  U1 = sum u;  U2 = sum u u;  U3 = sum (u u) u;
+ *             A3 = sum |(u u) u|;  T2 = sum ((dvx^2 + dvy^2) + dvz^2);  WW = sum m_i m_j (the product of two floats in
+ *             double is exact).  The flag word `series` selects which are computed; count is always on, and a call
+ *             without velocity series loads no velocity per pair.
+ * Exact sums. The format of the profiles (above) with a window that is known before the pair pass, so that the pairs are
+ *             walked once.  vmax = the largest of |vx|, |vy|, |vz| over the finite particles of the range, ev = the
+ *             smallest integer with vmax < 2^ev (-1074 where vmax is 0), Eu = ev + 2.  The windows: E(U1) = Eu,
+ *             E(U2) = E(T2) = 2 Eu, E(U3) = E(A3) = 3 Eu.  They bound every term: |u| <= |dv| <= sqrt(3) 2^(ev + 1)
+ *             = 0.87 2^Eu, and the margin covers the roundings.  mmax and em likewise over |m|, E(WW) = 2 em.
+ *             fixed(t) = sign(t) floor(|t| 2^(64 - E)), made by shifting the mantissa; a 128-bit two's-complement sum per
+ *             bin and series; one rounding to the nearest double at the end (ties to even, subnormals included), built
+ *             bit by bit as sx_profile_from_fixed does.  A term is below 2^64 in magnitude (a product that underflows
+ *             may round up to 2^E itself, i.e. to 2^64: still far inside the 128 bits) and a bin holds fewer than 2^62
+ *             pairs (n <= 2^31 - 1), so no sum can overflow whatever the input.  A sum differs from the real sum of
+ *             its rounded terms by less than count 2^(E - 64).
+ * Result.     Only integers are added: the result does not depend on launch shape, atomics order or run, and with an id
+ *             column not on the order of storage either.
+ * One rank.   Pairs across a rank boundary need halos of width r_max: sx_sim_twopoint refuses a sim with a communicator
+ *             of more than one rank. */
+#define SX_TP_U1 1u
+#define SX_TP_U2 2u
+#define SX_TP_U3 4u
+#define SX_TP_A3 8u
+#define SX_TP_T2 16u
+#define SX_TP_WW 32u
+#define SX_TP_VEL (SX_TP_U1 | SX_TP_U2 | SX_TP_U3 | SX_TP_A3 | SX_TP_T2)
+#define SX_TP_ALL (SX_TP_VEL | SX_TP_WW)
+#define SX_TP_MAX_BINS 256
+typedef struct sx_twopoint
+{
+    const double* edges;  /* host, nbins + 1 */
+    uint32_t      nbins;
+    uint32_t      series; /* SX_TP_* flags; count is always computed */
+    uint32_t      stride, phase;
+} sx_twopoint;
+/*! every pointer nullable (then not written); device pointers for sx_twopoint_compute, host pointers for
+ *  sx_sim_twopoint.  A series whose flag is not set is not written either. */
+typedef struct sx_twopoint_result
+{
+    uint64_t* count;                     /* [nbins] */
+    double *  U1, *U2, *U3, *A3, *T2, *WW; /* [nbins] each */
+    uint64_t* totals;                    /* [3]: targets, nonfinite, coincident */
+} sx_twopoint_result;
+/*! host only, needs no GPU: SX_OK, or SX_ERR_ARG with the reason and its figures in sx_last_error(NULL) (per thread).
+ *  Refused, each with its own message: a NULL argument, nbins of 0 or above 256, an edge that is not finite, edges that
+ *  do not ascend strictly, a negative first edge, stride == 0, phase >= stride, unknown series flags, r_max above a third
+ *  of the box length on a periodic axis (three distinct cells and an unambiguous minimum image need it). */
+int sx_twopoint_check(const sx_twopoint* tp, const sx_box* box);
+/*! host only: the cell grid a call on n particles uses: the rule of sx_fof_grid with r_max = edges[nbins] in the place
+ *  of the linking length.  SX_ERR_ARG: whatever sx_twopoint_check refuses. */
+int sx_twopoint_grid(const sx_twopoint* tp, const sx_box* box, uint64_t n, uint32_t dims[3]);
+/*! the series of the particles [first, last) of f (x, y, z, vx, vy, vz; m for WW: no other column is read, so the
+ *  gravity-only layout serves) into the device arrays of deviceOut.  id: device, f->n entries, or NULL.  Stages: the cell
+ *  grid of sx_fof (keys, count, sort); one pass over the particles for the windows, nonfinite and targets (integer maxima
+ *  on exponent keys) and a gather into the sorted order; the pair kernel (a lane per sorted particle, every unordered
+ *  pair visited once from its earlier member, the bins as 128-bit integers in block-private LDS, 64-bit integer atomics
+ *  only); the conversion.  The scratch lives in the context under the tags twopoint.*, about 90 bytes per particle.
+ *  SX_ERR_ARG: whatever sx_twopoint_check refuses, missing columns, first > last or last > f->n, more than 2^31 - 1
+ *  particles.  Synchronises. */
+int sx_twopoint_compute(sx_ctx* ctx, const sx_fields* f, const sx_box* box, uint32_t first, uint32_t last,
+                        const uint64_t* id, const sx_twopoint* tp, const sx_twopoint_result* deviceOut);
+/*! the context's last call: {pairs tested (separations evaluated: both members finite, one a target, the later one in
+ *  the 27 cells round the earlier), pairs binned, targets, nonfinite, coincident}; SX_ERR_ARG before the first */
+int sx_twopoint_stats(sx_ctx* ctx, uint64_t out[5]);
+/*! measurement: with on != 0 the following calls time their stages with HIP events; sx_twopoint_times: {grid,
+ *  windows + gather, pairs, conversion} in ms of the last call */
+int sx_set_twopoint_timing(sx_ctx* ctx, int on);
+int sx_twopoint_times(sx_ctx* ctx, double out[4]);
+/*! host only, the number format of the exact sums (shift 64): *E = the smallest integer with max |t| < 2^E over the n
+ *  terms (-1074 where every term is 0); SX_ERR_ARG for a term that is not finite */
+int sx_twopoint_window(const double* t, size_t n, int32_t* E);
+/*! host only: sign(t[i]) floor(|t[i]| 2^(64 - E)) as two words, lohi[2 i] the low and lohi[2 i + 1] the high half of the
+ *  128-bit two's-complement integer; SX_ERR_ARG for a term that is not finite or above 2^E in magnitude */
+int sx_twopoint_to_fixed(const double* t, size_t n, int32_t E, uint64_t* lohi);
+/*! host only: acc (low, high) += the n integers of lohi, modulo 2^128 */
+int sx_twopoint_add_fixed(uint64_t acc[2], const uint64_t* lohi, size_t n);
+/*! host only: *out = the double nearest (ties to even) to acc * 2^(E - 64), subnormals included */
+int sx_twopoint_from_fixed(const uint64_t acc[2], int32_t E, double* out);
+
 /* ---- self-gravity: ryoanji MultipoleHolder seam (multipole_holder.cuh:40-66, gravity_wrapper.hpp:104-174) ----- */
 /*! expansion centers (mass centers, {x,y,z,mac^2}, numNodes x 4 doubles; mac = 2 max(node size)/theta + |com-geo|,
  *  setMac, source_center.hpp:130-143) and Cartesian quadrupoles (numNodes x 8 floats, Cqi order,
@@ -1036,6 +1138,15 @@ int    sx_sim_profile_stats(sx_sim* sim, uint64_t out[4]);
  *  sim's last call. */
 int    sx_sim_fof(sx_sim* sim, const sx_fof* fof, const sx_fof_result* hostOut);
 int    sx_sim_fof_stats(sx_sim* sim, uint64_t out[4]);
+/*! sx_twopoint_compute of the locals of the current state with the sim's id column, into the host arrays of hostOut
+ *  through a pinned buffer; synchronises.  Reads x, y, z, vx, vy, vz, m and id only: every propagator, the gravity-only
+ *  one included, under ve-bdt between any two substeps; nothing in sx_sim_step calls it and it changes no field and no
+ *  scalar.  The buffers live in the sim's arena under the tags twopoint.*, are allocated by the first call and counted
+ *  by sx_sim_memory from then on.  A sim with a communicator of more than one rank is refused on every rank before any
+ *  collective (SX_ERR_ARG): pairs across rank boundaries are not counted.  sx_sim_twopoint_stats: sx_twopoint_stats of
+ *  the sim's last call. */
+int    sx_sim_twopoint(sx_sim* sim, const sx_twopoint* tp, const sx_twopoint_result* hostOut);
+int    sx_sim_twopoint_stats(sx_sim* sim, uint64_t out[5]);
 /*! device time (ms) of each hot kernel alone in the last step (HIP events on the launch stream, bracketing just the
  *  launch): findNeighbors, xmass, veDefGradh, iadDivvCurlv, avSwitches, momentumEnergy */
 int    sx_sim_kernel_times(sx_sim* sim, float* ms, int cap, const char** names);

@@ -23,6 +23,7 @@
 #include "sx_observables.hpp"
 #include "sx_profile.hpp"
 #include "sx_fof.hpp"
+#include "sx_twopoint.hpp"
 #include "sx_spectrum.hpp"
 #include "sx_tree.hpp"
 #include "sx_timestep.hpp"
@@ -131,6 +132,7 @@ struct sx_ctx
     sx::spectrum::SpecBuffers specBuf;   // scratch, per-n tables, meshes and figures of the spectra
     sx::profile::ProfBuffers profBuf;    // accumulators, uploaded edges and tables and figures of the profiles
     sx::fof::FofBuffers fofBuf;          // grid, union-find and catalogue scratch and figures of the group finder
+    sx::twopoint::TwoPointBuffers tpBuf; // grid, sorted columns and accumulators of the two-point statistics
     float2*     wh{nullptr};
     float2*     whd{nullptr};
     double      K{0};
@@ -203,6 +205,7 @@ extern "C"
     void          sx_ctx_set_error_internal(sx_ctx* c, const char* msg) { fail(c, SX_ERR_ARG, msg); }
     uint32_t      sx_ctx_pack12_max_internal(sx_ctx* c) { return c->packMax(); }
     sx::fof::FofBuffers* sx_ctx_fof_buffers_internal(sx_ctx* c) { return &c->fofBuf; }
+    sx::twopoint::TwoPointBuffers* sx_ctx_twopoint_buffers_internal(sx_ctx* c) { return &c->tpBuf; }
 
     int sx_set_pack12_max(sx_ctx* c, uint32_t maxUnion)
     {
@@ -277,6 +280,7 @@ extern "C"
         sx::pairbin::release(c->specBuf.bin);
         sx::profile::release(c->profBuf);
         sx::fof::release(c->fofBuf);
+        sx::twopoint::release(c->tpBuf);
         c->arena.release();
         if (c->own) (void)hipStreamDestroy(c->own);
         delete c;
@@ -1730,6 +1734,99 @@ extern "C"
         if (!c || !out) return SX_ERR_ARG;
         for (int k = 0; k < 4; ++k)
             out[k] = c->fofBuf.ms[k];
+        return SX_OK;
+    }
+
+    // ---- two-point statistics (sx_twopoint.hpp) ---------------------------------------------------------------------
+    int sx_twopoint_check(const sx_twopoint* p, const sx_box* box)
+    {
+        if (std::string why = sx::twopoint::checkSpec(p, box); !why.empty()) return fail(nullptr, SX_ERR_ARG, why);
+        return SX_OK;
+    }
+
+    int sx_twopoint_grid(const sx_twopoint* p, const sx_box* box, uint64_t n, uint32_t dims[3])
+    {
+        if (!dims) return fail(nullptr, SX_ERR_ARG, "sx_twopoint_grid: null dims");
+        if (std::string why = sx::twopoint::checkSpec(p, box); !why.empty()) return fail(nullptr, SX_ERR_ARG, why);
+        sx::twopoint::chooseGrid(*p, *box, n, dims);
+        return SX_OK;
+    }
+
+    int sx_twopoint_compute(sx_ctx* c, const sx_fields* f, const sx_box* box, uint32_t first, uint32_t last,
+                            const uint64_t* id, const sx_twopoint* p, const sx_twopoint_result* res)
+    {
+        if (!c) return SX_ERR_ARG;
+        if (std::string why = sx::twopoint::whyRefused(p, box, f, first, last, res); !why.empty())
+            return fail(c, SX_ERR_ARG, why);
+        std::string err;
+        const int   rc = sx::twopoint::compute(c->arena, c->tpBuf, *p, *f, *box, first, last, id, *res, false, c->stream, err);
+        return rc == SX_OK ? SX_OK : fail(c, rc, err);
+    }
+
+    int sx_twopoint_stats(sx_ctx* c, uint64_t out[5])
+    {
+        if (!c || !out) return SX_ERR_ARG;
+        if (!c->tpBuf.done) return fail(c, SX_ERR_ARG, "sx_twopoint_stats: no pairs have been counted");
+        std::copy(c->tpBuf.stats, c->tpBuf.stats + 5, out);
+        return SX_OK;
+    }
+
+    int sx_set_twopoint_timing(sx_ctx* c, int on)
+    {
+        if (!c) return SX_ERR_ARG;
+        c->tpBuf.timing = on != 0;
+        return SX_OK;
+    }
+
+    int sx_twopoint_times(sx_ctx* c, double out[4])
+    {
+        if (!c || !out) return SX_ERR_ARG;
+        for (int k = 0; k < 4; ++k)
+            out[k] = c->tpBuf.msStage[k];
+        return SX_OK;
+    }
+
+    int sx_twopoint_window(const double* t, size_t n, int32_t* E)
+    {
+        if ((!t && n) || !E) return fail(nullptr, SX_ERR_ARG, "sx_twopoint_window: null terms or E");
+        uint32_t key = 0;
+        for (size_t i = 0; i < n; ++i)
+        {
+            if (!std::isfinite(t[i])) return fail(nullptr, SX_ERR_ARG, "sx_twopoint_window: a term is not finite");
+            key = std::max(key, sx::profile::windowKey(t[i]));
+        }
+        *E = sx::profile::windowOfKey(key);
+        return SX_OK;
+    }
+
+    int sx_twopoint_to_fixed(const double* t, size_t n, int32_t E, uint64_t* lohi)
+    {
+        if ((!t || !lohi) && n) return fail(nullptr, SX_ERR_ARG, "sx_twopoint_to_fixed: null terms or output");
+        for (size_t i = 0; i < n; ++i)
+        {
+            // 2^E itself is let through: a product that underflows may round up to it (include/sphexa_hip.h)
+            if (!std::isfinite(t[i]) || !(std::fabs(t[i]) <= std::ldexp(1.0, E)))
+                return fail(nullptr, SX_ERR_ARG, "sx_twopoint_to_fixed: a term is not finite or above 2^E");
+            const sx::profile::U128 v = sx::profile::toFixedShift(t[i], E, sx::twopoint::kShift);
+            lohi[2 * i] = v.lo, lohi[2 * i + 1] = v.hi;
+        }
+        return SX_OK;
+    }
+
+    int sx_twopoint_add_fixed(uint64_t acc[2], const uint64_t* lohi, size_t n)
+    {
+        if (!acc || (!lohi && n)) return fail(nullptr, SX_ERR_ARG, "sx_twopoint_add_fixed: null accumulator or terms");
+        sx::profile::U128 a{acc[0], acc[1]};
+        for (size_t i = 0; i < n; ++i)
+            sx::profile::addFixed(a, sx::profile::U128{lohi[2 * i], lohi[2 * i + 1]});
+        acc[0] = a.lo, acc[1] = a.hi;
+        return SX_OK;
+    }
+
+    int sx_twopoint_from_fixed(const uint64_t acc[2], int32_t E, double* out)
+    {
+        if (!acc || !out) return fail(nullptr, SX_ERR_ARG, "sx_twopoint_from_fixed: null accumulator or output");
+        *out = sx::profile::fromFixedShift(sx::profile::U128{acc[0], acc[1]}, E, sx::twopoint::kShift);
         return SX_OK;
     }
 

@@ -50,22 +50,7 @@ std::string checkSpec(const sx_fof* p, const sx_box* box)
 
 void chooseGrid(const sx_fof& p, const sx_box& box, uint64_t n, uint32_t dims[3])
 {
-    uint32_t lowest[3];
-    for (int a = 0; a < 3; ++a)
-    {
-        const double L = box.lim[2 * a + 1] - box.lim[2 * a];
-        const double q = std::floor(L / p.linking * (1.0 - 0x1p-20));
-        lowest[a]      = box.bnd[a] == 1 ? 3 : 1;
-        dims[a]        = q >= (double)kMaxDim ? kMaxDim : q >= (double)lowest[a] ? (uint32_t)q : lowest[a];
-    }
-    const uint64_t limit = std::max<uint64_t>(27, 2 * n);
-    while ((uint64_t)dims[0] * dims[1] * dims[2] > limit)
-    {
-        int a = 0;
-        for (int k = 1; k < 3; ++k)
-            if (dims[k] > dims[a]) a = k;
-        dims[a] = std::max(lowest[a], (dims[a] + 1) / 2);
-    }
+    cellgrid::chooseDims(p.linking, box, n, dims);
 }
 
 std::string whyRefused(const sx_fof* p, const sx_box* box, const sx_fields* f, uint32_t first, uint32_t last,
@@ -88,42 +73,8 @@ std::string whyRefused(const sx_fof* p, const sx_box* box, const sx_fields* f, u
 namespace
 {
 
-struct Grid
-{
-    double   lo[3], hi[3], len[3], half[3], inv[3]; // inv: cells per unit length (0 on an axis without extent)
-    uint32_t dims[3];
-    int      pbc[3];
-    double   l2;
-};
-
-__device__ __forceinline__ uint32_t cellOf(double v, const Grid& g, int a)
-{
-    const double t = (v - g.lo[a]) * g.inv[a];
-    if (!(fabs(t) < 1e15)) return 0; // not a number, or far outside: any cell will do, it has no friends
-    long long       c = (long long)floor(t);
-    const long long d = g.dims[a];
-    if (g.pbc[a])
-    {
-        c %= d;
-        if (c < 0) c += d;
-    }
-    else c = c < 0 ? 0 : c > d - 1 ? d - 1 : c;
-    return (uint32_t)c;
-}
-
-__global__ __launch_bounds__(kBlock) void keyKernel(const double* __restrict__ x, const double* __restrict__ y,
-                                                    const double* __restrict__ z, uint32_t first, uint32_t n, Grid g,
-                                                    uint32_t* __restrict__ keys, uint32_t* __restrict__ idx,
-                                                    uint32_t* __restrict__ cellCount)
-{
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const size_t   p   = (size_t)first + i;
-    const uint32_t key = cellOf(x[p], g, 0) + g.dims[0] * (cellOf(y[p], g, 1) + g.dims[1] * cellOf(z[p], g, 2));
-    keys[i]            = key;
-    idx[i]             = i;
-    atomicAdd(cellCount + key, 1u);
-}
+using cellgrid::Grid;
+using cellgrid::minImage;
 
 __global__ __launch_bounds__(kBlock) void gatherKernel(const double* __restrict__ x, const double* __restrict__ y,
                                                        const double* __restrict__ z, uint32_t first, uint32_t n,
@@ -185,16 +136,6 @@ struct LinkArgs
     unsigned long long* counters;
 };
 
-__device__ __forceinline__ double minImage(double d, int pbc, double half, double len)
-{
-    if (pbc)
-    {
-        if (d > half) d -= len;
-        else if (d < -half) d += len;
-    }
-    return d;
-}
-
 /*! one wave per 64 consecutive sorted targets, a lane per target.  A target tests the particles behind it in the sorted
  *  order that lie in the 27 cells around its own, so every unordered pair is tested once. */
 __global__ __launch_bounds__(kBlock) void linkKernel(LinkArgs a)
@@ -206,9 +147,6 @@ __global__ __launch_bounds__(kBlock) void linkKernel(LinkArgs a)
         const Grid&    g  = a.g;
         const double   xi = a.xs[i], yi = a.ys[i], zi = a.zs[i];
         const uint32_t key = a.keys[i];
-        const int      dx = (int)g.dims[0], dy = (int)g.dims[1], dz = (int)g.dims[2];
-        const int      cx = (int)(key % g.dims[0]), cy = (int)((key / g.dims[0]) % g.dims[1]);
-        const int      cz = (int)(key / (g.dims[0] * g.dims[1]));
         uint32_t       ri = i;
         auto scan = [&](uint32_t begin, uint32_t end)
         {
@@ -221,32 +159,7 @@ __global__ __launch_bounds__(kBlock) void linkKernel(LinkArgs a)
                 if (ddx * ddx + ddy * ddy + ddz * ddz < g.l2) ri = unite(a.parent, ri, j, retries);
             }
         };
-        for (int oz = -1; oz <= 1; ++oz)
-        {
-            int zc = cz + oz;
-            if (zc < 0 || zc >= dz)
-            {
-                if (!g.pbc[2]) continue;
-                zc += zc < 0 ? dz : -dz;
-            }
-            for (int oy = -1; oy <= 1; ++oy)
-            {
-                int yc = cy + oy;
-                if (yc < 0 || yc >= dy)
-                {
-                    if (!g.pbc[1]) continue;
-                    yc += yc < 0 ? dy : -dy;
-                }
-                const uint32_t row = (uint32_t)dx * ((uint32_t)yc + (uint32_t)dy * (uint32_t)zc);
-                const int      xl = cx > 0 ? cx - 1 : 0, xh = cx < dx - 1 ? cx + 1 : dx - 1;
-                scan(a.cellStart[row + xl], a.cellStart[row + xh + 1]);
-                if (g.pbc[0]) // three cells or more: the far end is not in the run above
-                {
-                    if (cx == 0) scan(a.cellStart[row + dx - 1], a.cellStart[row + dx]);
-                    else if (cx == dx - 1) scan(a.cellStart[row], a.cellStart[row + 1]);
-                }
-            }
-        }
+        cellgrid::forEachRun(g, key, a.cellStart, scan);
     }
     // the wave's counts in one add each; every lane of the wave arrives here
     for (int o = 32; o > 0; o >>= 1)
@@ -517,17 +430,7 @@ int compute(Arena& arena, FofBuffers& b, const sx_fof& p, const sx_fields& f, co
         return SX_ERR_NOMEM;
     }
 
-    Grid g{};
-    for (int a = 0; a < 3; ++a)
-    {
-        g.lo[a] = box.lim[2 * a], g.hi[a] = box.lim[2 * a + 1];
-        g.len[a]  = g.hi[a] - g.lo[a];
-        g.half[a] = 0.5 * g.len[a];
-        g.dims[a] = dims[a];
-        g.inv[a]  = g.len[a] > 0.0 && std::isfinite(g.len[a]) ? dims[a] / g.len[a] : 0.0;
-        g.pbc[a]  = box.bnd[a] == 1;
-    }
-    g.l2 = p.linking * p.linking;
+    const Grid g = cellgrid::makeGrid(box, dims, p.linking);
     auto* counters = reinterpret_cast<unsigned long long*>(b.counters);
     auto* minId    = reinterpret_cast<unsigned long long*>(b.minId);
     const int keyBits = std::max(1, bitLength(cells - 1));
@@ -535,7 +438,7 @@ int compute(Arena& arena, FofBuffers& b, const sx_fof& p, const sx_fields& f, co
     // ---- grid
     if (b.timing) FOF_HIP(hipEventRecord(b.ev[0], s));
     FOF_HIP(hipMemsetAsync(b.cellCount, 0, ((size_t)cells + 1) * sizeof(uint32_t), s));
-    keyKernel<<<blocks(n), kBlock, 0, s>>>(f.x, f.y, f.z, first, n, g, b.keys, b.idx, b.cellCount);
+    cellgrid::keyKernel<><<<blocks(n), kBlock, 0, s>>>(f.x, f.y, f.z, first, n, g, b.keys, b.idx, b.cellCount);
     FOF_HIP(hipcub::DeviceRadixSort::SortPairs(b.sortTmp, tmpBytes, (const uint32_t*)b.keys, b.keysSorted,
                                                (const uint32_t*)b.idx, b.order, (int)n, 0, keyBits, s));
     FOF_HIP(hipcub::DeviceScan::ExclusiveSum(b.sortTmp, tmpBytes, (const uint32_t*)b.cellCount, b.cellStart,

@@ -4,7 +4,7 @@
  *        this file holds the grid decision, shared by the host entry points and the launcher, and the typed owner of
  *        the scratch.
  *
- * The grid.  Cells of edge > linking length, x-fastest key cx + dx (cy + dy cz), particles sorted by key: the 27 cells
+ * The grid (sx_cellgrid.hpp, shared with the two-point statistics).  Cells of edge > linking length, x-fastest key cx + dx (cy + dy cz), particles sorted by key: the 27 cells
  * around a target are nine x-runs of up to three cells, each one contiguous range of the sorted particles (a run that
  * wraps round a periodic x axis adds the cell at the far end as a range of its own).  The cell count is capped at
  * max(27, 2 n), so a sparse set gets cells wider than the linking length instead of a start array larger than its columns.
@@ -22,12 +22,13 @@
 #include <string>
 
 #include "../../include/sphexa_hip.h"
+#include "sx_cellgrid.hpp"
 #include "sx_tree.hpp"
 
 namespace sx::fof
 {
 
-constexpr uint32_t kMaxDim       = 1024;          //!< cells per axis: keys stay below 2^30
+constexpr uint32_t kMaxDim       = cellgrid::kMaxDim;
 constexpr uint64_t kMaxParticles = 0x7fffffffull; //!< sorted indices and hipcub's item counts are ints
 constexpr int      kBlock        = 256;
 constexpr uint32_t kNoGroup      = 0xffffffffu;

@@ -79,15 +79,17 @@ SX_PROF_HD uint32_t windowKey(double t)
 
 SX_PROF_HD int32_t windowOfKey(uint32_t key) { return (int32_t)key - 1074; }
 
-//! fixed(t) of window E; |t| < 2^E (a larger term would lose its top bits: the callers rule it out)
-SX_PROF_HD U128 toFixed(double t, int32_t E)
+constexpr int kShift = 96; //!< the profile's fixed point: fixed(t) = sign(t) floor(|t| 2^(kShift - E))
+
+//! sign(t) floor(|t| 2^(shift - E)); |t| < 2^(E + 128 - shift - 1) (a larger term would lose its top bits: the callers rule it out)
+SX_PROF_HD U128 toFixedShift(double t, int32_t E, int shift)
 {
     const uint64_t bits = doubleBits(t);
     const uint32_t be   = (uint32_t)((bits >> 52) & 0x7ff);
     const uint64_t frac = bits & 0xfffffffffffffull;
     const uint64_t m    = be ? (frac | (1ull << 52)) : frac;
     const int      e    = be ? (int)be - 1075 : -1074;
-    const int      s    = e + 96 - E;
+    const int      s    = e + shift - E;
     U128           v{0, 0};
     if (m == 0 || s <= -64) return v;
     if (s < 0) v.lo = m >> (-s);
@@ -102,6 +104,9 @@ SX_PROF_HD U128 toFixed(double t, int32_t E)
     return v;
 }
 
+//! fixed(t) of window E; |t| < 2^E
+SX_PROF_HD U128 toFixed(double t, int32_t E) { return toFixedShift(t, E, kShift); }
+
 SX_PROF_HD void addFixed(U128& acc, U128 v)
 {
     const uint64_t lo = acc.lo + v.lo;
@@ -109,8 +114,8 @@ SX_PROF_HD void addFixed(U128& acc, U128 v)
     acc.lo = lo;
 }
 
-//! the double nearest (ties to even) to acc 2^(E - 96), acc a 128-bit two's-complement integer
-SX_PROF_HD double fromFixed(U128 acc, int32_t E)
+//! the double nearest (ties to even) to acc 2^(E - shift), acc a 128-bit two's-complement integer
+SX_PROF_HD double fromFixedShift(U128 acc, int32_t E, int shift)
 {
     const uint64_t sign = acc.hi >> 63;
     if (sign)
@@ -122,9 +127,10 @@ SX_PROF_HD double fromFixed(U128 acc, int32_t E)
     const int len = acc.hi ? 64 + bitLength(acc.hi) : bitLength(acc.lo);
     // bits to drop: down to 53 significant ones, and nothing below 2^-1074
     int drop = len - 53;
-    if (-978 - E > drop) drop = -978 - E;
+    if (shift - 1074 - E > drop) drop = shift - 1074 - E;
+    if (drop > 127) return bitsDouble(sign << 63); // below half of 2^-1074 whatever the 127 bits hold
     uint64_t q;
-    int      exp2 = E - 96; // the value is q 2^exp2
+    int      exp2 = E - shift; // the value is q 2^exp2
     if (drop <= 0) q = acc.lo;
     else
     {
@@ -181,6 +187,8 @@ SX_PROF_HD double fromFixed(U128 acc, int32_t E)
     }
     return bitsDouble(out | (sign << 63));
 }
+
+SX_PROF_HD double fromFixed(U128 acc, int32_t E) { return fromFixedShift(acc, E, kShift); }
 
 //! finite doubles as u64 whose order is the doubles' (min and max per bin through integer atomics)
 SX_PROF_HD uint64_t orderKey(double d)

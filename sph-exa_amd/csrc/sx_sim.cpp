@@ -1030,6 +1030,7 @@ extern "C"
         sx::pairbin::release(s->specBuf.bin);
         sx::profile::release(s->profBuf);
         sx::fof::release(s->fofBuf);
+        sx::twopoint::release(s->tpBuf);
         delete s;
     }
 

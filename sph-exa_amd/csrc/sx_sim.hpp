@@ -20,6 +20,7 @@
 #include "sx_map.hpp"
 #include "sx_profile.hpp"
 #include "sx_fof.hpp"
+#include "sx_twopoint.hpp"
 #include "sx_spectrum.hpp"
 #include "sx_step_timer.hpp"
 #include "sx_tree.hpp"
@@ -275,6 +276,7 @@ struct sx_sim
     sx::spectrum::SpecBuffers specBuf; // sx_sim_spectrum: meshes, tables and pair scratch (in `work`, from the first call on)
     sx::profile::ProfBuffers profBuf; // sx_sim_profile: accumulators, edges, tables and the pinned result (in `work`, from the first call on)
     sx::fof::FofBuffers fofBuf; // sx_sim_fof: grid, union-find and catalogue scratch (in `work`, from the first call on)
+    sx::twopoint::TwoPointBuffers tpBuf; // sx_sim_twopoint: grid, sorted columns and accumulators (in `work`, from the first call on)
     sx::turb::SimTurb* turb{nullptr}; // turbulence stirring (sx_sim_set_turbulence), VE propagator on one rank
 
     // the observable of sx_sim_observe (observablesFactory, main/src/observables/factory.hpp:46-69)

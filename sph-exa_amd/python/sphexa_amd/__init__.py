@@ -467,6 +467,99 @@ def _fof_dict(arr, n, cap):
     return out
 
 
+class SxTwoPoint(C.Structure):
+    """sx_twopoint: the bin edges (kept alive here), the series flags, and the target rule key % stride == phase"""
+    _fields_ = [("edges", C.c_void_p), ("nbins", C.c_uint32), ("series", C.c_uint32), ("stride", C.c_uint32),
+                ("phase", C.c_uint32)]
+
+    def __init__(self, edges=None, series=("count", "vel"), stride=1, phase=0, mass=False):
+        e = np.ascontiguousarray(edges if edges is not None else [], dtype=np.float64)
+        self._keep = e
+        super().__init__(e.ctypes.data if e.size else None, max(0, e.size - 1),
+                         twopoint_flags(series) | (TP_FLAGS["WW"] if mass else 0), int(stride), int(phase))
+
+
+class SxTwoPointResult(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("count", "U1", "U2", "U3", "A3", "T2", "WW", "totals")]
+
+
+TP_SERIES = ("U1", "U2", "U3", "A3", "T2", "WW")
+TP_FLAGS = {k: 1 << i for i, k in enumerate(TP_SERIES)}
+TP_VEL = 31
+
+
+def twopoint_flags(series):
+    """the flag word of a list of series names: "count" (always on), "vel" (the five velocity series), "mass" or one of
+    U1 U2 U3 A3 T2 WW; an integer is passed through"""
+    if isinstance(series, int):
+        return series
+    flags = 0
+    for name in series:
+        if name == "count":
+            continue
+        if name == "vel":
+            flags |= TP_VEL
+        elif name == "mass":
+            flags |= TP_FLAGS["WW"]
+        elif name in TP_FLAGS:
+            flags |= TP_FLAGS[name]
+        else:
+            raise ValueError(f"twopoint: unknown series {name!r}")
+    return flags
+
+
+def twopoint_check(spec, box):
+    """sx_twopoint_check: raises SxError with the reason for a specification a call would refuse.  Needs no GPU."""
+    if lib().sx_twopoint_check(C.byref(spec) if spec is not None else None,
+                               C.byref(box) if box is not None else None) != SX_OK:
+        raise SxError(lib().sx_last_error(None).decode())
+
+
+def twopoint_grid(spec, box, n):
+    """the cells per axis a call on n particles uses (sx_twopoint_grid).  Needs no GPU."""
+    dims = (C.c_uint32 * 3)()
+    if lib().sx_twopoint_grid(C.byref(spec) if spec is not None else None, C.byref(box) if box is not None else None,
+                              int(n), dims) != SX_OK:
+        raise SxError(lib().sx_last_error(None).decode())
+    return tuple(int(d) for d in dims)
+
+
+def _twopoint_arrays(spec):
+    """host arrays of a two-point call: sx_twopoint_result member -> array; the series that are off keep their NaNs"""
+    nb = max(1, int(spec.nbins))
+    out = {"count": np.zeros(nb, np.uint64), "totals": np.zeros(3, np.uint64)}
+    for k in TP_SERIES:
+        out[k] = np.full(nb, np.nan, np.float64)
+    return out
+
+
+def twopoint_dict(spec, arr, box, n):
+    """the dict Context.twopoint and Sim.twopoint return from the filled arrays of _twopoint_arrays over n particles"""
+    nb = int(spec.nbins)
+    edges = spec._keep.copy()
+    count = arr["count"][:nb]
+    targets, nonfinite, coincident = (int(v) for v in arr["totals"])
+    out = {"edges": edges, "count": count, "targets": targets, "nonfinite": nonfinite, "coincident": coincident,
+           "raw": arr}
+    for k in TP_SERIES:
+        out[k] = arr[k][:nb] if spec.series & TP_FLAGS[k] else None
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cnt = count.astype(np.float64)
+        for name, k in (("s1", "U1"), ("s2", "U2"), ("s3", "U3"), ("s3abs", "A3"), ("dv2", "T2")):
+            out[name] = out[k] / cnt if out[k] is not None else None
+    out["ww"] = out["WW"]
+    nf = int(n) - nonfinite
+    out["pairs_expected"] = targets * (nf - 1) - targets * (targets - 1) // 2
+    out["xi"] = None
+    if all(int(b) == 1 for b in box.bnd):
+        lim = box.lim
+        vol = (lim[1] - lim[0]) * (lim[3] - lim[2]) * (lim[5] - lim[4])
+        shell = (4.0 * np.pi / 3.0) * (edges[1:] ** 3 - edges[:-1] ** 3)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["xi"] = cnt / (out["pairs_expected"] * shell / vol) - 1.0
+    return out
+
+
 class SxOctree(C.Structure):
     _fields_ = [("prefixes", _P), ("childOffsets", _P), ("parents", _P), ("levelRange", _P),
                 ("internalToLeaf", _P), ("leafToInternal", _P)]
@@ -715,6 +808,19 @@ def lib():
         "sx_fof_times": (C.c_int, [vp, C.POINTER(C.c_double)]),
         "sx_sim_fof": (C.c_int, [vp, C.POINTER(SxFof), C.POINTER(SxFofResult)]),
         "sx_sim_fof_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        "sx_twopoint_check": (C.c_int, [C.POINTER(SxTwoPoint), C.POINTER(SxBox)]),
+        "sx_twopoint_grid": (C.c_int, [C.POINTER(SxTwoPoint), C.POINTER(SxBox), C.c_uint64, C.POINTER(u32)]),
+        "sx_twopoint_compute": (C.c_int, [vp, C.POINTER(SxFields), C.POINTER(SxBox), u32, u32, vp,
+                                          C.POINTER(SxTwoPoint), C.POINTER(SxTwoPointResult)]),
+        "sx_twopoint_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        "sx_set_twopoint_timing": (C.c_int, [vp, C.c_int]),
+        "sx_twopoint_times": (C.c_int, [vp, C.POINTER(C.c_double)]),
+        "sx_twopoint_window": (C.c_int, [vp, sz, C.POINTER(i32)]),
+        "sx_twopoint_to_fixed": (C.c_int, [vp, sz, i32, vp]),
+        "sx_twopoint_add_fixed": (C.c_int, [vp, vp, sz]),
+        "sx_twopoint_from_fixed": (C.c_int, [vp, i32, C.POINTER(C.c_double)]),
+        "sx_sim_twopoint": (C.c_int, [vp, C.POINTER(SxTwoPoint), C.POINTER(SxTwoPointResult)]),
+        "sx_sim_twopoint_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     }
     for name, (res, args) in sig.items():
         # a measurement build named by SPHEXA_AMD_LIB (an A/B against an older library) may predate an entry
@@ -1223,6 +1329,46 @@ class Context:
         out = (C.c_double * 4)()
         self.check(self.L.sx_fof_times(self.h, out), "sx_fof_times")
         return {"grid_ms": out[0], "link_ms": out[1], "compress_ms": out[2], "catalogue_ms": out[3]}
+
+    # ---- two-point statistics -----------------------------------------------------------------------------------
+    def twopoint(self, fields, box, spec, id=None, first=0, last=None):
+        """the pair counts and velocity structure functions `spec` (an SxTwoPoint) of the particles [first, last) of an
+        SxFields (sx_twopoint_compute).  id: a DeviceArray of uint64, one per particle of fields, or None (targets go
+        by index then).  A dict: edges, count (uint64 per bin), the exact sums U1 U2 U3 A3 T2 WW (None where the series
+        is off), the means s1 s2 s3 s3abs dv2 = sum / count (NaN in an empty bin), ww, targets, nonfinite, coincident,
+        pairs_expected = targets (n_f - 1) - targets (targets - 1) / 2, and in a box periodic on all three axes
+        xi = count / (pairs_expected (4 pi / 3)(e_{b+1}^3 - e_b^3) / V) - 1."""
+        last = fields.n if last is None else last
+        if id is not None and id.dtype != np.dtype(np.uint64):
+            raise TypeError("twopoint: id must be uint64")
+        host = _twopoint_arrays(spec)
+        dev = {k: self.upload(a) for k, a in host.items()}
+        res = SxTwoPointResult(**{k: d.ptr for k, d in dev.items()})
+        try:
+            self.check(self.L.sx_twopoint_compute(self.h, C.byref(fields), C.byref(box), int(first), int(last),
+                                                  id.ptr if id is not None else None, C.byref(spec), C.byref(res)),
+                       "sx_twopoint_compute")
+            got = {k: dev[k].get() for k in host}
+            return twopoint_dict(spec, got, box, max(0, int(last) - int(first)))
+        finally:
+            for d in dev.values():
+                self.free(d)
+
+    def twopoint_stats(self):
+        """the last twopoint(): {pairs tested, pairs binned, targets, nonfinite, coincident}"""
+        out = (C.c_uint64 * 5)()
+        self.check(self.L.sx_twopoint_stats(self.h, out), "sx_twopoint_stats")
+        return dict(zip(["pairs_tested", "pairs_binned", "targets", "nonfinite", "coincident"], [int(v) for v in out]))
+
+    def set_twopoint_timing(self, on=True):
+        self.check(self.L.sx_set_twopoint_timing(self.h, 1 if on else 0), "sx_set_twopoint_timing")
+
+    def twopoint_times(self):
+        """{grid, windows + gather, pairs, conversion} in ms of the last twopoint() of the context or of a Sim on it
+        (after set_twopoint_timing)"""
+        out = (C.c_double * 4)()
+        self.check(self.L.sx_twopoint_times(self.h, out), "sx_twopoint_times")
+        return {"grid_ms": out[0], "window_ms": out[1], "pairs_ms": out[2], "final_ms": out[3]}
 
     def observables(self, fields, kind, first=0, last=None, box=None, settings=None, mui=10.0, gamma=5.0 / 3.0,
                     cap=None):
@@ -1832,6 +1978,27 @@ class Sim:
         out = (C.c_uint64 * 4)()
         self.ctx.check(self.L.sx_sim_fof_stats(self.h, out), "sx_sim_fof_stats")
         return dict(zip(["pair_tests", "union_retries", "num_all", "num_groups"], [int(v) for v in out]))
+
+    def twopoint_spec(self, edges, series=("count", "vel"), stride=1, phase=0, mass=False):
+        """the SxTwoPoint of twopoint(): absolute bin edges, the series ("count", "vel", "mass" or single names), and
+        the targets key % stride == phase on the id column"""
+        return SxTwoPoint(edges, series, stride, phase, mass)
+
+    def twopoint(self, edges=None, series=("count", "vel"), stride=1, phase=0, mass=False, spec=None):
+        """the pair counts and longitudinal velocity structure functions of the current state binned by separation
+        (sx_sim_twopoint; one rank): the dict of Context.twopoint.  stride > 1 takes every stride-th id as a target and
+        counts the pairs with at least one target member.  Changes no state."""
+        spec = spec if spec is not None else self.twopoint_spec(edges, series, stride, phase, mass)
+        arr = _twopoint_arrays(spec)
+        res = SxTwoPointResult(**{k: a.ctypes.data for k, a in arr.items()})
+        self.ctx.check(self.L.sx_sim_twopoint(self.h, C.byref(spec), C.byref(res)), "sx_sim_twopoint")
+        return twopoint_dict(spec, arr, self.box, self.size())
+
+    def twopoint_stats(self):
+        """the last twopoint(): {pairs tested, pairs binned, targets, nonfinite, coincident}"""
+        out = (C.c_uint64 * 5)()
+        self.ctx.check(self.L.sx_sim_twopoint_stats(self.h, out), "sx_sim_twopoint_stats")
+        return dict(zip(["pairs_tested", "pairs_binned", "targets", "nonfinite", "coincident"], [int(v) for v in out]))
 
     def write_constants(self, fileobj):
         """append the row of observe() to a constants.txt (format_constants_row); returns the row"""
