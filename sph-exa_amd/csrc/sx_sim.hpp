@@ -137,6 +137,7 @@ struct SkinBuffers
     // skinReserveSearch (skinSearch)
     float *   rel{nullptr}, *hb{nullptr}, *acc{nullptr};
     uint32_t *sloc{nullptr}, *scnt{nullptr}, *ucountS{nullptr}, *l1{nullptr}, *l2{nullptr}, *l3{nullptr};
+    uint8_t*  dec{nullptr}; // a reuse step's decision per cluster (skinDecide)
     uint32_t* host{nullptr}; // pinned: the list counts read back
     uint8_t * streak{nullptr}, *same{nullptr};
     uint32_t* hitmask{nullptr};

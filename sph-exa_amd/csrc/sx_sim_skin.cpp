@@ -215,6 +215,7 @@ static bool skinReserveSearch(sx_sim* s, const NsArgs& na, uint32_t ncl, bool tw
     B.l1      = M.get<uint32_t>("skin.l1", ncl + 1);
     B.l2      = M.get<uint32_t>("skin.l2", ncl + 1);
     B.l3      = M.get<uint32_t>("skin.l3", ncl + 1);
+    B.dec     = M.get<uint8_t>("skin.dec", ncl);
     B.host    = M.pinned<uint32_t>("skin.host", 4);
     B.streak  = M.get<uint8_t>("skin.streak", ncl);
     B.hitmask = M.get<uint32_t>("skin.hitmask", na.numGroups * (size_t)kSkinMaskWords * kWave);
@@ -224,7 +225,7 @@ static bool skinReserveSearch(sx_sim* s, const NsArgs& na, uint32_t ncl, bool tw
     B.nlocB    = twoSets ? M.get<uint32_t>("skin.nlocB", na.numGroups * (size_t)nlocWords(na.ngmax) * kWave) : nullptr;
     B.ucountB  = twoSets ? M.get<uint32_t>("skin.ucountB", ncl) : nullptr;
     B.hitmaskB = twoSets ? M.get<uint32_t>("skin.hitmaskB", na.numGroups * (size_t)kSkinMaskWords * kWave) : nullptr;
-    return disp && B.rel && B.sloc && B.scnt && B.hb && B.acc && B.ucountS && B.l1 && B.l2 && B.l3 && B.host &&
+    return disp && B.rel && B.sloc && B.scnt && B.hb && B.acc && B.ucountS && B.l1 && B.l2 && B.l3 && B.dec && B.host &&
            B.streak && B.hitmask && B.same && B.frz && (!twoSets || (B.nlocB && B.ucountB && B.hitmaskB));
 }
 
@@ -303,6 +304,17 @@ int skinSearch(sx_sim* s, const NsArgs& na, bool reuse, hipStream_t st, float* x
     // reuse steps: a cluster stale again on the step after its rebuild goes straight to the exact search (l2)
     fa.streak = reuse ? B.streak : nullptr;
     fa.direct = reuse ? l2 : nullptr;
+    if (reuse)
+    {
+        // decide first (every cluster: stale, frozen or walk), then the frozen clusters' XMass over their exact lists
+        // and the walk of the others; a consumer's workgroup leaves at once when its cluster is not marked for it
+        fa.dec = B.dec;
+        // (SX_SKIN_FROZEN_STAGE: a smaller staging, so that small test unions take the path of oversized ones)
+        const char* fs = getenv("SX_SKIN_FROZEN_STAGE");
+        fa.frozenStage = fs ? (uint32_t)std::max(0, atoi(fs)) : (uint32_t)kSkinFrozenCap;
+        SIM_HIP(skinDecide(fa, ncl, st));
+        SIM_HIP(skinFrozen(fa, ncl, st));
+    }
     SIM_HIP(skinFilter(fa, ncl, st));
     SIM_HIP(hipMemcpyAsync(hl, l1, 4, hipMemcpyDeviceToHost, st));
     SIM_HIP(hipMemcpyAsync(hl + 1, l2, 4, hipMemcpyDeviceToHost, st));
@@ -364,6 +376,7 @@ int skinSearch(sx_sim* s, const NsArgs& na, bool reuse, hipStream_t st, float* x
         fa.stale  = early ? l3 : l2;
         fa.streak = nullptr;
         fa.direct = nullptr;
+        fa.dec    = nullptr;
         SIM_HIP(skinFilter(fa, ncl, st));
         SIM_HIP(hipMemcpyAsync(hl + 2, fa.stale, 4, hipMemcpyDeviceToHost, st));
         SIM_HIP(hipStreamSynchronize(st));

@@ -5,7 +5,9 @@
  * The filter replaces the step's search (cstone::findNeighbors + sph::findNeighborsSph, findneighbors.hpp:95-188,
  * find_neighbors.hpp:10-44) for every cluster whose skin is still valid.  One 256-thread workgroup per cluster:
  *   1. validity: each target's drift bound against its skin (sx_skin.hpp); the region's per-step displacement maximum
- *      comes from the grid cells around the wave boxes;
+ *      comes from the grid cells around the wave boxes.  On a reuse step this is a kernel of its own over every cluster
+ *      (skinDecideKernel), which also tests the freeze reference (1b) and marks the clusters stale, frozen or walk;
+ *      2 - 5 (skinFilterKernel) run over the clusters marked walk, or over clusters just built;
  *   2. the cluster's skin union U_s is staged in LDS as float positions relative to the cluster origin (minimum image,
  *      folded in double) with |p|^2, and the global indices;
  *   3. every lane walks its skin list (two u16 positions per word, prefetched) and tests each entry with the packed
@@ -18,7 +20,8 @@
  *      packed12, sx_pack12.hpp, where that union holds at most SkinArgs::packMax entries, else u16 pairs) are written
  *      only by a cluster that completes;
  *   4b. (round 6) a walk whose hit bits equal one of the cluster's two recorded list sets keeps that set (no 5), and a
- *      cluster whose freeze reference proves its hits unchanged is not walked (1b: the XMass over its exact lists).
+ *      cluster whose freeze reference proves its hits unchanged is not walked (1b: the XMass over its exact lists,
+ *      skinFrozenKernel over the clusters marked frozen).
  * This file is compiled with -ffp-contract=off (the double criterion must round like the reference).
  */
 #include "sx_kernel_poly.hpp"
@@ -174,6 +177,345 @@ __device__ __forceinline__ void pushStale(const SkinArgs& a, uint32_t c)
 }
 static_assert((kWalkBlocks + 1) / 2 <= (int)kSkinMaskWords, "hit-mask words per target");
 
+//! the cluster's list-set state on a reuse step (SkinArgs::same; 0 unless the lists in place are the last skin search's)
+__device__ __forceinline__ uint32_t listState(const SkinArgs& a, uint32_t c)
+{
+    return (a.same && a.keepLists && !a.fresh) ? (uint32_t)a.same[c] : 0u;
+}
+
+/*! A reuse step's decision per cluster (one 256-thread workgroup, one lane per target; streaming, about 52 B read and
+ *  4 B written per target):
+ *   1.  validity: each target's relative path d_i since the build (a.rel, advanced here by the last position update's
+ *       displacement), the region's A_C (a.acc, advanced by the step's largest |d - u| over the grid cells around the
+ *       wave boxes grown by the largest skin radius), 2h + d_i + A_C <= R (1 - eps) for every target, else STALE;
+ *   1b. FROZEN: the freeze reference of the last pass that walked the cluster still holds for every target.
+ *  a.dec[c] says which; a stale cluster is also listed in a.stale / a.direct (pushStale).  rel and acc are written for
+ *  the clusters that are not stale (a stale cluster's are reset by its rebuild). */
+__global__ __launch_bounds__(kB) void skinDecideKernel(SkinArgs a)
+{
+    __shared__ float s_red[kClusterWaves];
+    __shared__ int   s_vote[kClusterWaves];
+
+    const uint32_t c    = blockIdx.x;
+    const int      wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const uint32_t gw   = c * kClusterWaves + wave;
+    const uint32_t c0   = a.first + c * kCluster;
+    const uint32_t i    = c0 + threadIdx.x;
+    const bool     valid = gw < a.numGroups && i < a.last;
+    const uint32_t iS    = valid ? i : c0;
+    const double   xi = a.x[iS], yi = a.y[iS], zi = a.z[iS];
+    const double   ox = a.x[c0], oy = a.y[c0], oz = a.z[c0];
+    const float    hi  = a.h[iS];
+    const float    hbi = a.hb[iS];
+    // the last step's displacement relative to the cluster's reference particle (its first): this target's relative
+    // path since the build, d_i (rounding of the float displacements pushed upwards)
+    const float    ux = a.dispX[c0], uy = a.dispY[c0], uz = a.dispZ[c0];
+    const float    di = a.rel[iS] + norm3up(a.dispX[iS] - ux, a.dispY[iS] - uy, a.dispZ[iS] - uz);
+    const float    Ri = 2.0f * (hbi * a.skin1);
+    const uint32_t scount = valid ? a.scnt[i] - 1u : 0u;
+    const uint32_t U      = __builtin_amdgcn_readfirstlane(a.ucountS[c]);
+    const float    kEps   = 0x1p-16f;
+    // the freeze reference (1b) of the cluster's current list set, where that set holds lists
+    const uint32_t lstate    = listState(a, c);
+    const uint32_t lcur      = (a.nlocB && (lstate & kListsBSel)) ? 1u : 0u;
+    const bool     mayFreeze = a.frz && ((lstate >> lcur) & 1u) != 0;
+    const float2   fref      = mayFreeze ? a.frz[c] : make_float2(-INFINITY, -INFINITY);
+
+    // ---- 1. the region's displacement since the build: A = acc + this step's maximum over the grid cells around
+    //         the wave boxes grown by the largest skin radius
+    const double rx = foldPbc(xi - ox, a.box, 0), ry = foldPbc(yi - oy, a.box, 1), rz = foldPbc(zi - oz, a.box, 2);
+    double       lo[3]  = {valid ? rx : INFINITY, valid ? ry : INFINITY, valid ? rz : INFINITY};
+    double       hb3[3] = {valid ? rx : -INFINITY, valid ? ry : -INFINITY, valid ? rz : -INFINITY};
+    float        rmax   = valid ? Ri : 0.0f;
+    for (int d = 0; d < 3; ++d)
+    {
+        lo[d]  = -waveMax(-lo[d]);
+        hb3[d] = waveMax(hb3[d]);
+    }
+    rmax      = waveMax(rmax);
+    float gmx = 0.0f;
+    if (rmax > 0.0f)
+    {
+        const double o[3] = {ox, oy, oz};
+        int          k0[3], nk[3];
+        uint32_t     total = 1; // at most grid.n^3 (each nk within [1, grid.n]): 32-bit division below
+        for (int d = 0; d < 3; ++d)
+        {
+            k0[d]  = cellIndex(o[d] + lo[d] - (double)rmax, a.grid, d);
+            int k1 = cellIndex(o[d] + hb3[d] + (double)rmax, a.grid, d);
+            nk[d]  = k1 - k0[d] + 1;
+            if (a.grid.pbc[d] && nk[d] >= a.grid.n) k0[d] = 0, nk[d] = a.grid.n;
+            total *= nk[d];
+        }
+        // a region of many cells (a wave spanning an SFC seam across the box) scans them all: rare
+        for (uint32_t q = lane; q < total; q += kWave)
+        {
+            int      k[3];
+            uint32_t r = q;
+            for (int d = 0; d < 3; ++d)
+            {
+                const uint32_t rq = r / (uint32_t)nk[d];
+                k[d]              = k0[d] + (int)(r - rq * (uint32_t)nk[d]);
+                r                 = rq;
+                if (a.grid.pbc[d]) k[d] = wrapCell(k[d], a.grid.n);
+            }
+            const size_t nc   = (size_t)a.grid.n * a.grid.n * a.grid.n;
+            const size_t cell = ((size_t)k[2] * a.grid.n + k[1]) * a.grid.n + k[0];
+            const uint32_t lx = a.cells[cell], ly = a.cells[nc + cell], lz = a.cells[2 * nc + cell];
+            if (lx != 0xffffffffu) // a cell without particles has no range
+            {
+                // the largest |d - u| over the cell's component ranges
+                const float ex = fmaxf(fabsf(orderedFloat(lx) - ux), fabsf(orderedFloat(a.cells[3 * nc + cell]) - ux));
+                const float ey = fmaxf(fabsf(orderedFloat(ly) - uy), fabsf(orderedFloat(a.cells[4 * nc + cell]) - uy));
+                const float ez = fmaxf(fabsf(orderedFloat(lz) - uz), fabsf(orderedFloat(a.cells[5 * nc + cell]) - uz));
+                gmx = fmaxf(gmx, norm3up(ex, ey, ez));
+            }
+        }
+    }
+    gmx = waveMax(gmx);
+    if (lane == 0) s_red[wave] = gmx;
+    __syncthreads();
+    float g = s_red[0];
+    for (int w = 1; w < kClusterWaves; ++w)
+        g = fmaxf(g, s_red[w]);
+    const float A = a.acc[c] + g;
+
+    // a target's skin holds every current neighbor while 2h + d + A <= R (1 - eps); a build that overflowed a capacity
+    // (skin list beyond ngmaxS, union beyond the slot) never serves, nor a union beyond the LDS capacity
+    const bool bad = valid && (scount > a.ngmaxS || !(2.0f * hi + di + A <= Ri * (1.0f - kEps)));
+    // one more drift like the one since the build would make the cluster stale (stats[13]: the host stops using
+    // skins that cannot outlast two steps, sx_sim.cpp)
+    const bool thin = valid && 2.0f * hi + 2.0f * (di + A) > Ri * (1.0f - kEps);
+    // ---- 1b. frozen: since the last pass that walked this cluster (its reference: per target the smallest distance
+    //          g of a skin entry to the 2h sphere, and d_i + A_C, h then) no target and no entry has moved, nor has
+    //          2h changed, by enough for any entry to cross the sphere -- the relative motion of i and an entry is at
+    //          most the growth of d_i + A_C since (sx_skin.hpp's bound, also for entries outside the ball), so
+    //          2 |h - h_ref| + (d_i + A_C) - (d_i + A_C)_ref < g keeps every hit and miss.  The exact lists in place
+    //          are then this step's: no walk of the skin lists, the XMass over the exact lists (skinFrozenKernel).
+    //          Per cluster the reference pass left fref = min over its targets of K_i + 2 h_i and of K_i - 2 h_i,
+    //          K_i = g_i + (d_i + A_C) then (-inf: never frozen); d_i + A_C + 2h_i below the first and d_i + A_C - 2h_i
+    //          below the second give 2 |h_i - h_i,ref| + (d_i + A_C) < K_i for every target.  One vote with 1.
+    const float e    = di + A + kEps * Ri;
+    const bool  melt = valid && !(e + 2.0f * hi < fref.x && e - 2.0f * hi < fref.y);
+    // per decision whether any thread of the workgroup takes it (one vote round for the three)
+    uint32_t w = 0;
+    w |= __ballot(bad) != 0 ? 1u : 0u;
+    w |= __ballot(thin) != 0 ? 2u : 0u;
+    w |= __ballot(melt) != 0 ? 4u : 0u;
+    if (lane == 0) s_vote[wave] = (int)w;
+    __syncthreads();
+    uint32_t v = 0;
+    for (int k = 0; k < kClusterWaves; ++k)
+        v |= (uint32_t)s_vote[k];
+    if ((v & 1u) || U > (uint32_t)kSkinCap || U > a.ucap - a.uoff)
+    {
+        if (threadIdx.x == 0)
+        {
+            pushStale(a, c);
+            a.dec[c] = kSkinStale;
+        }
+        return;
+    }
+    if (valid) a.rel[i] = di;
+    if (threadIdx.x == 0)
+    {
+        if (v & 2u) atomicAdd(&a.stats[13], 1u);
+        a.acc[c] = A;
+        a.dec[c] = (mayFreeze && !(v & 4u)) ? kSkinFrozen : kSkinWalk;
+    }
+}
+
+/*! A frozen cluster's step (the clusters skinDecideKernel marked): its exact lists stand, so count, h, lists and union
+ *  stay as they are; the cluster's current set's exact union is staged in LDS as float positions relative to the
+ *  cluster origin (minimum image, folded in double) with the masses, and every lane sums the XMass (xmassJLoop,
+ *  hydro_ve/xmass_kern.hpp:50-79) over its exact list in list order.  Outputs: RecX, xm (RecT), the cluster statistics
+ *  with the kept and frozen bits.  26.6 KB of LDS and at most 80 VGPRs: six workgroups per CU */
+__global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(6))) void skinFrozenKernel(SkinArgs a)
+{
+    __shared__ float4 s_rec[kSkinFrozenCap]; // exact-union positions relative to the cluster origin, mass
+    __shared__ uint4  s_cst[kClusterWaves];
+
+    const uint32_t c = xcdBlock(blockIdx.x, gridDim.x);
+    if (a.dec[c] != kSkinFrozen) return;
+    const int      wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const uint32_t gw   = c * kClusterWaves + wave;
+    const uint32_t c0   = a.first + c * kCluster;
+    const uint32_t i    = c0 + threadIdx.x;
+    const bool     valid = gw < a.numGroups && i < a.last;
+    const uint32_t iS    = valid ? i : c0;
+    const double   xi = a.x[iS], yi = a.y[iS], zi = a.z[iS];
+    const double   ox = a.x[c0], oy = a.y[c0], oz = a.z[c0];
+    const float    hi = a.h[iS], mi = a.m[iS];
+    const uint32_t count  = valid ? a.nc[i] - 1u : 0u; // (the count in place)
+    const uint32_t stored = min(count, a.ngmax);
+    const uint32_t scount = valid ? a.scnt[i] - 1u : 0u;
+    // the cluster's current list set: its lists of this lane, its union
+    const bool      setB = a.nlocB && (a.same[c] & kListsBSel);
+    const uint32_t* ll   = (setB ? a.nlocB : a.nloc) + (size_t)gw * nlocWords(a.ngmax) * kWave + lane;
+    const uint32_t* un   = a.uni + (size_t)c * a.ucap + (setB ? a.uoffB : 0u);
+    const uint32_t  ue   = __builtin_amdgcn_readfirstlane(setB ? a.ucountB[c] : a.ucount[c]);
+    float           rho0 = mi;
+    const uint32_t  cap  = min(a.frozenStage, (uint32_t)kSkinFrozenCap); // union entries staged
+    if (a.xmOut)
+    {
+        const float xr = (float)foldPbc(xi - ox, a.box, 0), yr = (float)foldPbc(yi - oy, a.box, 1),
+                    zr = (float)foldPbc(zi - oz, a.box, 2);
+        //! union entry j as the staged record
+        auto record = [&](uint32_t j) {
+            return make_float4((float)foldPbc(a.x[j] - ox, a.box, 0), (float)foldPbc(a.y[j] - oy, a.box, 1),
+                               (float)foldPbc(a.z[j] - oz, a.box, 2), a.m[j]);
+        };
+        {
+            // unconditional loads (clamped), four entries of a thread in flight together (a load under a condition is
+            // waited for at the branch merge; more at once would not fit the 80 VGPRs of six workgroups per CU)
+            constexpr int  S = 4;
+            const uint32_t ns = min(ue, cap);
+#pragma unroll 1
+            for (uint32_t u0 = threadIdx.x; u0 < ns; u0 += S * kB)
+            {
+                uint32_t js[S];
+#pragma unroll
+                for (int q = 0; q < S; ++q)
+                    js[q] = un[min(u0 + q * kB, ns - 1u)];
+                double px[S], py[S], pz[S];
+                float  mq[S];
+#pragma unroll
+                for (int q = 0; q < S; ++q)
+                    px[q] = a.x[js[q]], py[q] = a.y[js[q]], pz[q] = a.z[js[q]], mq[q] = a.m[js[q]];
+#pragma unroll
+                for (int q = 0; q < S; ++q)
+                    if (u0 + q * kB < ns)
+                        s_rec[u0 + q * kB] = make_float4((float)foldPbc(px[q] - ox, a.box, 0), (float)foldPbc(py[q] - oy, a.box, 1),
+                                                         (float)foldPbc(pz[q] - oz, a.box, 2), mq[q]);
+            }
+            __syncthreads();
+        }
+        const float hInv = 1.0f / hi, hInv2 = hInv * hInv;
+        //! one entry's term: the record of union position p (clamped: a word's unused half past an odd count)
+        auto term = [&](uint32_t p, bool k) {
+            const float4 q  = s_rec[min(p, (uint32_t)kSkinFrozenCap - 1u)];
+            const float  dx = q.x - xr, dy = q.y - yr, dz = q.z - zr;
+            const float  r2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+            rho0 += keepOrZero(kernelWt(r2 * hInv2) * q.w, k);
+        };
+        const bool staged = ue <= cap;
+        if (valid && staged && ue <= a.packMax)
+        {
+            // packed12 lists (sx_pack12.hpp): two groups (six words, 16 entries) per iteration, the next two loaded
+            // a block ahead, every load unconditional (clamped to the list's last group)
+            const uint32_t  ngr = p12::groups(stored), lastG = ngr ? ngr - 1 : 0u;
+            const uint32_t* lp  = ll + (p12::kWords - 1) * lane;
+            constexpr int   PW  = 2 * p12::kWords;
+            auto            lw  = [&](uint32_t g0, int u) {
+                return lp[(size_t)min(g0 + u / p12::kWords, lastG) * (p12::kWords * kWave) + u % p12::kWords];
+            };
+            uint32_t nx[PW];
+#pragma unroll
+            for (int u = 0; u < PW; ++u)
+                nx[u] = lw(0, u);
+            for (uint32_t g0 = 0; g0 < ngr; g0 += 2)
+            {
+                uint32_t cw[PW];
+#pragma unroll
+                for (int u = 0; u < PW; ++u)
+                {
+                    cw[u] = nx[u];
+                    nx[u] = lw(g0 + 2, u);
+                }
+#pragma unroll
+                for (int h2 = 0; h2 < 2; ++h2)
+                {
+                    const uint32_t w0 = cw[3 * h2], w1 = cw[3 * h2 + 1], w2 = cw[3 * h2 + 2];
+                    const uint32_t pos[8] = {p12::get<0>(w0, w1, w2), p12::get<1>(w0, w1, w2), p12::get<2>(w0, w1, w2),
+                                             p12::get<3>(w0, w1, w2), p12::get<4>(w0, w1, w2), p12::get<5>(w0, w1, w2),
+                                             p12::get<6>(w0, w1, w2), p12::get<7>(w0, w1, w2)};
+#pragma unroll
+                    for (uint32_t e = 0; e < 8; ++e)
+                        term(pos[e], 8 * (g0 + h2) + e < stored);
+                }
+            }
+        }
+        else if (valid && staged)
+        {
+            // u16 lists: eight words (16 entries) per iteration, the next eight loaded a block ahead
+            const uint32_t nw = (stored + 1) >> 1, last = nw ? nw - 1 : 0u;
+            constexpr int  PF = kWalkPF;
+            uint32_t       nx[PF];
+#pragma unroll
+            for (int u = 0; u < PF; ++u)
+                nx[u] = ll[(size_t)min((uint32_t)u, last) * kWave];
+            for (uint32_t w0 = 0; w0 < nw; w0 += PF)
+            {
+                uint32_t cw[PF];
+#pragma unroll
+                for (int u = 0; u < PF; ++u)
+                {
+                    cw[u] = nx[u];
+                    nx[u] = ll[(size_t)min(w0 + PF + u, last) * kWave];
+                }
+#pragma unroll
+                for (int u = 0; u < PF; ++u)
+                {
+                    term(cw[u] & 0xffffu, 2 * (w0 + u) < stored);
+                    term(cw[u] >> 16, 2 * (w0 + u) + 1 < stored);
+                }
+            }
+        }
+        else if (valid)
+        {
+            // a union beyond the staging (rare): entry by entry, the upper entries' records from global memory -- the
+            // same floats, summed in the same order (the terms masked to +0 above change no sum)
+#pragma unroll 1
+            for (uint32_t e = 0; e < stored; ++e)
+            {
+                uint32_t p;
+                if (ue <= a.packMax)
+                {
+                    const uint32_t* g = ll + (p12::kWords - 1) * lane + (size_t)(e / p12::kGroup) * (p12::kWords * kWave);
+                    const uint32_t  w[p12::kWords] = {g[0], g[1], g[2]};
+                    p                              = p12::get(w, e % p12::kGroup);
+                }
+                else
+                {
+                    const uint32_t w = ll[(size_t)(e >> 1) * kWave];
+                    p                = (e & 1u) ? w >> 16 : w & 0xffffu;
+                }
+                const float4 q  = p < cap ? s_rec[p] : record(un[min(p, ue - 1u)]);
+                const float  dx = q.x - xr, dy = q.y - yr, dz = q.z - zr;
+                const float  r2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+                rho0 += kernelWt(r2 * hInv2) * q.w;
+            }
+        }
+    }
+
+    // ---- outputs
+    if (valid)
+    {
+        if (a.rxOut) a.rxOut[i] = RecX{xi, yi, zi, hi, mi};
+        if (a.xmOut)
+        {
+            const float hInv  = 1.0f / hi;
+            const float h3Inv = hInv * hInv * hInv;
+            const float xm    = (float)((double)mi / ((double)rho0 * a.K * (double)h3Inv));
+            a.xmOut[i]        = xm;
+            if (a.rtXm) a.rtXm[i] = RecT{xm, 0.0f, 0.0f, 0.0f};
+        }
+    }
+    const uint32_t maxCnt = waveMax(count), nst = waveSum(stored), walked = waveSum(scount);
+    if (lane == 0) s_cst[wave] = make_uint4(maxCnt, nst, walked, 0u);
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+        uint4 t = s_cst[0];
+        for (int w = 1; w < kClusterWaves; ++w)
+            t.x = max(t.x, s_cst[w].x), t.y += s_cst[w].y, t.z += s_cst[w].z;
+        t.y |= 0xc0000000u; // kept and frozen (stored entries < 2^30)
+        t.w          = ue;
+        a.clStats[c] = t;
+        if (a.streak) a.streak[c] = 0; // served by its skin: a later stale step rebuilds it again
+    }
+}
+
 //! four workgroups per CU by LDS: at most 128 VGPRs keep them all
 __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4))) void skinFilterKernel(SkinArgs a,
                                                                                               uint32_t numClusters)
@@ -193,6 +535,7 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4))) void sk
     if (blockIdx.x >= nWork) return;
     const uint32_t blk  = a.list ? blockIdx.x : xcdBlock(blockIdx.x, gridDim.x);
     const uint32_t c    = __builtin_amdgcn_readfirstlane(a.list ? a.list[1 + blk] : blk);
+    if (a.dec && a.dec[c] != kSkinWalk) return; // a reuse step: the clusters skinDecideKernel marked
     const int      wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const uint32_t gw   = c * kClusterWaves + wave;
     const uint32_t c0   = a.first + c * kCluster;
@@ -204,135 +547,44 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4))) void sk
     float          hi   = a.h[iS];
     const float    h0   = hi;
     const float    hbi  = a.fresh ? hi : a.hb[iS];
-    // the last step's displacement relative to the cluster's reference particle (its first): this target's relative
-    // path since the build, d_i (rounding of the float displacements pushed upwards)
-    const float    ux = a.dispX[c0], uy = a.dispY[c0], uz = a.dispZ[c0];
-    const float    di = a.fresh ? 0.0f
-                                : a.rel[iS] + norm3up(a.dispX[iS] - ux, a.dispY[iS] - uy, a.dispZ[iS] - uz);
+    // this target's relative path since the build, d_i, and the region's A_C: as skinDecideKernel left them this step
+    const float    di = a.fresh ? 0.0f : a.rel[iS];
+    const float    A  = a.fresh ? 0.0f : a.acc[c];
     const float    Ri = 2.0f * (hbi * a.skin1);
     const uint32_t scount = valid ? a.scnt[i] - 1u : 0u;
     const uint32_t U      = __builtin_amdgcn_readfirstlane(a.ucountS[c]);
     const float    kEps   = 0x1p-16f;
-    // the freeze reference (1b), loaded with the target's state: its latency off the vote's chain
     // the cluster's list sets (SkinArgs::same): the current one (B with a second set and its bit), which hold lists
-    const uint32_t lstate    = (a.same && a.keepLists && !a.fresh) ? (uint32_t)a.same[c] : 0u;
-    const uint32_t lcur      = (a.nlocB && (lstate & kListsBSel)) ? 1u : 0u;
-    const bool     curValid  = ((lstate >> lcur) & 1u) != 0;
-    const bool     mayFreeze = a.frz && curValid;
-    const float2   fref      = mayFreeze ? a.frz[c] : make_float2(-INFINITY, -INFINITY);
-    //! per bit k of v: whether any thread of the workgroup set it (one vote round for several decisions)
-    auto           blockBits = [&](uint32_t v) -> uint32_t {
-        uint32_t w = 0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            w |= __ballot((v >> k) & 1u) != 0 ? 1u << k : 0u;
-        if (lane == 0) s_vote[wave] = (int)w;
+    const uint32_t lstate   = listState(a, c);
+    const uint32_t lcur     = (a.nlocB && (lstate & kListsBSel)) ? 1u : 0u;
+    const bool     curValid = ((lstate >> lcur) & 1u) != 0;
+    //! whether v holds for any thread of the workgroup
+    auto blockAny = [&](bool v) -> bool {
+        const int w = __ballot(v) != 0; // (by every lane of the wave)
+        if (lane == 0) s_vote[wave] = w;
         __syncthreads();
-        uint32_t any = 0;
+        int any = 0;
         for (int k = 0; k < kClusterWaves; ++k)
-            any |= (uint32_t)s_vote[k];
+            any |= s_vote[k];
         __syncthreads();
-        return any;
+        return any != 0;
     };
-    auto blockAny = [&](bool v) -> bool { return blockBits(v ? 1u : 0u) != 0; };
 
-    // ---- 1. the region's displacement since the build: A = acc + this step's maximum over the grid cells around
-    //         the wave boxes grown by the largest skin radius
-    float A = 0.0f;
-    if (!a.fresh)
-    {
-        const double rx = foldPbc(xi - ox, a.box, 0), ry = foldPbc(yi - oy, a.box, 1), rz = foldPbc(zi - oz, a.box, 2);
-        double       lo[3]  = {valid ? rx : INFINITY, valid ? ry : INFINITY, valid ? rz : INFINITY};
-        double       hb3[3] = {valid ? rx : -INFINITY, valid ? ry : -INFINITY, valid ? rz : -INFINITY};
-        float        rmax   = valid ? Ri : 0.0f;
-        for (int d = 0; d < 3; ++d)
-        {
-            lo[d]  = -waveMax(-lo[d]);
-            hb3[d] = waveMax(hb3[d]);
-        }
-        rmax      = waveMax(rmax);
-        float gmx = 0.0f;
-        if (rmax > 0.0f)
-        {
-            const double o[3] = {ox, oy, oz};
-            int          k0[3], nk[3];
-            uint32_t     total = 1; // at most grid.n^3 (each nk within [1, grid.n]): 32-bit division below
-            for (int d = 0; d < 3; ++d)
-            {
-                k0[d]  = cellIndex(o[d] + lo[d] - (double)rmax, a.grid, d);
-                int k1 = cellIndex(o[d] + hb3[d] + (double)rmax, a.grid, d);
-                nk[d]  = k1 - k0[d] + 1;
-                if (a.grid.pbc[d] && nk[d] >= a.grid.n) k0[d] = 0, nk[d] = a.grid.n;
-                total *= nk[d];
-            }
-            // a region of many cells (a wave spanning an SFC seam across the box) scans them all: rare
-            for (uint32_t q = lane; q < total; q += kWave)
-            {
-                int      k[3];
-                uint32_t r = q;
-                for (int d = 0; d < 3; ++d)
-                {
-                    const uint32_t rq = r / (uint32_t)nk[d];
-                    k[d]              = k0[d] + (int)(r - rq * (uint32_t)nk[d]);
-                    r                 = rq;
-                    if (a.grid.pbc[d]) k[d] = wrapCell(k[d], a.grid.n);
-                }
-                const size_t nc   = (size_t)a.grid.n * a.grid.n * a.grid.n;
-                const size_t cell = ((size_t)k[2] * a.grid.n + k[1]) * a.grid.n + k[0];
-                const uint32_t lx = a.cells[cell], ly = a.cells[nc + cell], lz = a.cells[2 * nc + cell];
-                if (lx != 0xffffffffu) // a cell without particles has no range
-                {
-                    // the largest |d - u| over the cell's component ranges
-                    const float ex = fmaxf(fabsf(orderedFloat(lx) - ux), fabsf(orderedFloat(a.cells[3 * nc + cell]) - ux));
-                    const float ey = fmaxf(fabsf(orderedFloat(ly) - uy), fabsf(orderedFloat(a.cells[4 * nc + cell]) - uy));
-                    const float ez = fmaxf(fabsf(orderedFloat(lz) - uz), fabsf(orderedFloat(a.cells[5 * nc + cell]) - uz));
-                    gmx = fmaxf(gmx, norm3up(ex, ey, ez));
-                }
-            }
-        }
-        gmx = waveMax(gmx);
-        if (lane == 0) s_red[wave] = gmx;
-        __syncthreads();
-        float g = s_red[0];
-        for (int w = 1; w < kClusterWaves; ++w)
-            g = fmaxf(g, s_red[w]);
-        A = a.acc[c] + g;
-        __syncthreads();
-    }
     // a target's skin holds every current neighbor while 2h + d + A <= R (1 - eps); a build that overflowed a capacity
     // (skin list beyond ngmaxS, union beyond the slot) never serves, nor a union beyond the LDS capacity
     auto withinSkin = [&](float h) { return 2.0f * h + di + A <= Ri * (1.0f - kEps); };
-    // ---- 1b. frozen: since the last pass that walked this cluster (its reference: per target the smallest distance
-    //          g of a skin entry to the 2h sphere, and d_i + A_C, h then) no target and no entry has moved, nor has
-    //          2h changed, by enough for any entry to cross the sphere -- the relative motion of i and an entry is at
-    //          most the growth of d_i + A_C since (sx_skin.hpp's bound, also for entries outside the ball), so
-    //          2 |h - h_ref| + (d_i + A_C) - (d_i + A_C)_ref < g keeps every hit and miss.  The exact lists in place
-    //          are then this step's: no walk of the skin lists, the fused XMass over the exact lists
-    //          Per cluster the reference pass left fref = min over its targets of K_i + 2 h_i and of K_i - 2 h_i,
-    //          K_i = g_i + (d_i + A_C) then (-inf: never frozen); d_i + A_C + 2h_i below the first and d_i + A_C - 2h_i
-    //          below the second give 2 |h_i - h_i,ref| + (d_i + A_C) < K_i for every target.  One vote with 1.
-    bool frozen = false;
+    // ---- 1. a cluster just built (a reuse step's clusters passed skinDecideKernel's test)
+    if (a.fresh && (blockAny(valid && (scount > a.ngmaxS || !withinSkin(hi))) || U > (uint32_t)kSkinCap ||
+                    U > a.ucap - a.uoff))
     {
-        const bool bad  = valid && (scount > a.ngmaxS || !withinSkin(hi));
-        // one more drift like the one since the build would make the cluster stale (stats[13]: the host stops using
-        // skins that cannot outlast two steps, sx_sim.cpp)
-        const bool thin = !a.fresh && valid && 2.0f * hi + 2.0f * (di + A) > Ri * (1.0f - kEps);
-        const float e    = di + A + kEps * Ri;
-        const bool  melt = valid && !(e + 2.0f * hi < fref.x && e - 2.0f * hi < fref.y);
-        const uint32_t v = blockBits((bad ? 1u : 0u) | (thin ? 2u : 0u) | (melt ? 4u : 0u));
-        if ((v & 1u) || U > (uint32_t)kSkinCap || U > a.ucap - a.uoff)
-        {
-            if (threadIdx.x == 0) pushStale(a, c);
-            return;
-        }
-        if ((v & 2u) && threadIdx.x == 0) atomicAdd(&a.stats[13], 1u);
-        frozen = mayFreeze && !(v & 4u);
+        if (threadIdx.x == 0) pushStale(a, c);
+        return;
     }
     int      iteration = 0;
     unsigned count = 0, stored = 0;
     const float mi   = a.m[iS];
     float    rho0    = mi; // fused XMass (xmassJLoop, hydro_ve/xmass_kern.hpp:50-79) of the final pass
-    bool     kept    = frozen;
+    bool     kept    = false;
     uint32_t ue      = 0;
     float    frzK    = -INFINITY; // this pass's freeze reference (1b)
     const float xr = (float)foldPbc(xi - ox, a.box, 0), yr = (float)foldPbc(yi - oy, a.box, 1),
@@ -345,7 +597,6 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4))) void sk
         uint32_t* m = k ? a.hitMaskB : a.hitMask;
         return m ? m + (size_t)gw * kSkinMaskWords * kWave + lane : nullptr;
     };
-    const uint32_t* const ll = setLists(lcur); // the current set's lists (the frozen path's XMass)
     //! stages n union entries (global indices list[0 .. n)) as float positions relative to the cluster origin and
     //! masses; returns the largest |p|_1 over them (all loads of a thread in flight together)
     auto stage = [&](const uint32_t* list, uint32_t n) -> float {
@@ -384,92 +635,6 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4))) void sk
             r = fmaxf(r, s_red[w]);
         return r;
     };
-
-    if (frozen)
-    {
-        // ---- 2'/3'. the exact union staged, the fused XMass over the exact lists (count, h, lists unchanged)
-        ue = __builtin_amdgcn_readfirstlane(*setCount(lcur));
-        (void)stage(setUnion(lcur), ue);
-        count  = valid ? a.nc[i] - 1u : 0u;
-        stored = min(count, a.ngmax);
-        if (a.xmOut && valid && ue <= a.packMax)
-        {
-            // packed12 lists (sx_pack12.hpp): two groups (six words, 16 entries) per iteration, the next two loaded a
-            // block ahead, every load unconditional (clamped to the list's last group)
-            const float     hInv = 1.0f / hi, hInv2 = hInv * hInv;
-            const uint32_t  ngr = p12::groups(stored), lastG = ngr ? ngr - 1 : 0u;
-            const uint32_t* lp  = ll + (p12::kWords - 1) * lane;
-            constexpr int   PW  = 2 * p12::kWords;
-            auto            lw  = [&](uint32_t g0, int u) {
-                return lp[(size_t)min(g0 + u / p12::kWords, lastG) * (p12::kWords * kWave) + u % p12::kWords];
-            };
-            uint32_t nx[PW];
-#pragma unroll
-            for (int u = 0; u < PW; ++u)
-                nx[u] = lw(0, u);
-            for (uint32_t g0 = 0; g0 < ngr; g0 += 2)
-            {
-                uint32_t cw[PW];
-#pragma unroll
-                for (int u = 0; u < PW; ++u)
-                {
-                    cw[u] = nx[u];
-                    nx[u] = lw(g0 + 2, u);
-                }
-#pragma unroll
-                for (int h2 = 0; h2 < 2; ++h2)
-                {
-                    const uint32_t w0 = cw[3 * h2], w1 = cw[3 * h2 + 1], w2 = cw[3 * h2 + 2];
-                    const uint32_t pos[8] = {p12::get<0>(w0, w1, w2), p12::get<1>(w0, w1, w2), p12::get<2>(w0, w1, w2),
-                                             p12::get<3>(w0, w1, w2), p12::get<4>(w0, w1, w2), p12::get<5>(w0, w1, w2),
-                                             p12::get<6>(w0, w1, w2), p12::get<7>(w0, w1, w2)};
-#pragma unroll
-                    for (uint32_t e = 0; e < 8; ++e)
-                    {
-                        const float4 q  = s_rec[min(pos[e], (uint32_t)kSkinCap - 1u)];
-                        const float  dx = q.x - xr, dy = q.y - yr, dz = q.z - zr;
-                        const float  r2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
-                        rho0 += keepOrZero(kernelWt(r2 * hInv2) * q.w, 8 * (g0 + h2) + e < stored);
-                    }
-                }
-            }
-        }
-        else if (a.xmOut && valid)
-        {
-            const float    hInv = 1.0f / hi, hInv2 = hInv * hInv;
-            const uint32_t nw = (stored + 1) >> 1, last = nw ? nw - 1 : 0u;
-            constexpr int  PF = kWalkPF;
-            uint32_t       nx[PF];
-#pragma unroll
-            for (int u = 0; u < PF; ++u)
-                nx[u] = ll[(size_t)min((uint32_t)u, last) * kWave];
-            for (uint32_t w0 = 0; w0 < nw; w0 += PF)
-            {
-                uint32_t cw[PF];
-#pragma unroll
-                for (int u = 0; u < PF; ++u)
-                {
-                    cw[u] = nx[u];
-                    nx[u] = ll[(size_t)min(w0 + PF + u, last) * kWave];
-                }
-#pragma unroll
-                for (int u = 0; u < PF; ++u)
-                {
-                    const uint32_t w = w0 + u;
-#pragma unroll
-                    for (int h2 = 0; h2 < 2; ++h2)
-                    {
-                        const float4 q  = s_rec[min(h2 ? cw[u] >> 16 : cw[u] & 0xffffu, (uint32_t)kSkinCap - 1u)];
-                        const float  dx = q.x - xr, dy = q.y - yr, dz = q.z - zr;
-                        const float  r2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
-                        rho0 += keepOrZero(kernelWt(r2 * hInv2) * q.w, 2 * w + h2 < stored);
-                    }
-                }
-            }
-        }
-    }
-    else
-    {
 
     // ---- 2. stage U_s
     const uint32_t* un   = a.uni + (size_t)c * a.ucap + a.uoff;
@@ -767,19 +932,14 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4))) void sk
         if (threadIdx.x == 0) *setCount(ltgt) = ue;
     }
     if (threadIdx.x == 0 && a.same && lnew != lstate) a.same[c] = (uint8_t)lnew;
-    } // not frozen
 
     // ---- 6. outputs
     if (valid)
     {
-        if (!frozen)
-        {
-            a.nc[i] = count + 1; // (a frozen cluster's count is the one in place)
-        }
+        a.nc[i] = count + 1;
         if (a.iterateH && iteration > 0) a.h[i] = hi; // (h changes only by the iteration)
         if (a.rxOut) a.rxOut[i] = RecX{xi, yi, zi, hi, a.m[i]};
-        if (a.fresh) a.hb[i] = h0;
-        a.rel[i] = di; // 0 for a fresh cluster
+        if (a.fresh) a.hb[i] = h0, a.rel[i] = 0.0f;
         if (a.xmOut)
         {
             const float hInv  = 1.0f / hi;
@@ -791,7 +951,7 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4))) void sk
     }
     if (threadIdx.x == 0)
     {
-        a.acc[c]    = a.fresh ? 0.0f : A;
+        if (a.fresh) a.acc[c] = 0.0f;
         if (a.streak && !a.fresh) a.streak[c] = 0; // served by its skin: a later stale step rebuilds it again
     }
     const unsigned           failed = (valid && a.iterateH && iteration >= 10) ? 1u : 0u;
@@ -811,7 +971,7 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4))) void sk
     __syncthreads();
     if (threadIdx.x == 0)
     {
-        if (a.frz && !frozen)
+        if (a.frz)
         {
             float2 f = make_float2(__uint_as_float(s_cst[0].w), __uint_as_float(s_wsum[0]));
             for (int w = 1; w < kClusterWaves; ++w)
@@ -821,7 +981,7 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4))) void sk
         uint4 t = s_cst[0];
         for (int w = 1; w < kClusterWaves; ++w)
             t.x = max(t.x, s_cst[w].x), t.y += s_cst[w].y, t.z += s_cst[w].z;
-        t.y |= (kept ? 0x80000000u : 0u) | (frozen ? 0x40000000u : 0u); // (stored entries < 2^30)
+        t.y |= kept ? 0x80000000u : 0u; // (stored entries < 2^30; bit 30: skinFrozenKernel's)
         t.w          = ue; // (replaces the freeze minimum)
         a.clStats[c] = t;
     }
@@ -830,6 +990,18 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4))) void sk
 inline unsigned grid1(size_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
 
 } // namespace
+
+hipError_t skinDecide(const SkinArgs& a, uint32_t numClusters, hipStream_t s)
+{
+    if (numClusters) skinDecideKernel<<<numClusters, kB, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+hipError_t skinFrozen(const SkinArgs& a, uint32_t numClusters, hipStream_t s)
+{
+    if (numClusters) skinFrozenKernel<<<numClusters, kB, 0, s>>>(a);
+    return hipGetLastError();
+}
 
 hipError_t skinFilter(const SkinArgs& a, uint32_t numClusters, hipStream_t s)
 {

@@ -85,6 +85,10 @@ struct SkinArgs
     SkinGrid        grid;
     const uint32_t* list;  // nullable: the clusters list[1 .. list[0]], else all
     uint32_t*       stale; // [0] count, [1..] stale clusters (output)
+    // nullable (reuse steps): skinDecide's word per cluster, kSkinStale / kSkinFrozen / kSkinWalk; skinFrozen serves
+    // the clusters marked frozen, skinFilter (without a list) those marked walk
+    uint8_t*        dec;
+    uint32_t        frozenStage; // exact-union entries skinFrozen stages (at most kSkinFrozenCap: the default)
     // nullable (reuse steps): per cluster 1 while its last stale step sent it to a rebuild and it has not been served
     // by a skin since; such a cluster, stale again, is listed in `direct` (the exact search) instead of `stale`
     uint8_t*        streak;
@@ -120,6 +124,27 @@ struct SkinArgs
     uint4*          clStats; // per cluster {max count, stored, skin entries walked, union}
 };
 
+//! exact-union entries skinFrozen stages in LDS (16 B each: 26 KB, six workgroups per CU); the entries of a larger
+//! union beyond them come from global memory
+constexpr int kSkinFrozenCap = 1664;
+
+constexpr uint8_t kSkinStale = 0, kSkinFrozen = 1, kSkinWalk = 2; //!< SkinArgs::dec
+
+/*! A reuse step's search, in three launches over every cluster without a host read in between (a.fresh == 0, a.list ==
+ *  nullptr):
+ *  skinDecide  -- the targets' d_i (a.rel) and the region's A_C (a.acc) advanced by the last position update, then
+ *                 a.dec[c]: stale (listed in a.stale / a.direct, as the filter lists them), frozen or walk.  Streaming:
+ *                 no LDS staging, no list is read;
+ *  skinFrozen  -- the clusters marked frozen: the current set's exact union staged, the XMass over the current set's
+ *                 exact lists, RecX, xm and the cluster statistics;
+ *  skinFilter  -- the clusters marked walk: the walk, with d_i and A_C as the decide pass left them.
+ *  A consumer's workgroup whose cluster is not marked for it leaves at once.  (Compacted lists of the two kinds, one
+ *  atomic per cluster on a list's counter, were measured first: 250000 atomics on one address made the decide pass
+ *  2.9 ms at 64M particles.) */
+hipError_t skinDecide(const SkinArgs& a, uint32_t numClusters, hipStream_t s);
+hipError_t skinFrozen(const SkinArgs& a, uint32_t numClusters, hipStream_t s);
+/*! the filter over all clusters or a.list.  a.fresh: the clusters were just built (d_i = A_C = 0, hb recorded), every
+ *  one is walked; else (a.dec) the clusters skinDecide marked walk */
 hipError_t skinFilter(const SkinArgs& a, uint32_t numClusters, hipStream_t s);
 //! node boxes (center, half size) of the tree refreshed from the current positions: leaf boxes bound their particles,
 //! inner boxes their children (for a build between full syncs, when particles have left their cells); withCells:
