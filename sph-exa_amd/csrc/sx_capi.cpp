@@ -195,6 +195,29 @@ static int fail(sx_ctx* c, int code, const std::string& msg)
         if (e_ != hipSuccess) return fail(ctx, SX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));         \
     } while (0)
 
+// the host helpers of the exact sums (sx_exactsum.hpp) under sx_profile_* and sx_twopoint_*; fn: the caller's name
+static int exactWindow(const char* fn, const double* t, size_t n, int32_t* E)
+{
+    if ((!t && n) || !E) return fail(nullptr, SX_ERR_ARG, std::string(fn) + ": null terms or E");
+    uint32_t key = 0;
+    for (size_t i = 0; i < n; ++i)
+    {
+        if (!std::isfinite(t[i])) return fail(nullptr, SX_ERR_ARG, std::string(fn) + ": a term is not finite");
+        key = std::max(key, sx::exact::windowKey(t[i]));
+    }
+    *E = sx::exact::windowOfKey(key);
+    return SX_OK;
+}
+
+static int exactAddFixed(const char* fn, uint64_t acc[2], const uint64_t* lohi, size_t n)
+{
+    if (!acc || (!lohi && n)) return fail(nullptr, SX_ERR_ARG, std::string(fn) + ": null accumulator or terms");
+    sx::exact::U128 a{acc[0], acc[1]};
+    for (size_t i = 0; i < n; ++i)
+        sx::exact::addFixed(a, sx::exact::U128{lohi[2 * i], lohi[2 * i + 1]});
+    acc[0] = a.lo, acc[1] = a.hi;
+    return SX_OK;
+}
 
 extern "C"
 {
@@ -1594,27 +1617,16 @@ extern "C"
         return SX_OK;
     }
 
-    int sx_profile_window(const double* t, size_t n, int32_t* E)
-    {
-        if ((!t && n) || !E) return fail(nullptr, SX_ERR_ARG, "sx_profile_window: null terms or E");
-        uint32_t key = 0;
-        for (size_t i = 0; i < n; ++i)
-        {
-            if (!std::isfinite(t[i])) return fail(nullptr, SX_ERR_ARG, "sx_profile_window: a term is not finite");
-            key = std::max(key, sx::profile::windowKey(t[i]));
-        }
-        *E = sx::profile::windowOfKey(key);
-        return SX_OK;
-    }
+    int sx_profile_window(const double* t, size_t n, int32_t* E) { return exactWindow("sx_profile_window", t, n, E); }
 
     int sx_profile_to_fixed(const double* t, size_t n, int32_t E, uint64_t* lohi)
     {
         if ((!t || !lohi) && n) return fail(nullptr, SX_ERR_ARG, "sx_profile_to_fixed: null terms or output");
         for (size_t i = 0; i < n; ++i)
         {
-            if (!std::isfinite(t[i]) || sx::profile::windowOfKey(sx::profile::windowKey(t[i])) > E)
+            if (!std::isfinite(t[i]) || sx::exact::windowOfKey(sx::exact::windowKey(t[i])) > E)
                 return fail(nullptr, SX_ERR_ARG, "sx_profile_to_fixed: a term is not finite or not below 2^E");
-            const sx::profile::U128 v = sx::profile::toFixed(t[i], E);
+            const sx::exact::U128 v = sx::profile::toFixed(t[i], E);
             lohi[2 * i] = v.lo, lohi[2 * i + 1] = v.hi;
         }
         return SX_OK;
@@ -1622,18 +1634,13 @@ extern "C"
 
     int sx_profile_add_fixed(uint64_t acc[2], const uint64_t* lohi, size_t n)
     {
-        if (!acc || (!lohi && n)) return fail(nullptr, SX_ERR_ARG, "sx_profile_add_fixed: null accumulator or terms");
-        sx::profile::U128 a{acc[0], acc[1]};
-        for (size_t i = 0; i < n; ++i)
-            sx::profile::addFixed(a, sx::profile::U128{lohi[2 * i], lohi[2 * i + 1]});
-        acc[0] = a.lo, acc[1] = a.hi;
-        return SX_OK;
+        return exactAddFixed("sx_profile_add_fixed", acc, lohi, n);
     }
 
     int sx_profile_from_fixed(const uint64_t acc[2], int32_t E, double* out)
     {
         if (!acc || !out) return fail(nullptr, SX_ERR_ARG, "sx_profile_from_fixed: null accumulator or output");
-        *out = sx::profile::fromFixed(sx::profile::U128{acc[0], acc[1]}, E);
+        *out = sx::profile::fromFixed(sx::exact::U128{acc[0], acc[1]}, E);
         return SX_OK;
     }
 
@@ -1649,7 +1656,7 @@ extern "C"
     int sx_set_profile_timing(sx_ctx* c, int on)
     {
         if (!c) return SX_ERR_ARG;
-        c->profBuf.timing = on != 0;
+        c->profBuf.clock.on = on != 0;
         return SX_OK;
     }
 
@@ -1657,7 +1664,7 @@ extern "C"
     {
         if (!c || !out) return SX_ERR_ARG;
         for (int k = 0; k < 3; ++k)
-            out[k] = c->profBuf.ms[k];
+            out[k] = c->profBuf.clock.ms[k];
         out[3] = c->profBuf.passBytes;
         return SX_OK;
     }
@@ -1725,7 +1732,7 @@ extern "C"
     int sx_set_fof_timing(sx_ctx* c, int on)
     {
         if (!c) return SX_ERR_ARG;
-        c->fofBuf.timing = on != 0;
+        c->fofBuf.clock.on = on != 0;
         return SX_OK;
     }
 
@@ -1733,7 +1740,7 @@ extern "C"
     {
         if (!c || !out) return SX_ERR_ARG;
         for (int k = 0; k < 4; ++k)
-            out[k] = c->fofBuf.ms[k];
+            out[k] = c->fofBuf.clock.ms[k];
         return SX_OK;
     }
 
@@ -1774,7 +1781,7 @@ extern "C"
     int sx_set_twopoint_timing(sx_ctx* c, int on)
     {
         if (!c) return SX_ERR_ARG;
-        c->tpBuf.timing = on != 0;
+        c->tpBuf.clock.on = on != 0;
         return SX_OK;
     }
 
@@ -1782,22 +1789,11 @@ extern "C"
     {
         if (!c || !out) return SX_ERR_ARG;
         for (int k = 0; k < 4; ++k)
-            out[k] = c->tpBuf.msStage[k];
+            out[k] = c->tpBuf.clock.ms[k];
         return SX_OK;
     }
 
-    int sx_twopoint_window(const double* t, size_t n, int32_t* E)
-    {
-        if ((!t && n) || !E) return fail(nullptr, SX_ERR_ARG, "sx_twopoint_window: null terms or E");
-        uint32_t key = 0;
-        for (size_t i = 0; i < n; ++i)
-        {
-            if (!std::isfinite(t[i])) return fail(nullptr, SX_ERR_ARG, "sx_twopoint_window: a term is not finite");
-            key = std::max(key, sx::profile::windowKey(t[i]));
-        }
-        *E = sx::profile::windowOfKey(key);
-        return SX_OK;
-    }
+    int sx_twopoint_window(const double* t, size_t n, int32_t* E) { return exactWindow("sx_twopoint_window", t, n, E); }
 
     int sx_twopoint_to_fixed(const double* t, size_t n, int32_t E, uint64_t* lohi)
     {
@@ -1807,7 +1803,7 @@ extern "C"
             // 2^E itself is let through: a product that underflows may round up to it (include/sphexa_hip.h)
             if (!std::isfinite(t[i]) || !(std::fabs(t[i]) <= std::ldexp(1.0, E)))
                 return fail(nullptr, SX_ERR_ARG, "sx_twopoint_to_fixed: a term is not finite or above 2^E");
-            const sx::profile::U128 v = sx::profile::toFixedShift(t[i], E, sx::twopoint::kShift);
+            const sx::exact::U128 v = sx::exact::toFixedShift(t[i], E, sx::twopoint::kShift);
             lohi[2 * i] = v.lo, lohi[2 * i + 1] = v.hi;
         }
         return SX_OK;
@@ -1815,18 +1811,13 @@ extern "C"
 
     int sx_twopoint_add_fixed(uint64_t acc[2], const uint64_t* lohi, size_t n)
     {
-        if (!acc || (!lohi && n)) return fail(nullptr, SX_ERR_ARG, "sx_twopoint_add_fixed: null accumulator or terms");
-        sx::profile::U128 a{acc[0], acc[1]};
-        for (size_t i = 0; i < n; ++i)
-            sx::profile::addFixed(a, sx::profile::U128{lohi[2 * i], lohi[2 * i + 1]});
-        acc[0] = a.lo, acc[1] = a.hi;
-        return SX_OK;
+        return exactAddFixed("sx_twopoint_add_fixed", acc, lohi, n);
     }
 
     int sx_twopoint_from_fixed(const uint64_t acc[2], int32_t E, double* out)
     {
         if (!acc || !out) return fail(nullptr, SX_ERR_ARG, "sx_twopoint_from_fixed: null accumulator or output");
-        *out = sx::profile::fromFixedShift(sx::profile::U128{acc[0], acc[1]}, E, sx::twopoint::kShift);
+        *out = sx::exact::fromFixedShift(sx::exact::U128{acc[0], acc[1]}, E, sx::twopoint::kShift);
         return SX_OK;
     }
 

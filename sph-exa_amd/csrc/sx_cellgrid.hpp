@@ -1,11 +1,13 @@
 /*! @file sx_cellgrid.hpp
  * @brief The cell grid under the pair searches within a fixed length (sx_fof.hip: the linking length, sx_twopoint.hip:
- *        r_max): the rule for the cells per axis, the cell of a coordinate, the key kernel and the minimum image.
+ *        r_max): the rule for the cells per axis, the index of the particles by cell and its build (sx_cellgrid.hip),
+ *        the cell of a coordinate, the minimum image and the walk over the 27 cells round one.
  *
  * Cells of edge > length, x-fastest key cx + dx (cy + dy cz), particles sorted by key: the 27 cells around a particle are
  * nine x-runs of up to three cells, each one contiguous range of the sorted particles (a run that wraps round a periodic
  * x axis adds the cell at the far end as a range of its own).  The cell count is capped at max(27, 2 n), so a sparse set
- * gets cells wider than the length instead of a start array larger than its columns.
+ * gets cells wider than the length instead of a start array larger than its columns.  hipcub stays in sx_cellgrid.hip:
+ * this header is reached from every file of the step driver.
  */
 #pragma once
 
@@ -14,8 +16,10 @@
 
 #include <algorithm>
 #include <cmath>
+#include <string>
 
 #include "../../include/sphexa_hip.h"
+#include "sx_tree.hpp"
 
 namespace sx::cellgrid
 {
@@ -70,6 +74,25 @@ inline Grid makeGrid(const sx_box& box, const uint32_t dims[3], double length)
     return g;
 }
 
+/*! the particles of a range by cell: the typed owner of <prefix>keys, keysSorted, idx, order, cellCount, cellStart and
+ *  sortTmp (prefix "fof." or "twopoint."), requested at one site, in build, which stores the pointers here */
+struct Index
+{
+    uint32_t *keys{nullptr}, *keysSorted{nullptr}, *idx{nullptr}, *order{nullptr}; // order[s]: column index - first
+    uint32_t *cellCount{nullptr}, *cellStart{nullptr};                              // cells + 1
+    void*     sortTmp{nullptr}; // tmpBytes: hipcub's temporary storage, the client's further sorts and scans included
+    uint32_t  cells{0};
+    int       keyBits{1}; // of the largest key, at least 1: the bits the sort looks at
+    size_t    tmpBytes{0};
+};
+
+/*! the index of the particles [first, first + n) in the cells of g: keys and cell counts, the particles sorted by
+ *  key, the exclusive sum of the counts over cells + 1.  sortTmp is sized once, for the sort, the scan and the
+ *  minTmpBytes of the client's own hipcub calls.  n == 0: the buffers and no launch; n < 2^31.  who: for the messages */
+int build(Arena& arena, const std::string& tagPrefix, Index& ix, const Grid& g, const double* x, const double* y,
+          const double* z, uint32_t first, uint32_t n, size_t minTmpBytes, hipStream_t s, const char* who,
+          std::string& err);
+
 __device__ __forceinline__ uint32_t cellOf(double v, const Grid& g, int a)
 {
     const double t = (v - g.lo[a]) * g.inv[a];
@@ -83,22 +106,6 @@ __device__ __forceinline__ uint32_t cellOf(double v, const Grid& g, int a)
     }
     else c = c < 0 ? 0 : c > d - 1 ? d - 1 : c;
     return (uint32_t)c;
-}
-
-//! key, identity index and cell count of the particles [first, first + n); a template so that only its users emit it
-template<int Block = kBlock>
-__global__ __launch_bounds__(Block) void keyKernel(const double* __restrict__ x, const double* __restrict__ y,
-                                                           const double* __restrict__ z, uint32_t first, uint32_t n,
-                                                           Grid g, uint32_t* __restrict__ keys,
-                                                           uint32_t* __restrict__ idx, uint32_t* __restrict__ cellCount)
-{
-    const uint32_t i = blockIdx.x * Block + threadIdx.x;
-    if (i >= n) return;
-    const size_t   p   = (size_t)first + i;
-    const uint32_t key = cellOf(x[p], g, 0) + g.dims[0] * (cellOf(y[p], g, 1) + g.dims[1] * cellOf(z[p], g, 2));
-    keys[i]            = key;
-    idx[i]             = i;
-    atomicAdd(cellCount + key, 1u);
 }
 
 __device__ __forceinline__ double minImage(double d, int pbc, double half, double len)

@@ -7,20 +7,11 @@
 #include <cmath>
 #include <cstdio>
 
+#include "sx_exactsum.hpp"
 #include "sx_fof.hpp"
 
 namespace sx::fof
 {
-
-#define FOF_HIP(call)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t e_ = (call);                                                                                        \
-        if (e_ != hipSuccess)                                                                                          \
-        {                                                                                                              \
-            err = std::string("sx_fof: " #call ": ") + hipGetErrorString(e_);                                          \
-            return SX_ERR_HIP;                                                                                         \
-        }                                                                                                              \
-    } while (0)
 
 // ---- host decisions ---------------------------------------------------------------------------------------------
 
@@ -346,9 +337,7 @@ __global__ __launch_bounds__(kBlock) void reduceKernel(ReduceArgs a)
     }
 }
 
-unsigned blocks(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
-int bitLength(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
+constexpr const char* kWho = "sx_fof"; // in front of the messages of SX_TRY_HIP and the cell index
 
 } // namespace
 
@@ -360,7 +349,6 @@ int compute(Arena& arena, FofBuffers& b, const sx_fof& p, const sx_fields& f, co
     const uint32_t n = last - first;
     uint32_t       dims[3];
     chooseGrid(p, box, n, dims);
-    const uint32_t cells      = dims[0] * dims[1] * dims[2];
     const uint32_t minMembers = std::max(1u, p.minMembers);
     const bool     wantReal   = res.groupMass || res.groupCom || res.groupVel;
     const bool     wantCat    = wantReal || res.groupLabel || res.groupCount;
@@ -374,98 +362,74 @@ int compute(Arena& arena, FofBuffers& b, const sx_fof& p, const sx_fields& f, co
         err = "sx_fof: counter buffers";
         return SX_ERR_NOMEM;
     }
-    if (b.timing)
-        for (auto& e : b.ev)
-            if (!e) FOF_HIP(hipEventCreate(&e));
-    std::fill(b.ms, b.ms + 4, 0.f);
-    FOF_HIP(hipMemsetAsync(b.counters, 0, 4 * sizeof(uint64_t), s));
+    SX_TRY_HIP(kWho, b.clock.begin());
+    SX_TRY_HIP(kWho, hipMemsetAsync(b.counters, 0, 4 * sizeof(uint64_t), s));
     if (n == 0)
     {
-        if (res.numGroups) FOF_HIP(hipMemcpyAsync(res.numGroups, b.counters, 2 * sizeof(uint64_t), kind, s));
-        FOF_HIP(hipStreamSynchronize(s));
+        if (res.numGroups) SX_TRY_HIP(kWho, hipMemcpyAsync(res.numGroups, b.counters, 2 * sizeof(uint64_t), kind, s));
+        SX_TRY_HIP(kWho, hipStreamSynchronize(s));
         std::fill(b.stats, b.stats + 4, 0ull);
         b.done = true;
         return SX_OK;
     }
 
-    // the temporary storage of the largest sort or scan
-    size_t tmpBytes = 0;
-    {
-        size_t q = 0;
-        FOF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, q, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                                   (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 32, s));
-        tmpBytes = std::max(tmpBytes, q);
-        FOF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, q, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                                   (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 64, s));
-        tmpBytes = std::max(tmpBytes, q);
-        FOF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, q, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                                 (int)std::max(cells + 1, n), s));
-        tmpBytes = std::max(tmpBytes, q);
-    }
-    b.keys       = arena.get<uint32_t>("fof.keys", n);
-    b.keysSorted = arena.get<uint32_t>("fof.keysSorted", n);
-    b.idx        = arena.get<uint32_t>("fof.idx", n);
-    b.order      = arena.get<uint32_t>("fof.order", n);
-    b.cellCount  = arena.get<uint32_t>("fof.cellCount", (size_t)cells + 1);
-    b.cellStart  = arena.get<uint32_t>("fof.cellStart", (size_t)cells + 1);
-    b.xs         = arena.get<double>("fof.xs", n);
-    b.ys         = arena.get<double>("fof.ys", n);
-    b.zs         = arena.get<double>("fof.zs", n);
-    b.sortTmp    = arena.get<char>("fof.sortTmp", tmpBytes);
-    b.parent     = arena.get<uint32_t>("fof.parent", n);
-    b.root       = arena.get<uint32_t>("fof.root", n);
-    b.count      = arena.get<uint32_t>("fof.count", n);
-    b.rankOf     = arena.get<uint32_t>("fof.rankOf", n);
-    b.minId      = arena.get<uint64_t>("fof.minId", n);
-    b.label      = arena.get<uint64_t>("fof.label", n);
-    b.selLabel   = arena.get<uint64_t>("fof.selLabel", n);
-    b.selRoot    = arena.get<uint32_t>("fof.selRoot", n);
-    b.idKeys     = arena.get<uint64_t>("fof.idKeys", n);
-    b.mem        = arena.get<uint32_t>("fof.mem", n);
-    if (!b.keys || !b.keysSorted || !b.idx || !b.order || !b.cellCount || !b.cellStart || !b.xs || !b.ys || !b.zs ||
-        !b.sortTmp || !b.parent || !b.root || !b.count || !b.rankOf || !b.minId || !b.label || !b.selLabel ||
-        !b.selRoot || !b.idKeys || !b.mem)
+    // the catalogue's largest sort and its scan run in the cell index's temporary storage (a size query reads no pointer)
+    size_t sortTmp = 0, scanTmp = 0;
+    SX_TRY_HIP(kWho, hipcub::DeviceRadixSort::SortPairs(nullptr, sortTmp, b.idKeys, b.idKeysSorted, b.mem, b.memById,
+                                                        (int)n, 0, 64, s));
+    SX_TRY_HIP(kWho, hipcub::DeviceScan::ExclusiveSum(nullptr, scanTmp, b.segCount, b.segStart, (int)n, s));
+    b.xs       = arena.get<double>("fof.xs", n);
+    b.ys       = arena.get<double>("fof.ys", n);
+    b.zs       = arena.get<double>("fof.zs", n);
+    b.parent   = arena.get<uint32_t>("fof.parent", n);
+    b.root     = arena.get<uint32_t>("fof.root", n);
+    b.count    = arena.get<uint32_t>("fof.count", n);
+    b.rankOf   = arena.get<uint32_t>("fof.rankOf", n);
+    b.minId    = arena.get<uint64_t>("fof.minId", n);
+    b.label    = arena.get<uint64_t>("fof.label", n);
+    b.selLabel = arena.get<uint64_t>("fof.selLabel", n);
+    b.selRoot  = arena.get<uint32_t>("fof.selRoot", n);
+    b.idKeys   = arena.get<uint64_t>("fof.idKeys", n);
+    b.mem      = arena.get<uint32_t>("fof.mem", n);
+    if (!b.xs || !b.ys || !b.zs || !b.parent || !b.root || !b.count || !b.rankOf || !b.minId || !b.label ||
+        !b.selLabel || !b.selRoot || !b.idKeys || !b.mem)
     {
         err = "sx_fof: scratch buffers";
         return SX_ERR_NOMEM;
     }
 
-    const Grid g = cellgrid::makeGrid(box, dims, p.linking);
-    auto* counters = reinterpret_cast<unsigned long long*>(b.counters);
-    auto* minId    = reinterpret_cast<unsigned long long*>(b.minId);
-    const int keyBits = std::max(1, bitLength(cells - 1));
+    const Grid      g        = cellgrid::makeGrid(box, dims, p.linking);
+    cellgrid::Index& ix      = b.grid;
+    auto*           counters = reinterpret_cast<unsigned long long*>(b.counters);
+    auto*           minId    = reinterpret_cast<unsigned long long*>(b.minId);
 
     // ---- grid
-    if (b.timing) FOF_HIP(hipEventRecord(b.ev[0], s));
-    FOF_HIP(hipMemsetAsync(b.cellCount, 0, ((size_t)cells + 1) * sizeof(uint32_t), s));
-    cellgrid::keyKernel<><<<blocks(n), kBlock, 0, s>>>(f.x, f.y, f.z, first, n, g, b.keys, b.idx, b.cellCount);
-    FOF_HIP(hipcub::DeviceRadixSort::SortPairs(b.sortTmp, tmpBytes, (const uint32_t*)b.keys, b.keysSorted,
-                                               (const uint32_t*)b.idx, b.order, (int)n, 0, keyBits, s));
-    FOF_HIP(hipcub::DeviceScan::ExclusiveSum(b.sortTmp, tmpBytes, (const uint32_t*)b.cellCount, b.cellStart,
-                                             (int)(cells + 1), s));
-    gatherKernel<<<blocks(n), kBlock, 0, s>>>(f.x, f.y, f.z, first, n, b.order, b.xs, b.ys, b.zs, b.parent, b.count,
+    SX_TRY_HIP(kWho, b.clock.mark(0, s));
+    if (int rc = cellgrid::build(arena, "fof.", ix, g, f.x, f.y, f.z, first, n, std::max(sortTmp, scanTmp), s, kWho, err))
+        return rc;
+    gatherKernel<<<blocks(n), kBlock, 0, s>>>(f.x, f.y, f.z, first, n, ix.order, b.xs, b.ys, b.zs, b.parent, b.count,
                                               minId, b.rankOf);
-    if (b.timing) FOF_HIP(hipEventRecord(b.ev[1], s));
+    SX_TRY_HIP(kWho, b.clock.mark(1, s));
     // ---- link
-    LinkArgs la{b.xs, b.ys, b.zs, b.keysSorted, b.cellStart, b.parent, n, g, counters};
+    LinkArgs la{b.xs, b.ys, b.zs, ix.keysSorted, ix.cellStart, b.parent, n, g, counters};
     linkKernel<<<blocks(n), kBlock, 0, s>>>(la);
-    if (b.timing) FOF_HIP(hipEventRecord(b.ev[2], s));
+    SX_TRY_HIP(kWho, b.clock.mark(2, s));
     // ---- compress, labels, counts
-    compressKernel<<<blocks(n), kBlock, 0, s>>>(b.parent, n, first, b.order, id, b.root, minId, b.count, b.idKeys, b.mem);
-    labelKernel<<<blocks(n), kBlock, 0, s>>>(b.root, n, b.order, minId, b.count, minMembers, b.label, b.selLabel,
+    compressKernel<<<blocks(n), kBlock, 0, s>>>(b.parent, n, first, ix.order, id, b.root, minId, b.count, b.idKeys, b.mem);
+    labelKernel<<<blocks(n), kBlock, 0, s>>>(b.root, n, ix.order, minId, b.count, minMembers, b.label, b.selLabel,
                                              b.selRoot, counters);
-    if (b.timing) FOF_HIP(hipEventRecord(b.ev[3], s));
-    FOF_HIP(hipGetLastError());
-    FOF_HIP(hipMemcpyAsync(b.countersHost, b.counters, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    FOF_HIP(hipStreamSynchronize(s));
+    SX_TRY_HIP(kWho, b.clock.mark(3, s));
+    SX_TRY_HIP(kWho, hipGetLastError());
+    SX_TRY_HIP(kWho, hipMemcpyAsync(b.countersHost, b.counters, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    SX_TRY_HIP(kWho, hipStreamSynchronize(s));
     const uint64_t numAll = b.countersHost[2], G = b.countersHost[3];
     const uint32_t Gc     = (uint32_t)std::min<uint64_t>(G, cap);
-    if (res.label) FOF_HIP(hipMemcpyAsync(res.label, b.label, (size_t)n * sizeof(uint64_t), kind, s));
+    if (res.label) SX_TRY_HIP(kWho, hipMemcpyAsync(res.label, b.label, (size_t)n * sizeof(uint64_t), kind, s));
     if (res.numGroups)
     {
         // [selected, all]: the counters hold them the other way round
-        FOF_HIP(hipMemcpyAsync(res.numGroups, b.counters + 3, sizeof(uint64_t), kind, s));
-        FOF_HIP(hipMemcpyAsync(res.numGroups + 1, b.counters + 2, sizeof(uint64_t), kind, s));
+        SX_TRY_HIP(kWho, hipMemcpyAsync(res.numGroups, b.counters + 3, sizeof(uint64_t), kind, s));
+        SX_TRY_HIP(kWho, hipMemcpyAsync(res.numGroups + 1, b.counters + 2, sizeof(uint64_t), kind, s));
     }
 
     // ---- catalogue
@@ -488,15 +452,17 @@ int compute(Arena& arena, FofBuffers& b, const sx_fof& p, const sx_fields& f, co
             return SX_ERR_NOMEM;
         }
         // by label ascending, then (stable) by count descending
-        FOF_HIP(hipcub::DeviceRadixSort::SortPairs(b.sortTmp, tmpBytes, (const uint64_t*)b.selLabel, b.selLabelSorted,
-                                                   (const uint32_t*)b.selRoot, b.selRootSorted, (int)G, 0, 64, s));
+        SX_TRY_HIP(kWho, hipcub::DeviceRadixSort::SortPairs(ix.sortTmp, ix.tmpBytes, b.selLabel, b.selLabelSorted,
+                                                            b.selRoot, b.selRootSorted, (int)G, 0, 64, s));
         selKeyKernel<<<blocks(G), kBlock, 0, s>>>(b.selRootSorted, b.count, (uint32_t)G, b.selKey, b.selPos);
-        FOF_HIP(hipcub::DeviceRadixSort::SortPairs(b.sortTmp, tmpBytes, (const uint32_t*)b.selKey, b.selKeySorted,
-                                                   (const uint32_t*)b.selPos, b.selPosSorted, (int)G, 0, 32, s));
+        SX_TRY_HIP(kWho, hipcub::DeviceRadixSort::SortPairs(ix.sortTmp, ix.tmpBytes, b.selKey, b.selKeySorted, b.selPos,
+                                                            b.selPosSorted, (int)G, 0, 32, s));
         rankKernel<<<blocks(Gc), kBlock, 0, s>>>(b.selPosSorted, b.selRootSorted, b.selLabelSorted, b.count, Gc, b.rankOf,
                                                  b.outLabel, b.outCount, b.segCount);
-        if (res.groupLabel) FOF_HIP(hipMemcpyAsync(res.groupLabel, b.outLabel, (size_t)Gc * sizeof(uint64_t), kind, s));
-        if (res.groupCount) FOF_HIP(hipMemcpyAsync(res.groupCount, b.outCount, (size_t)Gc * sizeof(uint32_t), kind, s));
+        if (res.groupLabel)
+            SX_TRY_HIP(kWho, hipMemcpyAsync(res.groupLabel, b.outLabel, (size_t)Gc * sizeof(uint64_t), kind, s));
+        if (res.groupCount)
+            SX_TRY_HIP(kWho, hipMemcpyAsync(res.groupCount, b.outCount, (size_t)Gc * sizeof(uint32_t), kind, s));
         if (wantReal)
         {
             b.idKeysSorted = arena.get<uint64_t>("fof.idKeysSorted", n);
@@ -510,40 +476,35 @@ int compute(Arena& arena, FofBuffers& b, const sx_fof& p, const sx_fields& f, co
                 err = "sx_fof: member buffers";
                 return SX_ERR_NOMEM;
             }
-            FOF_HIP(hipcub::DeviceScan::ExclusiveSum(b.sortTmp, tmpBytes, (const uint32_t*)b.segCount, b.segStart,
-                                                     (int)Gc, s));
+            SX_TRY_HIP(kWho, hipcub::DeviceScan::ExclusiveSum(ix.sortTmp, ix.tmpBytes, b.segCount, b.segStart,
+                                                              (int)Gc, s));
             // the members by id ascending, then (stable) by group: the catalogue groups' segments lead
-            FOF_HIP(hipcub::DeviceRadixSort::SortPairs(b.sortTmp, tmpBytes, (const uint64_t*)b.idKeys, b.idKeysSorted,
-                                                       (const uint32_t*)b.mem, b.memById, (int)n, 0, 64, s));
+            SX_TRY_HIP(kWho, hipcub::DeviceRadixSort::SortPairs(ix.sortTmp, ix.tmpBytes, b.idKeys, b.idKeysSorted,
+                                                                b.mem, b.memById, (int)n, 0, 64, s));
             memKeyKernel<<<blocks(n), kBlock, 0, s>>>(b.memById, b.root, b.rankOf, n, Gc, b.memKey);
-            FOF_HIP(hipcub::DeviceRadixSort::SortPairs(b.sortTmp, tmpBytes, (const uint32_t*)b.memKey, b.memKeySorted,
-                                                       (const uint32_t*)b.memById, b.memSorted, (int)n, 0,
-                                                       std::max(1, bitLength(Gc)), s));
-            ReduceArgs ra{b.memSorted, b.segStart, b.outCount, b.order, b.xs, b.ys, b.zs, f.m, f.vx, f.vy, f.vz, first, Gc, g,
+            SX_TRY_HIP(kWho, hipcub::DeviceRadixSort::SortPairs(ix.sortTmp, ix.tmpBytes, b.memKey, b.memKeySorted,
+                                                                b.memById, b.memSorted, (int)n, 0,
+                                                                std::max(1, exact::bitLength(Gc)), s));
+            ReduceArgs ra{b.memSorted, b.segStart, b.outCount, ix.order, b.xs, b.ys, b.zs, f.m, f.vx, f.vy, f.vz, first, Gc, g,
                           b.outReal};
             reduceKernel<<<Gc, kBlock, 0, s>>>(ra);
-            if (res.groupMass) FOF_HIP(hipMemcpyAsync(res.groupMass, b.outReal, (size_t)Gc * sizeof(double), kind, s));
+            if (res.groupMass)
+                SX_TRY_HIP(kWho, hipMemcpyAsync(res.groupMass, b.outReal, (size_t)Gc * sizeof(double), kind, s));
             if (res.groupCom)
-                FOF_HIP(hipMemcpyAsync(res.groupCom, b.outReal + Gc, 3 * (size_t)Gc * sizeof(double), kind, s));
+                SX_TRY_HIP(kWho, hipMemcpyAsync(res.groupCom, b.outReal + Gc, 3 * (size_t)Gc * sizeof(double), kind,
+                                                s));
             if (res.groupVel)
-                FOF_HIP(hipMemcpyAsync(res.groupVel, b.outReal + 4 * (size_t)Gc, 3 * (size_t)Gc * sizeof(double), kind, s));
+                SX_TRY_HIP(kWho, hipMemcpyAsync(res.groupVel, b.outReal + 4 * (size_t)Gc,
+                                                3 * (size_t)Gc * sizeof(double), kind, s));
         }
     }
-    if (b.timing) FOF_HIP(hipEventRecord(b.ev[4], s));
-    FOF_HIP(hipGetLastError());
-    FOF_HIP(hipStreamSynchronize(s));
-    if (b.timing)
-        for (int k = 0; k < 4; ++k)
-            if (hipEventElapsedTime(&b.ms[k], b.ev[k], b.ev[k + 1]) != hipSuccess) b.ms[k] = 0;
+    SX_TRY_HIP(kWho, b.clock.mark(4, s));
+    SX_TRY_HIP(kWho, hipGetLastError());
+    SX_TRY_HIP(kWho, hipStreamSynchronize(s));
+    b.clock.finish();
     b.stats[0] = b.countersHost[0], b.stats[1] = b.countersHost[1], b.stats[2] = numAll, b.stats[3] = G;
     b.done     = true;
     return SX_OK;
-}
-
-void release(FofBuffers& b)
-{
-    for (auto& e : b.ev)
-        if (e) (void)hipEventDestroy(e), e = nullptr;
 }
 
 } // namespace sx::fof

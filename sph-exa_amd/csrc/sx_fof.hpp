@@ -4,10 +4,8 @@
  *        this file holds the grid decision, shared by the host entry points and the launcher, and the typed owner of
  *        the scratch.
  *
- * The grid (sx_cellgrid.hpp, shared with the two-point statistics).  Cells of edge > linking length, x-fastest key cx + dx (cy + dy cz), particles sorted by key: the 27 cells
- * around a target are nine x-runs of up to three cells, each one contiguous range of the sorted particles (a run that
- * wraps round a periodic x axis adds the cell at the far end as a range of its own).  The cell count is capped at
- * max(27, 2 n), so a sparse set gets cells wider than the linking length instead of a start array larger than its columns.
+ * The grid and the index of the particles by cell are sx_cellgrid.hpp's, shared with the two-point statistics, with the
+ * linking length as the search length.
  *
  * Union-find.  parent[] over the sorted indices, parent[i] <= i always.  A link hooks the larger root under the smaller
  * with a compare-and-swap that expects the larger to be a root still; a loser starts again from what it found there.
@@ -23,12 +21,11 @@
 
 #include "../../include/sphexa_hip.h"
 #include "sx_cellgrid.hpp"
-#include "sx_tree.hpp"
+#include "sx_step_timer.hpp"
 
 namespace sx::fof
 {
 
-constexpr uint32_t kMaxDim       = cellgrid::kMaxDim;
 constexpr uint64_t kMaxParticles = 0x7fffffffull; //!< sorted indices and hipcub's item counts are ints
 constexpr int      kBlock        = 256;
 constexpr uint32_t kNoGroup      = 0xffffffffu;
@@ -38,15 +35,12 @@ std::string checkSpec(const sx_fof* p, const sx_box* box);
 //! the cell grid of sx_fof_grid; p and box have passed checkSpec
 void chooseGrid(const sx_fof& p, const sx_box& box, uint64_t n, uint32_t dims[3]);
 
-/*! the typed owner of the scratch and the last call's figures.  Every "fof.*" arena tag is requested at one site in
- *  sx_fof.hip, which stores the pointer here. */
+/*! the typed owner of the scratch and the last call's figures.  Every "fof.*" arena tag is requested at one site, the
+ *  cell index's seven (cellgrid::Index) in cellgrid::build, the others in sx_fof.hip, which stores the pointer here. */
 struct FofBuffers
 {
-    // grid
-    uint32_t *keys{nullptr}, *keysSorted{nullptr}, *idx{nullptr}, *order{nullptr}; // order[s]: column index - first
-    uint32_t *cellCount{nullptr}, *cellStart{nullptr};                              // cells + 1
-    double *  xs{nullptr}, *ys{nullptr}, *zs{nullptr};                              // sorted coordinates
-    void*     sortTmp{nullptr};
+    cellgrid::Index grid; // its sortTmp serves the catalogue's sorts and scan as well
+    double *        xs{nullptr}, *ys{nullptr}, *zs{nullptr}; // sorted coordinates
     // union-find and labels, by sorted index; count, minId and rankOf are read at the roots
     uint32_t *parent{nullptr}, *root{nullptr}, *count{nullptr}, *rankOf{nullptr};
     uint64_t *minId{nullptr}, *label{nullptr};
@@ -60,10 +54,9 @@ struct FofBuffers
     uint32_t* outCount{nullptr};
     double*   outReal{nullptr}; // [mass G | com 3 G | vel 3 G]
     uint64_t *counters{nullptr}, *countersHost{nullptr}; // pair tests, union retries, all groups, selected groups
-    bool       timing{false}, done{false};
-    float      ms[4]{};
-    uint64_t   stats[4]{};
-    hipEvent_t ev[5]{};
+    bool          done{false};
+    StageClock<4> clock; // grid, link, compress and labels, catalogue
+    uint64_t      stats[4]{};
 };
 
 /*! all stages over [first, last) of f; the results go to the non-null arrays of res, device pointers (toHost false) or
@@ -74,6 +67,6 @@ int compute(Arena& arena, FofBuffers& b, const sx_fof& p, const sx_fields& f, co
 //! the reason a call on [first, last) of f is refused, or empty: checkSpec, the columns, the range, the capacity
 std::string whyRefused(const sx_fof* p, const sx_box* box, const sx_fields* f, uint32_t first, uint32_t last,
                        const sx_fof_result* res);
-void release(FofBuffers& b);
+inline void release(FofBuffers& b) { b.clock.release(); }
 
 } // namespace sx::fof

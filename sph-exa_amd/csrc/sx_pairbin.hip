@@ -63,16 +63,6 @@ __global__ void offsetsKernel(const uint64_t* sorted, uint32_t num, uint32_t uni
 
 } // namespace
 
-#define BIN_HIP(call)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t e_ = (call);                                                                                        \
-        if (e_ != hipSuccess)                                                                                          \
-        {                                                                                                              \
-            err = std::string(nm.hipFn) + ": " #call ": " + hipGetErrorString(e_);                                     \
-            return SX_ERR_HIP;                                                                                         \
-        }                                                                                                              \
-    } while (0)
-
 hipError_t ensureEvents(Buffers& b)
 {
     if (b.timing)
@@ -95,18 +85,19 @@ int drive(Arena& arena, Buffers& b, const Names& nm, int maxRows, int rows, uint
         return SX_ERR_NOMEM;
     }
     b.maxRows = maxRows;
-    BIN_HIP(ensureEvents(b));
+    SX_TRY_HIP(nm.hipFn, ensureEvents(b));
     b.ms[0] = b.ms[1] = b.ms[2] = 0.0f;
     float ms = 0.0f;
 
     // pairs per row
-    if (b.timing) BIN_HIP(hipEventRecord(b.ev[0], s));
-    BIN_HIP(hipMemsetAsync(b.counts, 0, numCount * sizeof(unsigned long long), s));
+    if (b.timing) SX_TRY_HIP(nm.hipFn, hipEventRecord(b.ev[0], s));
+    SX_TRY_HIP(nm.hipFn, hipMemsetAsync(b.counts, 0, numCount * sizeof(unsigned long long), s));
     l.count(b.counts);
-    BIN_HIP(hipGetLastError());
-    if (b.timing) BIN_HIP(hipEventRecord(b.ev[1], s));
-    BIN_HIP(hipMemcpyAsync(b.countsHost, b.counts, (2 + rows) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    BIN_HIP(hipStreamSynchronize(s));
+    SX_TRY_HIP(nm.hipFn, hipGetLastError());
+    if (b.timing) SX_TRY_HIP(nm.hipFn, hipEventRecord(b.ev[1], s));
+    SX_TRY_HIP(nm.hipFn, hipMemcpyAsync(b.countsHost, b.counts, (2 + rows) * sizeof(unsigned long long),
+                                        hipMemcpyDeviceToHost, s));
+    SX_TRY_HIP(nm.hipFn, hipStreamSynchronize(s));
     if (b.timing && hipEventElapsedTime(&ms, b.ev[0], b.ev[1]) == hipSuccess) b.ms[0] += ms;
 
     BandPlan plan;
@@ -119,8 +110,8 @@ int drive(Arena& arena, Buffers& b, const Names& nm, int maxRows, int rows, uint
         ++unitBits;
     size_t tmpBytes = 0;
     if (largest)
-        BIN_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tmpBytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)largest,
-                                                  0, 32 + unitBits, s));
+        SX_TRY_HIP(nm.hipFn, hipcub::DeviceRadixSort::SortKeys(nullptr, tmpBytes, (const uint64_t*)nullptr,
+                                                               (uint64_t*)nullptr, (int)largest, 0, 32 + unitBits, s));
     b.pairsIn  = arena.get<uint64_t>(tag + "pairsIn", largest);
     b.pairsOut = arena.get<uint64_t>(tag + "pairsOut", largest);
     b.sortTmp  = arena.get<char>(tag + "sortTmp", tmpBytes);
@@ -137,30 +128,30 @@ int drive(Arena& arena, Buffers& b, const Names& nm, int maxRows, int rows, uint
     {
         const uint32_t units = (uint32_t)(bd.r1 - bd.r0) * unitsPerRow;
         const uint32_t num   = (uint32_t)bd.pairs;
-        if (b.timing) BIN_HIP(hipEventRecord(b.ev[0], s));
-        BIN_HIP(hipMemsetAsync(b.cursor, 0, 4, s));
+        if (b.timing) SX_TRY_HIP(nm.hipFn, hipEventRecord(b.ev[0], s));
+        SX_TRY_HIP(nm.hipFn, hipMemsetAsync(b.cursor, 0, 4, s));
         if (num)
         {
             // keys beyond every unit: a slot the emit pass should leave unwritten sorts behind the last list
-            BIN_HIP(hipMemsetAsync(b.pairsIn, 0xff, (size_t)num * sizeof(uint64_t), s));
+            SX_TRY_HIP(nm.hipFn, hipMemsetAsync(b.pairsIn, 0xff, (size_t)num * sizeof(uint64_t), s));
             l.emit(bd, b.cursor, b.pairsIn);
-            BIN_HIP(hipGetLastError());
+            SX_TRY_HIP(nm.hipFn, hipGetLastError());
         }
-        if (b.timing) BIN_HIP(hipEventRecord(b.ev[1], s));
+        if (b.timing) SX_TRY_HIP(nm.hipFn, hipEventRecord(b.ev[1], s));
         if (num)
-            BIN_HIP(hipcub::DeviceRadixSort::SortKeys(b.sortTmp, tmpBytes, (const uint64_t*)b.pairsIn, b.pairsOut, (int)num, 0,
-                                                      32 + unitBits, s));
+            SX_TRY_HIP(nm.hipFn, hipcub::DeviceRadixSort::SortKeys(b.sortTmp, tmpBytes, (const uint64_t*)b.pairsIn,
+                                                                   b.pairsOut, (int)num, 0, 32 + unitBits, s));
         offsetsKernel<<<(units + 1 + 255) / 256, 256, 0, s>>>(b.pairsOut, num, units, b.offsets, b.cursor,
                                                               b.counts + 2 + maxRows);
-        BIN_HIP(hipGetLastError());
-        if (b.timing) BIN_HIP(hipEventRecord(b.ev[2], s));
+        SX_TRY_HIP(nm.hipFn, hipGetLastError());
+        if (b.timing) SX_TRY_HIP(nm.hipFn, hipEventRecord(b.ev[2], s));
         // a unit without pairs reads no particle
         l.gather(bd, b.pairsOut, b.offsets, b.counts);
-        BIN_HIP(hipGetLastError());
+        SX_TRY_HIP(nm.hipFn, hipGetLastError());
         if (b.timing)
         {
-            BIN_HIP(hipEventRecord(b.ev[3], s));
-            BIN_HIP(hipEventSynchronize(b.ev[3]));
+            SX_TRY_HIP(nm.hipFn, hipEventRecord(b.ev[3], s));
+            SX_TRY_HIP(nm.hipFn, hipEventSynchronize(b.ev[3]));
             for (int k = 0; k < 3; ++k)
                 if (hipEventElapsedTime(&ms, b.ev[k], b.ev[k + 1]) == hipSuccess) b.ms[k] += ms;
         }

@@ -232,20 +232,6 @@ __global__ __launch_bounds__(kBlock) void pass1Kernel(KArgs a)
     if (threadIdx.x == 0 && sBad) atomicAdd((unsigned long long*)a.acc, (unsigned long long)sBad);
 }
 
-//! p[0], p[1] += v as one 128-bit integer (LDS or global)
-template<class P>
-__device__ __forceinline__ void add128(P p, U128 v)
-{
-    if ((v.lo | v.hi) == 0) return;
-    uint64_t hi = v.hi;
-    if (v.lo)
-    {
-        const unsigned long long old = atomicAdd(p, (unsigned long long)v.lo);
-        if (old + v.lo < old) ++hi;
-    }
-    if (hi) atomicAdd(p + 1, (unsigned long long)hi);
-}
-
 extern __shared__ unsigned long long sBins[];
 
 template<bool Lds>
@@ -408,17 +394,7 @@ __global__ void finalKernel(const uint64_t* acc, const uint32_t* keys, uint32_t 
     else if (t == nSum + nb2 + 2 * nq * nb2) out[nb2] = acc[0];
 }
 
-#define PROF_HIP(call)                                                                                                 \
-    do {                                                                                                               \
-        hipError_t e_ = (call);                                                                                        \
-        if (e_ != hipSuccess)                                                                                          \
-        {                                                                                                              \
-            err = std::string("sx_profile: ") + #call + ": " + hipGetErrorString(e_);                                  \
-            return SX_ERR_HIP;                                                                                         \
-        }                                                                                                              \
-    } while (0)
-
-inline unsigned blocks(size_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
+constexpr const char* kWho = "sx_profile"; // in front of the messages of SX_TRY_HIP
 
 } // namespace
 
@@ -501,13 +477,6 @@ const char* whyRefused(const sx_profile* p, const sx_box* box, const sx_fields& 
     return nullptr;
 }
 
-static int ensureEvents(ProfBuffers& b, std::string& err)
-{
-    for (auto& e : b.ev)
-        if (!e) PROF_HIP(hipEventCreate(&e));
-    return SX_OK;
-}
-
 //! bytes per particle one pass reads: the coordinates and every distinct column of the quantities and the weight
 static double bytesPerParticle(const sx_profile& p, int std)
 {
@@ -550,7 +519,7 @@ int compute(Arena& arena, ProfBuffers& b, const sx_profile& p, const sx_fields& 
         err = "sx_profile: window buffers";
         return SX_ERR_NOMEM;
     }
-    PROF_HIP(hipMemsetAsync(b.keys, 0, kKeyWords * sizeof(uint32_t), s));
+    SX_TRY_HIP(kWho, hipMemsetAsync(b.keys, 0, kKeyWords * sizeof(uint32_t), s));
     if (refused)
     {
         err = refused;
@@ -558,9 +527,9 @@ int compute(Arena& arena, ProfBuffers& b, const sx_profile& p, const sx_fields& 
         {
             // take part in the one collective every rank reaches whatever its specification, then leave
             const uint32_t one = 1;
-            PROF_HIP(hipMemcpyAsync(b.keys, &one, sizeof(one), hipMemcpyHostToDevice, s));
+            SX_TRY_HIP(kWho, hipMemcpyAsync(b.keys, &one, sizeof(one), hipMemcpyHostToDevice, s));
             if (!reduce.maxU32(b.keys, kKeyWords)) return SX_ERR_HIP;
-            PROF_HIP(hipStreamSynchronize(s));
+            SX_TRY_HIP(kWho, hipStreamSynchronize(s));
         }
         return SX_ERR_ARG;
     }
@@ -587,8 +556,7 @@ int compute(Arena& arena, ProfBuffers& b, const sx_profile& p, const sx_fields& 
         err = "sx_profile: accumulator buffers";
         return SX_ERR_NOMEM;
     }
-    if (b.timing)
-        if (int rc = ensureEvents(b, err)) return rc;
+    SX_TRY_HIP(kWho, b.clock.begin());
 
     KArgs a{};
     a.x = f.x, a.y = f.y, a.z = f.z, a.temp = f.temp;
@@ -613,7 +581,7 @@ int compute(Arena& arena, ProfBuffers& b, const sx_profile& p, const sx_fields& 
     a.nq = (int)nq;
     a.cv = (double)idealGasCv(muiConst, gamma), a.gm1 = gamma - 1.0;
     a.keys = b.keys, a.acc = b.acc;
-    PROF_HIP(hipMemcpyAsync(b.edges, p.edges, (p.nbins + 1) * sizeof(double), hipMemcpyHostToDevice, s));
+    SX_TRY_HIP(kWho, hipMemcpyAsync(b.edges, p.edges, (p.nbins + 1) * sizeof(double), hipMemcpyHostToDevice, s));
     double* tab = b.table;
     for (uint32_t k = 0; k < nq; ++k)
     {
@@ -625,8 +593,8 @@ int compute(Arena& arena, ProfBuffers& b, const sx_profile& p, const sx_fields& 
         if (h.kind == SX_PROF_SOL_TABLE)
         {
             d.nt = h.nt, d.r = tab, d.y = tab + h.nt;
-            PROF_HIP(hipMemcpyAsync(tab, h.r, h.nt * sizeof(double), hipMemcpyHostToDevice, s));
-            PROF_HIP(hipMemcpyAsync(tab + h.nt, h.y, h.nt * sizeof(double), hipMemcpyHostToDevice, s));
+            SX_TRY_HIP(kWho, hipMemcpyAsync(tab, h.r, h.nt * sizeof(double), hipMemcpyHostToDevice, s));
+            SX_TRY_HIP(kWho, hipMemcpyAsync(tab + h.nt, h.y, h.nt * sizeof(double), hipMemcpyHostToDevice, s));
             tab += 2 * (size_t)h.nt;
         }
         else if (h.kind == SX_PROF_SOL_NOH_RHO)
@@ -649,8 +617,8 @@ int compute(Arena& arena, ProfBuffers& b, const sx_profile& p, const sx_fields& 
     if (!b.numCus)
     {
         int dev = 0, cus = 0;
-        PROF_HIP(hipGetDevice(&dev));
-        PROF_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        SX_TRY_HIP(kWho, hipGetDevice(&dev));
+        SX_TRY_HIP(kWho, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
         b.numCus = cus > 0 ? cus : 256;
     }
     const uint32_t ldsBytes = tileBins * bytesPerBin((int)nq);
@@ -658,21 +626,21 @@ int compute(Arena& arena, ProfBuffers& b, const sx_profile& p, const sx_fields& 
     const unsigned grid1    = (unsigned)std::min<size_t>(blocks(n, kBlock), 8u * b.numCus);
     const unsigned grid     = (unsigned)std::min<size_t>(blocks(n, kBlock), perCu * b.numCus);
     initKernel<<<blocks(accWords), 256, 0, s>>>(b.acc, offMin, offMax, accWords);
-    if (b.timing) PROF_HIP(hipEventRecord(b.ev[0], s));
+    SX_TRY_HIP(kWho, b.clock.mark(0, s));
     if (n) pass1Kernel<<<grid1, kBlock, 0, s>>>(a);
-    if (b.timing) PROF_HIP(hipEventRecord(b.ev[1], s));
+    SX_TRY_HIP(kWho, b.clock.mark(1, s));
     if (dist)
     {
         if (!reduce.maxU32(b.keys, kKeyWords)) return SX_ERR_HIP;
-        PROF_HIP(hipMemcpyAsync(b.keysHost, b.keys, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        PROF_HIP(hipStreamSynchronize(s));
+        SX_TRY_HIP(kWho, hipMemcpyAsync(b.keysHost, b.keys, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        SX_TRY_HIP(kWho, hipStreamSynchronize(s));
         if (b.keysHost[0])
         {
             err = "sx_profile: refused on another rank (its sx_last_error has the reason)";
             return SX_ERR_ARG;
         }
     }
-    if (b.timing) PROF_HIP(hipEventRecord(b.ev[1], s));
+    SX_TRY_HIP(kWho, b.clock.mark(1, s));
     if (n)
     {
         if (lds)
@@ -683,7 +651,7 @@ int compute(Arena& arena, ProfBuffers& b, const sx_profile& p, const sx_fields& 
             }
         else pass2Kernel<false><<<grid, kBlock, 0, s>>>(a);
     }
-    if (b.timing) PROF_HIP(hipEventRecord(b.ev[2], s));
+    SX_TRY_HIP(kWho, b.clock.mark(2, s));
     if (dist)
     {
         // nonfinite, the sums and the counts are the first offMin + 1 words of acc: as limbs through the u32 sum
@@ -697,16 +665,14 @@ int compute(Arena& arena, ProfBuffers& b, const sx_profile& p, const sx_fields& 
             if (!reduce.minF64(b.minmax, 2 * (size_t)nq * nb2)) return SX_ERR_HIP;
             minMaxInKernel<<<blocks(2 * nq * nb2), 256, 0, s>>>(b.minmax, nq * nb2, b.acc + 1 + offMin);
         }
-        if (b.timing) PROF_HIP(hipEventRecord(b.ev[2], s));
+        SX_TRY_HIP(kWho, b.clock.mark(2, s));
     }
     finalKernel<<<blocks(nser * nb2 + nb2 + 2 * nq * nb2 + 1), 256, 0, s>>>(b.acc, b.keys, nb2, (int)nq, b.out);
-    if (b.timing) PROF_HIP(hipEventRecord(b.ev[3], s));
-    PROF_HIP(hipGetLastError());
-    PROF_HIP(hipMemcpyAsync(b.outHost, b.out, nOut * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    PROF_HIP(hipStreamSynchronize(s));
-    if (b.timing)
-        for (int k = 0; k < 3; ++k)
-            if (hipEventElapsedTime(&b.ms[k], b.ev[k], b.ev[k + 1]) != hipSuccess) b.ms[k] = 0;
+    SX_TRY_HIP(kWho, b.clock.mark(3, s));
+    SX_TRY_HIP(kWho, hipGetLastError());
+    SX_TRY_HIP(kWho, hipMemcpyAsync(b.outHost, b.out, nOut * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    SX_TRY_HIP(kWho, hipStreamSynchronize(s));
+    b.clock.finish();
     b.passBytes = bytesPerParticle(p, std) * (double)n;
     uint64_t total = b.outHost[nb2];
     for (uint32_t k = 0; k < nb2; ++k)
@@ -719,12 +685,6 @@ int compute(Arena& arena, ProfBuffers& b, const sx_profile& p, const sx_fields& 
         return SX_ERR_ARG;
     }
     return SX_OK;
-}
-
-void release(ProfBuffers& b)
-{
-    for (auto& e : b.ev)
-        if (e) (void)hipEventDestroy(e), e = nullptr;
 }
 
 } // namespace sx::profile

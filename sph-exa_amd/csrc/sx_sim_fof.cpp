@@ -41,11 +41,11 @@ extern "C"
         }
         // sx_set_fof_timing and sx_fof_times of the context serve the sim's calls as well
         sx::fof::FofBuffers* cb = sx_ctx_fof_buffers_internal(s->ctx);
-        s->fofBuf.timing        = cb->timing;
+        s->fofBuf.clock.on      = cb->clock.on;
         std::string err;
         const int   rc = sx::fof::compute(s->work, s->fofBuf, *p, f, s->box, (uint32_t)s->first, (uint32_t)s->last, s->id,
                                           *res, true, (hipStream_t)sx_ctx_stream_internal(s->ctx), err);
-        std::copy(s->fofBuf.ms, s->fofBuf.ms + 4, cb->ms);
+        std::copy(s->fofBuf.clock.ms, s->fofBuf.clock.ms + 4, cb->clock.ms);
         if (rc != SX_OK) sx_ctx_set_error_internal(s->ctx, err.c_str());
         return rc;
     }

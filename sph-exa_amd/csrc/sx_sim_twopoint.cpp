@@ -42,11 +42,11 @@ extern "C"
         }
         // sx_set_twopoint_timing and sx_twopoint_times of the context serve the sim's calls as well
         sx::twopoint::TwoPointBuffers* cb = sx_ctx_twopoint_buffers_internal(s->ctx);
-        s->tpBuf.timing                   = cb->timing;
+        s->tpBuf.clock.on                 = cb->clock.on;
         std::string err;
         const int   rc = sx::twopoint::compute(s->work, s->tpBuf, *p, f, s->box, (uint32_t)s->first, (uint32_t)s->last,
                                                s->id, *res, true, (hipStream_t)sx_ctx_stream_internal(s->ctx), err);
-        std::copy(s->tpBuf.msStage, s->tpBuf.msStage + 4, cb->msStage);
+        std::copy(s->tpBuf.clock.ms, s->tpBuf.clock.ms + 4, cb->clock.ms);
         if (rc != SX_OK) sx_ctx_set_error_internal(s->ctx, err.c_str());
         return rc;
     }

@@ -355,16 +355,6 @@ bool reserveOut(Arena& arena, SpecBuffers& b)
 
 } // namespace
 
-#define SPEC_HIP(call)                                                                                                 \
-    do {                                                                                                               \
-        hipError_t e_ = (call);                                                                                        \
-        if (e_ != hipSuccess)                                                                                          \
-        {                                                                                                              \
-            err = std::string("sx_spectrum: " #call ": ") + hipGetErrorString(e_);                                     \
-            return SX_ERR_HIP;                                                                                         \
-        }                                                                                                              \
-    } while (0)
-
 int deposit(Arena& arena, SpecBuffers& b, const DepositArgs& a, hipStream_t s, std::string& err)
 {
     if (!validN(a.n))
@@ -422,18 +412,18 @@ int fft3d(Arena& arena, SpecBuffers& b, double* complexMesh, uint32_t n, hipStre
         }
         std::vector<double2> t;
         twiddleTable(n, t);
-        SPEC_HIP(hipStreamSynchronize(s)); // a transform of another n may still read the table
-        SPEC_HIP(hipMemcpy(b.twiddle, t.data(), n * sizeof(double2), hipMemcpyHostToDevice));
+        SX_TRY_HIP("sx_spectrum", hipStreamSynchronize(s)); // a transform of another n may still read the table
+        SX_TRY_HIP("sx_spectrum", hipMemcpy(b.twiddle, t.data(), n * sizeof(double2), hipMemcpyHostToDevice));
         b.twiddleN = n;
     }
-    SPEC_HIP(pairbin::ensureEvents(b.bin));
-    if (b.bin.timing) SPEC_HIP(hipEventRecord(b.bin.ev[0], s));
-    SPEC_HIP(fftLaunch(reinterpret_cast<double2*>(complexMesh), n, b.twiddle, s));
+    SX_TRY_HIP("sx_spectrum", pairbin::ensureEvents(b.bin));
+    if (b.bin.timing) SX_TRY_HIP("sx_spectrum", hipEventRecord(b.bin.ev[0], s));
+    SX_TRY_HIP("sx_spectrum", fftLaunch(reinterpret_cast<double2*>(complexMesh), n, b.twiddle, s));
     if (b.bin.timing)
     {
         float ms = 0.0f;
-        SPEC_HIP(hipEventRecord(b.bin.ev[1], s));
-        SPEC_HIP(hipEventSynchronize(b.bin.ev[1]));
+        SX_TRY_HIP("sx_spectrum", hipEventRecord(b.bin.ev[1], s));
+        SX_TRY_HIP("sx_spectrum", hipEventSynchronize(b.bin.ev[1]));
         if (hipEventElapsedTime(&ms, b.bin.ev[0], b.bin.ev[1]) == hipSuccess) b.msFft += ms;
     }
     return SX_OK;
@@ -495,11 +485,11 @@ static int ensurePerm(Arena& arena, SpecBuffers& b, uint32_t n, hipStream_t s, s
         return SX_ERR_NOMEM;
     }
     b.permN = 0;
-    SPEC_HIP(hipStreamSynchronize(s));
-    SPEC_HIP(hipMemcpy(b.perm, perm.data(), n3 * 4, hipMemcpyHostToDevice));
-    SPEC_HIP(hipMemcpy(b.leafBeg, leafBeg.data(), leafBeg.size() * 4, hipMemcpyHostToDevice));
-    SPEC_HIP(hipMemcpy(b.shellLeaf, shellLeaf.data(), shellLeaf.size() * 4, hipMemcpyHostToDevice));
-    SPEC_HIP(hipMemcpy(b.shellBeg, beg.data(), beg.size() * 4, hipMemcpyHostToDevice));
+    SX_TRY_HIP("sx_spectrum", hipStreamSynchronize(s));
+    SX_TRY_HIP("sx_spectrum", hipMemcpy(b.perm, perm.data(), n3 * 4, hipMemcpyHostToDevice));
+    SX_TRY_HIP("sx_spectrum", hipMemcpy(b.leafBeg, leafBeg.data(), leafBeg.size() * 4, hipMemcpyHostToDevice));
+    SX_TRY_HIP("sx_spectrum", hipMemcpy(b.shellLeaf, shellLeaf.data(), shellLeaf.size() * 4, hipMemcpyHostToDevice));
+    SX_TRY_HIP("sx_spectrum", hipMemcpy(b.shellBeg, beg.data(), beg.size() * 4, hipMemcpyHostToDevice));
     b.numLeaves = nl;
     b.permN     = n;
     return SX_OK;
@@ -514,17 +504,17 @@ int shellSums(Arena& arena, SpecBuffers& b, const double* complexMesh, uint32_t 
         return SX_ERR_ARG;
     }
     if (int rc = ensurePerm(arena, b, n, s, err)) return rc;
-    SPEC_HIP(pairbin::ensureEvents(b.bin));
+    SX_TRY_HIP("sx_spectrum", pairbin::ensureEvents(b.bin));
     const uint32_t ns = numShells(n);
-    if (b.bin.timing) SPEC_HIP(hipEventRecord(b.bin.ev[0], s));
+    if (b.bin.timing) SX_TRY_HIP("sx_spectrum", hipEventRecord(b.bin.ev[0], s));
     leafKernel<<<b.numLeaves, 256, 0, s>>>(reinterpret_cast<const double2*>(complexMesh), b.perm, b.leafBeg, b.leafSum);
     shellKernel<<<(ns + 63) / 64, 64, 0, s>>>(b.leafSum, b.shellLeaf, b.shellBeg, ns, prefactor, accumulate, power, modes);
-    SPEC_HIP(hipGetLastError());
+    SX_TRY_HIP("sx_spectrum", hipGetLastError());
     if (b.bin.timing)
     {
         float ms = 0.0f;
-        SPEC_HIP(hipEventRecord(b.bin.ev[1], s));
-        SPEC_HIP(hipEventSynchronize(b.bin.ev[1]));
+        SX_TRY_HIP("sx_spectrum", hipEventRecord(b.bin.ev[1], s));
+        SX_TRY_HIP("sx_spectrum", hipEventSynchronize(b.bin.ev[1]));
         if (hipEventElapsedTime(&ms, b.bin.ev[0], b.bin.ev[1]) == hipSuccess) b.msShells += ms;
     }
     return SX_OK;
@@ -557,16 +547,16 @@ int compute(Arena& arena, SpecBuffers& b, const sx_spectrum& sp, DepositArgs a, 
     if (reduce)
     {
         const double lead[2] = {rc != SX_OK ? 1.0 : 0.0, 0.0};
-        if (rc != SX_OK) SPEC_HIP(hipMemsetAsync(b.sums, 0, count * sizeof(double), s));
-        SPEC_HIP(hipMemcpyAsync(b.sums, lead, sizeof(lead), hipMemcpyHostToDevice, s));
-        SPEC_HIP(hipStreamSynchronize(s)); // lead is on this frame
+        if (rc != SX_OK) SX_TRY_HIP("sx_spectrum", hipMemsetAsync(b.sums, 0, count * sizeof(double), s));
+        SX_TRY_HIP("sx_spectrum", hipMemcpyAsync(b.sums, lead, sizeof(lead), hipMemcpyHostToDevice, s));
+        SX_TRY_HIP("sx_spectrum", hipStreamSynchronize(s)); // lead is on this frame
         if (!reduce(b.sums, count))
         {
             if (rc == SX_OK) err = "sx_spectrum_compute: the reduction over the ranks failed";
             return rc != SX_OK ? rc : SX_ERR_HIP;
         }
-        SPEC_HIP(hipMemcpyAsync(b.outHost, b.sums, sizeof(double), hipMemcpyDeviceToHost, s));
-        SPEC_HIP(hipStreamSynchronize(s));
+        SX_TRY_HIP("sx_spectrum", hipMemcpyAsync(b.outHost, b.sums, sizeof(double), hipMemcpyDeviceToHost, s));
+        SX_TRY_HIP("sx_spectrum", hipStreamSynchronize(s));
         if (rc == SX_OK && b.outHost[0] != 0.0)
         {
             err = "sx_spectrum_compute: refused on another rank (its sx_last_error has the reason)";
@@ -583,22 +573,22 @@ int compute(Arena& arena, SpecBuffers& b, const sx_spectrum& sp, DepositArgs a, 
     if (sp.kind == SX_SPEC_VELOCITY)
     {
         fieldKernel<<<fblocks, 256, 0, s>>>(S0, S1, S1 + n3, sp.weight, n3, cm);
-        SPEC_HIP(hipGetLastError());
+        SX_TRY_HIP("sx_spectrum", hipGetLastError());
         if ((rc = fft3d(arena, b, b.cplx, n, s, err))) return rc;
         if ((rc = shellSums(arena, b, b.cplx, n, 0.5, 0, pw, md, s, err))) return rc;
         fieldKernel<<<fblocks, 256, 0, s>>>(S0, S1 + 2 * n3, nullptr, sp.weight, n3, cm);
-        SPEC_HIP(hipGetLastError());
+        SX_TRY_HIP("sx_spectrum", hipGetLastError());
         if ((rc = fft3d(arena, b, b.cplx, n, s, err))) return rc;
         if ((rc = shellSums(arena, b, b.cplx, n, 0.5, 1, pw, md, s, err))) return rc;
     }
     else
     {
         fieldKernel<<<fblocks, 256, 0, s>>>(S0, a.numA ? S1 : S0, nullptr, a.numA ? 0 : 3, n3, cm);
-        SPEC_HIP(hipGetLastError());
+        SX_TRY_HIP("sx_spectrum", hipGetLastError());
         if ((rc = fft3d(arena, b, b.cplx, n, s, err))) return rc;
         if ((rc = shellSums(arena, b, b.cplx, n, 1.0, 0, pw, md, s, err))) return rc;
     }
-    SPEC_HIP(hipStreamSynchronize(s));
+    SX_TRY_HIP("sx_spectrum", hipStreamSynchronize(s));
     return SX_OK;
 }
 

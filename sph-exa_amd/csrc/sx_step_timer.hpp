@@ -1,5 +1,6 @@
 /*! @file sx_step_timer.hpp
  * @brief stage and kernel times of one sx_sim step, by name: what sx_sim_stage_times / sx_sim_kernel_times report
+ *        (and, at the end, StageClock: the stage times of one call of an analysis)
  *
  * A step calls start(), marks "stage X ends here" and "kernel X begins / ends" on its stream where they happen, and
  * calls collect() once the stream is synchronised.  A stage runs from the last boundary recorded before its end mark
@@ -106,3 +107,48 @@ private:
 };
 
 } // namespace sx::sim
+
+namespace sx
+{
+
+/*! the times of the N consecutive stages of one call of an analysis (sx_fof.hip, sx_twopoint.hip, sx_profile.hip)
+ *  between N + 1 boundaries on its stream.  A call begins the clock, marks its boundaries where they happen and
+ *  finishes it once the stream is synchronised; with the clock off nothing is recorded and the figures are zeros */
+template<int N>
+struct StageClock
+{
+    bool       on{false};
+    float      ms[N]{}; //!< of the last call
+    hipEvent_t ev[N + 1]{};
+
+    //! the start of a call: no figure yet; the events are created by the first call that is timed
+    hipError_t begin()
+    {
+        for (float& m : ms)
+            m = 0.f;
+        if (on)
+            for (auto& e : ev)
+                if (!e)
+                    if (hipError_t rc = hipEventCreate(&e); rc != hipSuccess) return rc;
+        return hipSuccess;
+    }
+
+    //! boundary k lies here: stage k - 1 ends and stage k begins (marked again: it lies here instead)
+    hipError_t mark(int k, hipStream_t s) { return on ? hipEventRecord(ev[k], s) : hipSuccess; }
+
+    //! after the stream's synchronisation, all boundaries marked: the times, 0 where one cannot be read
+    void finish()
+    {
+        if (on)
+            for (int k = 0; k < N; ++k)
+                if (hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]) != hipSuccess) ms[k] = 0;
+    }
+
+    void release()
+    {
+        for (auto& e : ev)
+            if (e) (void)hipEventDestroy(e), e = nullptr;
+    }
+};
+
+} // namespace sx

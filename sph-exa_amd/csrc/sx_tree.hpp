@@ -11,8 +11,23 @@
 
 #include "sx_device.hpp"
 
+/*! in a host function with a std::string err that returns a status: a failed HIP call leaves "<who>: <call>: <HIP's
+ *  text>" in err and returns SX_ERR_HIP.  who is an expression (a literal, or the client's name of an engine) */
+#define SX_TRY_HIP(who, call)                                                                                          \
+    do {                                                                                                               \
+        hipError_t e_ = (call);                                                                                        \
+        if (e_ != hipSuccess)                                                                                          \
+        {                                                                                                              \
+            err = std::string(who) + ": " #call ": " + hipGetErrorString(e_);                                          \
+            return SX_ERR_HIP;                                                                                         \
+        }                                                                                                              \
+    } while (0)
+
 namespace sx
 {
+
+//! workgroups of b threads over n items
+inline unsigned blocks(size_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
 
 //! grow-only named device (and pinned host) buffers owned by a context; no allocation inside a steady-state step
 class Arena

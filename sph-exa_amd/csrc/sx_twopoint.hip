@@ -14,9 +14,6 @@
  * with 64-bit integer atomics once, at its end.  No floating-point atomic anywhere.
  * Built with -ffp-contract=off: the arithmetic rule of include/sphexa_hip.h.
  */
-#include <hipcub/hipcub.hpp>
-
-#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -25,16 +22,6 @@
 
 namespace sx::twopoint
 {
-
-#define TP_HIP(call)                                                                                                   \
-    do {                                                                                                               \
-        hipError_t e_ = (call);                                                                                        \
-        if (e_ != hipSuccess)                                                                                          \
-        {                                                                                                              \
-            err = std::string("sx_twopoint: " #call ": ") + hipGetErrorString(e_);                                     \
-            return SX_ERR_HIP;                                                                                         \
-        }                                                                                                              \
-    } while (0)
 
 // ---- host decisions ---------------------------------------------------------------------------------------------
 
@@ -118,9 +105,10 @@ namespace
 
 using cellgrid::Grid;
 using cellgrid::minImage;
-using profile::U128;
+using exact::add128;
+using exact::U128;
 
-__device__ __forceinline__ bool finite(double v) { return profile::finiteBits(profile::doubleBits(v)); }
+__device__ __forceinline__ bool finite(double v) { return exact::finiteBits(exact::doubleBits(v)); }
 
 /*! the windows, nonfinite, targets and the flags of the particles of the range, in the order of the columns.  Integer
  *  maxima on the exponent keys: any order gives the same key. */
@@ -148,11 +136,11 @@ __global__ __launch_bounds__(kBlock) void windowKernel(const double* __restrict_
         flags[i]           = (uint8_t)((fin ? kFinite : 0) | (tgt ? kTarget : 0));
         if (fin)
         {
-            const uint32_t kv = max(max(profile::windowKey(dvx), profile::windowKey(dvy)), profile::windowKey(dvz));
+            const uint32_t kv = max(max(exact::windowKey(dvx), exact::windowKey(dvy)), exact::windowKey(dvz));
             if (kv) atomicMax(&sKey[0], kv);
             if (m)
             {
-                const uint32_t km = profile::windowKey(dm);
+                const uint32_t km = exact::windowKey(dm);
                 if (km) atomicMax(&sKey[1], km);
             }
             if (tgt) atomicAdd(&sCnt[0], 1u);
@@ -190,20 +178,6 @@ __global__ __launch_bounds__(kBlock) void gatherKernel(const double* __restrict_
     flagsSorted[s] = fl;
 }
 
-//! p[0], p[1] += v as one 128-bit integer (LDS or global)
-template<class P>
-__device__ __forceinline__ void add128(P p, U128 v)
-{
-    if ((v.lo | v.hi) == 0) return;
-    uint64_t hi = v.hi;
-    if (v.lo)
-    {
-        const unsigned long long old = atomicAdd(p, (unsigned long long)v.lo);
-        if (old + v.lo < old) ++hi;
-    }
-    if (hi) atomicAdd(p + 1, (unsigned long long)hi);
-}
-
 struct PairArgs
 {
     const double *  xs, *ys, *zs;
@@ -221,7 +195,7 @@ struct PairArgs
 //! the windows of the six series from the two keys of the window pass
 __device__ __host__ __forceinline__ void windows(uint32_t vkey, uint32_t mkey, int32_t E[kSeries])
 {
-    const int32_t Eu = profile::windowOfKey(vkey) + 2, em = profile::windowOfKey(mkey);
+    const int32_t Eu = exact::windowOfKey(vkey) + 2, em = exact::windowOfKey(mkey);
     E[0] = Eu, E[1] = 2 * Eu, E[2] = 3 * Eu, E[3] = 3 * Eu, E[4] = 2 * Eu, E[5] = 2 * em;
 }
 
@@ -293,17 +267,17 @@ __global__ __launch_bounds__(kBlock) void pairKernel(PairArgs a)
                     const double dvx = (double)a.vxs[j] - vxi, dvy = (double)a.vys[j] - vyi, dvz = (double)a.vzs[j] - vzi;
                     const double u  = ((dvx * dx + dvy * dy) + dvz * dz) / r;
                     const double u2 = u * u, u3 = u2 * u;
-                    if (slot[0] >= 0) add128(&sBins[nb + 2 * (slot[0] * nb + lo)], profile::toFixedShift(u, E[0], kShift));
-                    if (slot[1] >= 0) add128(&sBins[nb + 2 * (slot[1] * nb + lo)], profile::toFixedShift(u2, E[1], kShift));
-                    if (slot[2] >= 0) add128(&sBins[nb + 2 * (slot[2] * nb + lo)], profile::toFixedShift(u3, E[2], kShift));
+                    if (slot[0] >= 0) add128(&sBins[nb + 2 * (slot[0] * nb + lo)], exact::toFixedShift(u, E[0], kShift));
+                    if (slot[1] >= 0) add128(&sBins[nb + 2 * (slot[1] * nb + lo)], exact::toFixedShift(u2, E[1], kShift));
+                    if (slot[2] >= 0) add128(&sBins[nb + 2 * (slot[2] * nb + lo)], exact::toFixedShift(u3, E[2], kShift));
                     if (slot[3] >= 0)
-                        add128(&sBins[nb + 2 * (slot[3] * nb + lo)], profile::toFixedShift(fabs(u3), E[3], kShift));
+                        add128(&sBins[nb + 2 * (slot[3] * nb + lo)], exact::toFixedShift(fabs(u3), E[3], kShift));
                     if (slot[4] >= 0)
                         add128(&sBins[nb + 2 * (slot[4] * nb + lo)],
-                               profile::toFixedShift((dvx * dvx + dvy * dvy) + dvz * dvz, E[4], kShift));
+                               exact::toFixedShift((dvx * dvx + dvy * dvy) + dvz * dvz, E[4], kShift));
                 }
                 if constexpr (Mass)
-                    add128(&sBins[nb + 2 * (slot[5] * nb + lo)], profile::toFixedShift(mi * (double)a.ms[j], E[5], kShift));
+                    add128(&sBins[nb + 2 * (slot[5] * nb + lo)], exact::toFixedShift(mi * (double)a.ms[j], E[5], kShift));
             }
         };
         cellgrid::forEachRun(g, a.keys[i], a.cellStart, scan);
@@ -346,7 +320,7 @@ __global__ void convertKernel(const uint64_t* __restrict__ acc, const uint32_t* 
         windows(winKeys[0], winKeys[1], E);
         const uint32_t  k = (w - nb) / nb, b = (w - nb) % nb;
         const uint64_t* p = acc + kHead + nb + 2 * ((size_t)k * nb + b);
-        out[w]            = profile::doubleBits(profile::fromFixedShift(U128{p[0], p[1]}, E[k], kShift));
+        out[w]            = exact::doubleBits(exact::fromFixedShift(U128{p[0], p[1]}, E[k], kShift));
     }
     else if (w < nb * (1 + kSeries) + 4)
     {
@@ -355,9 +329,7 @@ __global__ void convertKernel(const uint64_t* __restrict__ acc, const uint32_t* 
     }
 }
 
-unsigned blocks(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
-int bitLength(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
+constexpr const char* kWho = "sx_twopoint"; // in front of the messages of SX_TRY_HIP and the cell index
 
 } // namespace
 
@@ -370,28 +342,9 @@ int compute(Arena& arena, TwoPointBuffers& b, const sx_twopoint& p, const sx_fie
     const uint32_t n = last - first, nb = p.nbins;
     uint32_t       dims[3];
     chooseGrid(p, box, n, dims);
-    const uint32_t cells  = dims[0] * dims[1] * dims[2];
     const bool     wantM  = (p.series & SX_TP_WW) != 0;
     const size_t   nAcc   = accWords(nb), nOut = outWords(nb);
 
-    size_t tmpBytes = 0;
-    if (n)
-    {
-        size_t q = 0;
-        TP_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, q, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                                  (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 32, s));
-        tmpBytes = std::max(tmpBytes, q);
-        TP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, q, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                                (int)(cells + 1), s));
-        tmpBytes = std::max(tmpBytes, q);
-    }
-    b.keys        = arena.get<uint32_t>("twopoint.keys", n);
-    b.keysSorted  = arena.get<uint32_t>("twopoint.keysSorted", n);
-    b.idx         = arena.get<uint32_t>("twopoint.idx", n);
-    b.order       = arena.get<uint32_t>("twopoint.order", n);
-    b.cellCount   = arena.get<uint32_t>("twopoint.cellCount", (size_t)cells + 1);
-    b.cellStart   = arena.get<uint32_t>("twopoint.cellStart", (size_t)cells + 1);
-    b.sortTmp     = arena.get<char>("twopoint.sortTmp", tmpBytes);
     b.flags       = arena.get<uint8_t>("twopoint.flags", n);
     b.winKeys     = arena.get<uint32_t>("twopoint.winKeys", 2);
     b.xs          = arena.get<double>("twopoint.xs", n);
@@ -406,52 +359,40 @@ int compute(Arena& arena, TwoPointBuffers& b, const sx_twopoint& p, const sx_fie
     b.acc         = arena.get<uint64_t>("twopoint.acc", accWords(kMaxBins));
     b.out         = arena.get<uint64_t>("twopoint.out", outWords(kMaxBins));
     b.outHost     = arena.pinned<uint64_t>("twopoint.outHost", outWords(kMaxBins));
-    if (!b.keys || !b.keysSorted || !b.idx || !b.order || !b.cellCount || !b.cellStart || !b.sortTmp || !b.flags ||
-        !b.winKeys || !b.xs || !b.ys || !b.zs || !b.vxs || !b.vys || !b.vzs || !b.ms || !b.flagsSorted || !b.edges ||
-        !b.acc || !b.out || !b.outHost)
+    if (!b.flags || !b.winKeys || !b.xs || !b.ys || !b.zs || !b.vxs || !b.vys || !b.vzs || !b.ms || !b.flagsSorted ||
+        !b.edges || !b.acc || !b.out || !b.outHost)
     {
         err = "sx_twopoint: scratch buffers";
         return SX_ERR_NOMEM;
     }
-    if (b.timing)
-        for (auto& e : b.ev)
-            if (!e) TP_HIP(hipEventCreate(&e));
-    std::fill(b.msStage, b.msStage + 4, 0.f);
+    SX_TRY_HIP(kWho, b.clock.begin());
 
-    const Grid g   = cellgrid::makeGrid(box, dims, p.edges[nb]);
-    auto*      acc = reinterpret_cast<unsigned long long*>(b.acc);
-    TP_HIP(hipMemsetAsync(b.acc, 0, nAcc * sizeof(uint64_t), s));
-    TP_HIP(hipMemsetAsync(b.winKeys, 0, 2 * sizeof(uint32_t), s));
-    TP_HIP(hipMemcpyAsync(b.edges, p.edges, ((size_t)nb + 1) * sizeof(double), hipMemcpyHostToDevice, s));
+    const Grid       g   = cellgrid::makeGrid(box, dims, p.edges[nb]);
+    cellgrid::Index& ix  = b.grid;
+    auto*            acc = reinterpret_cast<unsigned long long*>(b.acc);
+    SX_TRY_HIP(kWho, hipMemsetAsync(b.acc, 0, nAcc * sizeof(uint64_t), s));
+    SX_TRY_HIP(kWho, hipMemsetAsync(b.winKeys, 0, 2 * sizeof(uint32_t), s));
+    SX_TRY_HIP(kWho, hipMemcpyAsync(b.edges, p.edges, ((size_t)nb + 1) * sizeof(double), hipMemcpyHostToDevice, s));
 
     // ---- grid
-    if (b.timing) TP_HIP(hipEventRecord(b.ev[0], s));
-    if (n)
-    {
-        const int keyBits = std::max(1, bitLength(cells - 1));
-        TP_HIP(hipMemsetAsync(b.cellCount, 0, ((size_t)cells + 1) * sizeof(uint32_t), s));
-        cellgrid::keyKernel<><<<blocks(n), kBlock, 0, s>>>(f.x, f.y, f.z, first, n, g, b.keys, b.idx, b.cellCount);
-        TP_HIP(hipcub::DeviceRadixSort::SortPairs(b.sortTmp, tmpBytes, (const uint32_t*)b.keys, b.keysSorted,
-                                                  (const uint32_t*)b.idx, b.order, (int)n, 0, keyBits, s));
-        TP_HIP(hipcub::DeviceScan::ExclusiveSum(b.sortTmp, tmpBytes, (const uint32_t*)b.cellCount, b.cellStart,
-                                                (int)(cells + 1), s));
-    }
-    if (b.timing) TP_HIP(hipEventRecord(b.ev[1], s));
+    SX_TRY_HIP(kWho, b.clock.mark(0, s));
+    if (int rc = cellgrid::build(arena, "twopoint.", ix, g, f.x, f.y, f.z, first, n, 0, s, kWho, err)) return rc;
+    SX_TRY_HIP(kWho, b.clock.mark(1, s));
     // ---- windows, gather
     if (n)
     {
         windowKernel<<<blocks(n), kBlock, 0, s>>>(f.x, f.y, f.z, f.vx, f.vy, f.vz, wantM ? f.m : nullptr, id, first, n,
                                                   p.stride, p.phase, b.flags, b.winKeys, acc);
         gatherKernel<<<blocks(n), kBlock, 0, s>>>(f.x, f.y, f.z, f.vx, f.vy, f.vz, wantM ? f.m : nullptr, first, n,
-                                                  b.order, b.flags, b.xs, b.ys, b.zs, b.vxs, b.vys, b.vzs, b.ms,
+                                                  ix.order, b.flags, b.xs, b.ys, b.zs, b.vxs, b.vys, b.vzs, b.ms,
                                                   b.flagsSorted);
     }
-    if (b.timing) TP_HIP(hipEventRecord(b.ev[2], s));
+    SX_TRY_HIP(kWho, b.clock.mark(2, s));
     // ---- pairs
     if (n)
     {
         const double rmax = p.edges[nb];
-        PairArgs     a{b.xs, b.ys, b.zs, b.vxs, b.vys, b.vzs, b.ms, b.flagsSorted, b.keysSorted, b.cellStart, b.winKeys,
+        PairArgs     a{b.xs, b.ys, b.zs, b.vxs, b.vys, b.vzs, b.ms, b.flagsSorted, ix.keysSorted, ix.cellStart, b.winKeys,
                    b.edges, n, nb, p.series, p.stride == 1, (rmax * rmax) * (1.0 + 0x1p-50), g, acc};
         const int    nslot = __builtin_popcount(p.series & SX_TP_ALL);
         const size_t lds   = ((size_t)nb + 1 + (size_t)nb * (1 + 2 * nslot)) * sizeof(uint64_t);
@@ -461,12 +402,12 @@ int compute(Arena& arena, TwoPointBuffers& b, const sx_twopoint& p, const sx_fie
         else if (wantM) pairKernel<false, true><<<blocks(n), kBlock, lds, s>>>(a);
         else pairKernel<false, false><<<blocks(n), kBlock, lds, s>>>(a);
     }
-    if (b.timing) TP_HIP(hipEventRecord(b.ev[3], s));
+    SX_TRY_HIP(kWho, b.clock.mark(3, s));
     // ---- conversion
     convertKernel<<<(unsigned)((nOut + 255) / 256), 256, 0, s>>>(b.acc, b.winKeys, nb, b.out);
-    if (b.timing) TP_HIP(hipEventRecord(b.ev[4], s));
-    TP_HIP(hipGetLastError());
-    TP_HIP(hipMemcpyAsync(b.outHost, b.out, nOut * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    SX_TRY_HIP(kWho, b.clock.mark(4, s));
+    SX_TRY_HIP(kWho, hipGetLastError());
+    SX_TRY_HIP(kWho, hipMemcpyAsync(b.outHost, b.out, nOut * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
 
     void* const dst[1 + kSeries] = {res.count, res.U1, res.U2, res.U3, res.A3, res.T2, res.WW};
     const size_t tot = (size_t)nb * (1 + kSeries);
@@ -474,11 +415,12 @@ int compute(Arena& arena, TwoPointBuffers& b, const sx_twopoint& p, const sx_fie
     {
         for (int k = 0; k <= kSeries; ++k)
             if (dst[k] && (k == 0 || ((p.series >> (k - 1)) & 1u)))
-                TP_HIP(hipMemcpyAsync(dst[k], b.out + (size_t)k * nb, (size_t)nb * sizeof(uint64_t),
+                SX_TRY_HIP(kWho, hipMemcpyAsync(dst[k], b.out + (size_t)k * nb, (size_t)nb * sizeof(uint64_t),
                                       hipMemcpyDeviceToDevice, s));
-        if (res.totals) TP_HIP(hipMemcpyAsync(res.totals, b.out + tot, 3 * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+        if (res.totals)
+            SX_TRY_HIP(kWho, hipMemcpyAsync(res.totals, b.out + tot, 3 * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
     }
-    TP_HIP(hipStreamSynchronize(s));
+    SX_TRY_HIP(kWho, hipStreamSynchronize(s));
     if (toHost)
     {
         for (int k = 0; k <= kSeries; ++k)
@@ -486,9 +428,7 @@ int compute(Arena& arena, TwoPointBuffers& b, const sx_twopoint& p, const sx_fie
                 std::memcpy(dst[k], b.outHost + (size_t)k * nb, (size_t)nb * sizeof(uint64_t));
         if (res.totals) std::memcpy(res.totals, b.outHost + tot, 3 * sizeof(uint64_t));
     }
-    if (b.timing)
-        for (int k = 0; k < 4; ++k)
-            if (hipEventElapsedTime(&b.msStage[k], b.ev[k], b.ev[k + 1]) != hipSuccess) b.msStage[k] = 0;
+    b.clock.finish();
     uint64_t binned = 0;
     for (uint32_t k = 0; k < nb; ++k)
         binned += b.outHost[k];
@@ -496,12 +436,6 @@ int compute(Arena& arena, TwoPointBuffers& b, const sx_twopoint& p, const sx_fie
     b.stats[2] = b.outHost[tot], b.stats[3] = b.outHost[tot + 1], b.stats[4] = b.outHost[tot + 2];
     b.done     = true;
     return SX_OK;
-}
-
-void release(TwoPointBuffers& b)
-{
-    for (auto& e : b.ev)
-        if (e) (void)hipEventDestroy(e), e = nullptr;
 }
 
 } // namespace sx::twopoint

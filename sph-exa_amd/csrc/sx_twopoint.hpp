@@ -4,8 +4,9 @@
  *        particles, targets, pairs, separation, bins, terms, series, windows -- are the header comment of the section in
  *        include/sphexa_hip.h; this file holds the spec check, the grid decision and the typed owner of the scratch.
  *
- * The grid is that of the group finder (sx_cellgrid.hpp) with r_max = edges[nbins] in the place of the linking length.
- * The number format is the profiles' (sx_profile.hpp) with shift 64 and windows that follow from the largest velocity
+ * The grid and the index of the particles by cell are those of the group finder (sx_cellgrid.hpp) with r_max =
+ * edges[nbins] in the place of the linking length.
+ * The number format is the profiles' (sx_exactsum.hpp) with shift 64 and windows that follow from the largest velocity
  * component and mass alone, so one cheap pass over the particles fixes them and the pairs are walked once.
  */
 #pragma once
@@ -17,8 +18,8 @@
 
 #include "../../include/sphexa_hip.h"
 #include "sx_cellgrid.hpp"
-#include "sx_profile.hpp"
-#include "sx_tree.hpp"
+#include "sx_exactsum.hpp"
+#include "sx_step_timer.hpp"
 
 namespace sx::twopoint
 {
@@ -39,14 +40,11 @@ void chooseGrid(const sx_twopoint& p, const sx_box& box, uint64_t n, uint32_t di
 std::string whyRefused(const sx_twopoint* p, const sx_box* box, const sx_fields* f, uint32_t first, uint32_t last,
                        const sx_twopoint_result* res);
 
-/*! the typed owner of the scratch and the last call's figures.  Every "twopoint.*" arena tag is requested at one site in
- *  sx_twopoint.hip, which stores the pointer here. */
+/*! the typed owner of the scratch and the last call's figures.  Every "twopoint.*" arena tag is requested at one site,
+ *  the cell index's seven (cellgrid::Index) in cellgrid::build, the others in sx_twopoint.hip, which stores them here. */
 struct TwoPointBuffers
 {
-    // grid
-    uint32_t *keys{nullptr}, *keysSorted{nullptr}, *idx{nullptr}, *order{nullptr}; // order[s]: column index - first
-    uint32_t *cellCount{nullptr}, *cellStart{nullptr};                              // cells + 1
-    void*     sortTmp{nullptr};
+    cellgrid::Index grid;
     // the window pass: per particle of the range its flags; [vmax key, mmax key]
     uint8_t*  flags{nullptr};
     uint32_t* winKeys{nullptr};
@@ -59,10 +57,9 @@ struct TwoPointBuffers
     uint64_t* acc{nullptr};
     // [count nbins | U1 .. WW: nbins each | targets, nonfinite, coincident, pairs tested]
     uint64_t *out{nullptr}, *outHost{nullptr};
-    bool       timing{false}, done{false};
-    float      msStage[4]{};
-    uint64_t   stats[5]{};
-    hipEvent_t ev[5]{};
+    bool          done{false};
+    StageClock<4> clock; // grid, windows and gather, pairs, conversion
+    uint64_t      stats[5]{};
 };
 
 constexpr size_t kHead = 4; //!< the counters in front of acc
@@ -74,6 +71,6 @@ inline size_t outWords(uint32_t nbins) { return (size_t)nbins * (1 + kSeries) + 
 int compute(Arena& arena, TwoPointBuffers& b, const sx_twopoint& p, const sx_fields& f, const sx_box& box, uint32_t first,
             uint32_t last, const uint64_t* id, const sx_twopoint_result& res, bool toHost, hipStream_t s,
             std::string& err);
-void release(TwoPointBuffers& b);
+inline void release(TwoPointBuffers& b) { b.clock.release(); }
 
 } // namespace sx::twopoint

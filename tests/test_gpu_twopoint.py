@@ -266,3 +266,55 @@ def test_fof_profile_twopoint_share_a_context(ctx):
         for k, v in alone.items():
             if isinstance(v, np.ndarray):
                 assert np.array_equal(v, together[which][k], equal_nan=True), (which, k)
+
+
+def same_bits(a, b):
+    """two results of a Context call (dicts and sequences of arrays, scalars and None) equal bit for bit"""
+    if isinstance(a, dict):
+        return isinstance(b, dict) and a.keys() == b.keys() and all(same_bits(a[k], b[k]) for k in a)
+    if isinstance(a, (list, tuple)):
+        return type(a) is type(b) and len(a) == len(b) and all(same_bits(x, y) for x, y in zip(a, b))
+    if a is None or b is None:
+        return a is b
+    a, b = np.asarray(a), np.asarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def test_timed_calls_give_the_same_bits(ctx):
+    """each of fof, twopoint and profile untimed, timed and untimed again on one context: the same results and stats,
+    figures after the timed call, and zeros in every _ms after an untimed one (the times are "of the last call")"""
+    f = dict(tr.uniform(257, seed=257), h=np.full(257, 0.05, np.float32))
+    box = sx.make_box(*tr.PERIODIC)
+    edges = np.linspace(0.0, 0.3, 9)
+    prof = sx.SxProfile(np.linspace(0.0, 0.8, 9), ("vel",), center=(0.5, 0.5, 0.5))
+    passes = {
+        "fof": (lambda d: ctx.fof(d.fields, box, sx.SxFof(0.1, 2, 256)), ctx.fof_stats, ctx.set_fof_timing,
+                ctx.fof_times, 4),
+        "twopoint": (lambda d: ctx.twopoint(d.fields, box, sx.SxTwoPoint(edges, tr.ALL)), ctx.twopoint_stats,
+                     ctx.set_twopoint_timing, ctx.twopoint_times, 4),
+        "profile": (lambda d: ctx.profile(d.fields, box, prof), ctx.profile_stats, ctx.set_profile_timing,
+                    ctx.profile_times, 3),
+    }
+    ds = sx.DeviceState(ctx, f)
+    try:
+        for name, (call, stats, set_timing, times, stages) in passes.items():
+            got, figures = [], []
+            for timed in (False, True, False):
+                set_timing(timed)
+                try:
+                    got.append((call(ds), stats()))
+                finally:
+                    set_timing(False)
+                figures.append(times())
+            assert same_bits(got[0], got[1]) and same_bits(got[0], got[2]), name
+            for fig in figures:
+                ms = [v for k, v in fig.items() if k.endswith("_ms")]
+                assert len(ms) == stages and len(fig) == (4 if name != "profile" else stages + 1), (name, fig)
+                assert all(np.isfinite(v) and v >= 0.0 for v in fig.values()), (name, fig)
+            # kernels ran between the first and the last boundary of the timed call
+            assert sum(v for k, v in figures[1].items() if k.endswith("_ms")) > 0.0, (name, figures[1])
+            assert all(v == 0.0 for k, v in figures[2].items() if k.endswith("_ms")), (name, figures[2])
+            if name == "profile":
+                assert figures[0]["pass_bytes"] == figures[1]["pass_bytes"] == figures[2]["pass_bytes"] > 0
+    finally:
+        ctx.free_all()
