@@ -529,18 +529,10 @@ extern "C"
         c->nbLast  = last;
         c->nbNgmax = p->ngmax;
         c->nbValid = true;
-        if (stats)
-        {
-            stats->numFailed     = c->statsHost[1];
-            stats->maxNeighbors  = c->statsHost[2];
-            stats->sumNeighbors  = *reinterpret_cast<uint64_t*>(c->statsHost + 4);
-            stats->sumCandidates = *reinterpret_cast<uint64_t*>(c->statsHost + 6);
-            stats->sumUnion      = *reinterpret_cast<uint64_t*>(c->statsHost + 8);
-            stats->build         = c->nsPolicy.lastBuild;
-            stats->maxUnion      = c->statsHost[12];
-        }
-        if (c->statsHost[0] & 1u) return fail(c, SX_ERR_TRAVERSAL, "GPU traversal stack exhausted in neighbor search");
-        if (iterate_h && c->statsHost[1]) return fail(c, SX_ERR_NOT_CONVERGED, "coupled nc/h-updated failed to converge");
+        if (stats) *stats = nbStats(c->statsHost, c->nsPolicy.lastBuild);
+        if (c->statsHost[kStatFlags] & kFlagError)
+            return fail(c, SX_ERR_TRAVERSAL, "GPU traversal stack exhausted in neighbor search");
+        if (iterate_h && c->statsHost[kStatFailed]) return fail(c, SX_ERR_NOT_CONVERGED, "coupled nc/h-updated failed to converge");
         return SX_OK;
     }
 

@@ -40,10 +40,7 @@ constexpr int kGList  = 176; //!< per-wave M2P / P2P interaction lists (LDS: 31 
  *  6.2 * 2^-23 * 8 = 5.9e-6 per pair, inside the 1e-5 the variant is held to.  SFC-sorted inputs whose softening is of
  *  the order of the spacing never trip it: a far leaf is about as far from the box as from the origin, a near one no
  *  further from the origin than a few spacings. */
-#ifndef SX_ORIGIN_GUARD
-#define SX_ORIGIN_GUARD 8.0f
-#endif
-constexpr float kOriginGuard = SX_ORIGIN_GUARD;
+constexpr float kOriginGuard = 8.0f;
 
 //! leaf index -> node index (the reference's leafToInternal + numInternalNodes)
 __global__ void leafToNodeKernel(const int32_t* childOffsets, const int32_t* internalToLeaf, int numNodes,
@@ -324,14 +321,7 @@ __device__ __forceinline__ void m2pRec(float (&acc)[4], float tx, float ty, floa
     const float Qry      = fmaf(r0, B.y, fmaf(r1, B.w, r2 * C.x));
     const float Qrz      = fmaf(r0, B.z, fmaf(r1, C.x, r2 * C.y));
     const float rQr      = fmaf(r0, Qrx, fmaf(r1, Qry, r2 * Qrz));
-#ifdef SX_M2P_V0
-    const float rQrAndMonopole = (-2.5f * rQr * r_minus5 - A.w * r_minus1) * r_minus2;
-    acc[0] -= fmaf(A.w, r_minus1, 0.5f * r_minus5 * rQr);
-    acc[1] += fmaf(r_minus5, Qrx, rQrAndMonopole * r0);
-    acc[2] += fmaf(r_minus5, Qry, rQrAndMonopole * r1);
-    acc[3] += fmaf(r_minus5, Qrz, rQrAndMonopole * r2);
-#else
-    // the same expansion with the shared factors formed once (X = rQr r^-5, M0 r^-1) and every accumulation a fused
+    // the reference's expansion with the shared factors formed once (X = rQr r^-5, M0 r^-1) and every accumulation a fused
     // multiply-add into the running sum: 35 instead of 41 VALU per interaction (the reference's operation order is
     // kept by the exact variant, m2p(); this fast form agrees to float rounding)
     const float X    = rQr * r_minus5;
@@ -341,7 +331,6 @@ __device__ __forceinline__ void m2pRec(float (&acc)[4], float tx, float ty, floa
     acc[1] = fmaf(r_minus5, Qrx, fmaf(K, r0, acc[1]));
     acc[2] = fmaf(r_minus5, Qry, fmaf(K, r1, acc[2]));
     acc[3] = fmaf(r_minus5, Qrz, fmaf(K, r2, acc[3]));
-#endif
 }
 
 typedef float v2f __attribute__((ext_vector_type(2)));
@@ -364,15 +353,13 @@ struct __attribute__((aligned(16))) GSrc
     float  m, h;
 };
 
-#ifndef SX_GRAV_WPE
-#define SX_GRAV_WPE 5 // 96 VGPRs: five waves per SIMD (a few spills, outside the evaluation loops)
-#endif
+constexpr int kGravWpe = 5; // 96 VGPRs: five waves per SIMD (a few spills, outside the evaluation loops)
 //! COUNT: the per-target interaction counts (GravArgs::interactions, BhStats) -- a separate instantiation because the
 //! counters' registers cost the traversal 9 SGPR and 4 VGPR spills and 3.6 ms at Evrard n=300 (A/B).  PBC: the walk
 //! over the periodic images (GravArgs::numShells) -- likewise its own instantiation (the loop's state took the open
 //! walk from 14 to 48 VGPR spills)
 template<bool FAST, bool COUNT, bool PBC = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SX_GRAV_WPE))) void gravityTraverseKernel(GravArgs args)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGravWpe))) void gravityTraverseKernel(GravArgs args)
 {
     // the fields the traversal reads, as scalars: with the many closures below capturing the kernel argument by
     // reference, the compiler copied the whole struct to scratch and addressed it through flat pointers

@@ -34,13 +34,6 @@ namespace cluster
 
 constexpr int kB = kCluster; // threads per workgroup
 
-#ifndef SX_LEAN_DEPTH
-#define SX_LEAN_DEPTH 2
-#endif
-#ifndef SX_ME_LEAN
-#define SX_ME_LEAN true // momentum: one record in flight (see neighborLoop)
-#endif
-
 //! per-workgroup cluster bookkeeping
 struct Clu
 {
@@ -158,7 +151,7 @@ __device__ __forceinline__ void combineShares(const Clu& cu, float (&v)[NV], flo
  *  of particle j.  `resident` carries "the whole union is already in LDS" from a previous pass over the same records.
  *  With the union resident (and the lists packed12) the loop is software-pipelined: the LDS records of the next
  *  neighbors are read while the current ones are computed, and list groups are prefetched one ahead. */
-template<int CH, int SPLIT, bool PF = true, bool LEAN = false, class Stage, class Load, class Compute>
+template<int CH, int SPLIT, bool PF = true, class Stage, class Load, class Compute>
 __device__ __forceinline__ void neighborLoop(const Clu& cu, Stage&& stage, Load&& load, Compute&& compute,
                                              bool& resident)
 {
@@ -204,7 +197,7 @@ __device__ __forceinline__ void neighborLoop(const Clu& cu, Stage&& stage, Load&
         };
 #define SX_P12(E, G) p12::get<E>((G).a, (G).b, (G).c)
         uint32_t g = gBeg;
-        if constexpr (LEAN || !PF)
+        if constexpr (!PF)
         {
             // one record in flight while the other is computed: the LDS read latency (~100 cycles) is far below a
             // heavy pair's compute, and half the record registers let one more wave per SIMD in (momentum 152 -> 128
@@ -250,7 +243,7 @@ __device__ __forceinline__ void neighborLoop(const Clu& cu, Stage&& stage, Load&
         // before a computation covers only the records it consumes (a masked prefetch leaves a path on which the
         // previous pair's reads may still be outstanding, and the merged wait then also waits for the new reads).
         // Measured (Sedov 64M): IAD -0.4 ms, AV -0.3 ms; momentum +0.3..0.7 ms (its records are 80 B: the extra
-        // registers of the unmasked form cost more than the wait), so momentum takes the LEAN form above.
+        // registers of the unmasked form cost more than the wait), so momentum takes the lean form above (PF = false).
         // Two pairs of record buffers used alternately (no register copies).
         auto         a0 = load(SX_P12(0, cur));
         auto         b0 = load(SX_P12(1, cur));
@@ -436,14 +429,14 @@ __global__ __launch_bounds__(kB * SPLIT) void veDefGradhKernel(PairArgs a)
     }
 }
 
-// ---- IAD + divv/curlv: IADJLoop (iad_kern.hpp:43-109) + divV_curlVJLoop (divv_curlv_kern.hpp:43-123) -------------
-//! STD: IADJLoopSTD (hydro_std/iad_kern.hpp:12-77), volumes m/rho and no velocity derivatives
-template<int CH, int SPLIT, bool STD = false>
-__global__ __launch_bounds__(kB * SPLIT) void iadDivvCurlvKernel(PairArgs a)
+// ---- IAD of the std propagator: IADJLoopSTD (hydro_std/iad_kern.hpp:12-77), volumes m/rho and no velocity derivatives
+//      (VE takes iadDivvCurlvFusedKernel below)
+template<int CH, int SPLIT>
+__global__ __launch_bounds__(kB * SPLIT) void iadStdKernel(PairArgs a)
 {
-    __shared__ float4 sP[CH];               // x, y, z, vol = xm/kx (std: m/rho)
-    __shared__ float4 sV[STD ? 1 : CH];     // vx, vy, vz, xm
+    __shared__ float4 sP[CH]; // x, y, z, vol = m/rho
     __shared__ float  s_red[kClusterWaves * SPLIT];
+    // (room for nine sums per share, six are combined: the kernel's LDS size stays as it was measured)
     __shared__ float  s_scr[SPLIT > 1 ? 9 * SPLIT * kCluster : 1];
     const Clu   cu  = setup<SPLIT>(a, s_red);
     const RecX  ri  = a.rx[cu.iSafe];
@@ -451,17 +444,8 @@ __global__ __launch_bounds__(kB * SPLIT) void iadDivvCurlvKernel(PairArgs a)
     const float hi = ri.h, hiInv = 1.0f / hi, hiInv2 = hiInv * hiInv, h2 = 2.0f * hi;
     auto        stage = [&](uint32_t j, uint32_t slot) {
         const RecX r = a.rx[j];
-        if constexpr (STD)
-            sP[slot] = make_float4(relc(r.x, cu.ox, a.box, 0), relc(r.y, cu.oy, a.box, 1), relc(r.z, cu.oz, a.box, 2),
-                                   r.m / a.rs[j].rho);
-        else
-        {
-            const RecV v = a.rv[j];
-            const RecT t = a.rt[j];
-            sP[slot]     = make_float4(relc(r.x, cu.ox, a.box, 0), relc(r.y, cu.oy, a.box, 1),
-                                   relc(r.z, cu.oz, a.box, 2), t.xm / t.kx);
-            sV[slot]     = make_float4(v.vx, v.vy, v.vz, t.xm);
-        }
+        sP[slot] = make_float4(relc(r.x, cu.ox, a.box, 0), relc(r.y, cu.oy, a.box, 1), relc(r.z, cu.oz, a.box, 2),
+                               r.m / a.rs[j].rho);
     };
     float t11 = 0, t12 = 0, t13 = 0, t22 = 0, t23 = 0, t33 = 0;
     bool  res = false;
@@ -487,72 +471,10 @@ __global__ __launch_bounds__(kB * SPLIT) void iadDivvCurlvKernel(PairArgs a)
     float cc[6];
     iadInvert(t11, t12, t13, t22, t23, t33, hi, a.K, cc);
     const float c11i = cc[0], c12i = cc[1], c13i = cc[2], c22i = cc[3], c23i = cc[4], c33i = cc[5];
-    if constexpr (STD)
-    {
-        if (cu.valid && cu.part == 0)
-        {
-            const uint32_t i = cu.i;
-            a.c11[i] = c11i, a.c12[i] = c12i, a.c13[i] = c13i, a.c22[i] = c22i, a.c23[i] = c23i, a.c33[i] = c33i;
-        }
-        return;
-    }
-    const RecV  vi  = a.rv[cu.iSafe];
-    const RecT  ti  = a.rt[cu.iSafe];
-    const float kxi = ti.kx;
-
-    float dVx0 = 0, dVx1 = 0, dVx2 = 0, dVy0 = 0, dVy1 = 0, dVy2 = 0, dVz0 = 0, dVz1 = 0, dVz2 = 0;
-    neighborLoop<CH, SPLIT>(
-        cu, stage, [&](uint32_t p) { return Rec8{sP[p], sV[p]}; },
-        [&](const Rec8& r) {
-            const float4& q  = r.a;
-            const float4& v  = r.b;
-            float         rx = xi - q.x, ry = yi - q.y, rz = zi - q.z;
-            pbcRule(cu, a.box, h2, rx, ry, rz);
-            const float Wi   = kernelWt((rx * rx + ry * ry + rz * rz) * hiInv2);
-            const float tA0  = -(c11i * rx + c12i * ry + c13i * rz) * Wi;
-            const float tA1  = -(c12i * rx + c22i * ry + c23i * rz) * Wi;
-            const float tA2  = -(c13i * rx + c23i * ry + c33i * rz) * Wi;
-            const float fx = (v.x - vi.vx) * v.w, fy = (v.y - vi.vy) * v.w, fz = (v.z - vi.vz) * v.w;
-            dVx0 += tA0 * fx;
-            dVx1 += tA1 * fx;
-            dVx2 += tA2 * fx;
-            dVy0 += tA0 * fy;
-            dVy1 += tA1 * fy;
-            dVy2 += tA2 * fy;
-            dVz0 += tA0 * fz;
-            dVz1 += tA1 * fz;
-            dVz2 += tA2 * fz;
-        },
-        res);
-    {
-        float v[9] = {dVx0, dVx1, dVx2, dVy0, dVy1, dVy2, dVz0, dVz1, dVz2};
-        __syncthreads(); // s_scr still holds the tau shares being read
-        combineShares<SPLIT>(cu, v, s_scr);
-        dVx0 = v[0], dVx1 = v[1], dVx2 = v[2], dVy0 = v[3], dVy1 = v[4], dVy2 = v[5], dVz0 = v[6], dVz1 = v[7],
-        dVz2 = v[8];
-    }
     if (cu.valid && cu.part == 0)
     {
         const uint32_t i = cu.i;
         a.c11[i] = c11i, a.c12[i] = c12i, a.c13[i] = c13i, a.c22[i] = c22i, a.c23[i] = c23i, a.c33[i] = c33i;
-        const float norm_kxi = (float)(a.K * (double)(hiInv * hiInv * hiInv) / (double)kxi);
-        const float divv_i   = norm_kxi * (dVx0 + dVy1 + dVz2);
-        a.divv[i]            = divv_i;
-        if (a.rcOut) a.rcOut[i] = RecC{c11i, c12i, c13i, c22i, c23i, c33i, divv_i, ti.xm / ti.kx};
-        if (a.curlv)
-        {
-            const float cv0 = dVz1 - dVy2, cv1 = dVx2 - dVz0, cv2 = dVy0 - dVx1;
-            a.curlv[i]      = norm_kxi * norm3(cv0, cv1, cv2);
-        }
-        if (a.dV11) // doGradV (divv_curlv_kern.hpp:113-121)
-        {
-            a.dV11[i] = norm_kxi * dVx0;
-            a.dV12[i] = norm_kxi * (dVx1 + dVy0);
-            a.dV13[i] = norm_kxi * (dVx2 + dVz0);
-            a.dV22[i] = norm_kxi * dVy1;
-            a.dV23[i] = norm_kxi * (dVy2 + dVz1);
-            a.dV33[i] = norm_kxi * dVz2;
-        }
     }
 }
 
@@ -1095,7 +1017,7 @@ __global__ __launch_bounds__(kB * SPLIT) void momentumEnergyKernel(PairArgs a, u
                 my += ki * u2i + kj * u2j;
                 mz += ki * u3i + kj * u3j;
             };
-        neighborLoop<CH, SPLIT, false, SX_ME_LEAN>(
+        neighborLoop<CH, SPLIT, false>( // one record in flight (see neighborLoop)
             cu, [&](uint32_t j, uint32_t slot) { stageRaw(meLoadRaw<AVC>(a, j), slot); }, loadRec, computeOne,
             res);
         // the next cluster's union records load during the share combination and this cluster's stores
@@ -1251,39 +1173,14 @@ __global__ __launch_bounds__(kB * SPLIT) void momentumStdKernel(PairArgs a)
 // LDS capacity per kernel (records of 16 / 20 / 32 / 36 / 80 B): the momentum union fills the CU's 160 KiB with
 // one workgroup; the lighter kernels keep two or more workgroups per CU.  SPLIT waves share each group's lists so a
 // CU holds enough waves to reach the VALU's two-cycle issue (one wave alone issues every four cycles).
-#ifndef SX_CH_ME
-#define SX_CH_ME 2000
-#endif
-#ifndef SX_SPLIT_XM
-#define SX_SPLIT_XM 2
-#endif
-#ifndef SX_SPLIT_VD
-#define SX_SPLIT_VD 2
-#endif
-#ifndef SX_SPLIT_IAD
-#define SX_SPLIT_IAD 2
-#endif
-#ifndef SX_SPLIT_AV_LARGE
-#define SX_SPLIT_AV_LARGE 3 // the 2048-record launch runs two workgroups per CU: three shares keep six waves per SIMD
-#endif
-#ifndef SX_SPLIT_AV
-#define SX_SPLIT_AV 2
-#endif
-#ifndef SX_SPLIT_ME
-#define SX_SPLIT_ME 3 // 12 waves on the CU's one (persistent) momentum workgroup: the loop's 104 VGPRs + the next cluster's prefetch
-#endif
-#ifndef SX_SPLIT_ME_AVC
-#define SX_SPLIT_ME_AVC 2 // the avClean variant needs 190 VGPRs: two waves per SIMD
-#endif
+constexpr int kSplitXm = 2, kSplitVd = 2, kSplitIad = 2, kSplitAv = 2;
+constexpr int kSplitAvLarge = 3; // the 2048-record launch runs two workgroups per CU: three shares keep six waves per SIMD
+constexpr int kSplitMe = 3; // 12 waves on the CU's one (persistent) momentum workgroup: the loop's 104 VGPRs + the next cluster's prefetch
+constexpr int kSplitMeAvc = 2; // the avClean variant needs 190 VGPRs: two waves per SIMD
 // kChVd = 2000: 40 KB of records, four VeDefGradh workgroups per CU (eight waves per SIMD)
-#ifndef SX_CH_IAD
-#define SX_CH_IAD 1660 // 53 KB: three IAD workgroups per CU (24 waves at 79 VGPRs; 2 at CH 1900: 10.3 -> 9.4 ms at 64M)
-#endif
-#ifndef SX_CH_AV
-#define SX_CH_AV 1470 // 53 KB: three AV workgroups per CU (2048: two; Sedov 64M AV 10.0 -> 8.6 ms, step -1.2 ms)
-#endif
-constexpr int kChXm = 2048, kChVd = 2000, kChIad = SX_CH_IAD, kChAv = SX_CH_AV, kChAvLarge = 2048, kChMe = SX_CH_ME,
-              kChMeAvc = 1536;
+constexpr int kChIad = 1660; // 53 KB: three IAD workgroups per CU (24 waves at 79 VGPRs; 2 at CH 1900: 10.3 -> 9.4 ms at 64M)
+constexpr int kChAv = 1470; // 53 KB: three AV workgroups per CU (2048: two; Sedov 64M AV 10.0 -> 8.6 ms, step -1.2 ms)
+constexpr int kChXm = 2048, kChVd = 2000, kChAvLarge = 2048, kChMe = 2000, kChMeAvc = 1536;
 
 static inline unsigned clusters(const PairArgs& a)
 {
@@ -1292,15 +1189,15 @@ static inline unsigned clusters(const PairArgs& a)
 
 void xmass(const PairArgs& a, hipStream_t s)
 {
-    if (a.numGroups && clusters(a)) xmassKernel<kChXm, SX_SPLIT_XM><<<clusters(a), kB * SX_SPLIT_XM, 0, s>>>(a);
+    if (a.numGroups && clusters(a)) xmassKernel<kChXm, kSplitXm><<<clusters(a), kB * kSplitXm, 0, s>>>(a);
 }
 void veDefGradh(const PairArgs& a, hipStream_t s)
 {
-    if (a.numGroups && clusters(a)) veDefGradhKernel<kChVd, SX_SPLIT_VD><<<clusters(a), kB * SX_SPLIT_VD, 0, s>>>(a);
+    if (a.numGroups && clusters(a)) veDefGradhKernel<kChVd, kSplitVd><<<clusters(a), kB * kSplitVd, 0, s>>>(a);
 }
 void iadDivvCurlv(const PairArgs& a, hipStream_t s)
 {
-    if (a.numGroups && clusters(a)) iadDivvCurlvFusedKernel<kChIad, SX_SPLIT_IAD><<<clusters(a), kB * SX_SPLIT_IAD, 0, s>>>(a);
+    if (a.numGroups && clusters(a)) iadDivvCurlvFusedKernel<kChIad, kSplitIad><<<clusters(a), kB * kSplitIad, 0, s>>>(a);
 }
 //! AV switches in two launches by union size: clusters whose union fits 1470 records run three workgroups per CU (53
 //! KB), larger ones (the lattice's 122-neighbor steps: ~1485 per cluster) two per CU with 2048 records instead of the
@@ -1308,9 +1205,9 @@ void iadDivvCurlv(const PairArgs& a, hipStream_t s)
 void avSwitches(const PairArgs& a, hipStream_t s)
 {
     if (!a.numGroups || !clusters(a)) return;
-    avSwitchesKernel<kChAv, SX_SPLIT_AV, 0, kChAv><<<clusters(a), kB * SX_SPLIT_AV, 0, s>>>(a);
+    avSwitchesKernel<kChAv, kSplitAv, 0, kChAv><<<clusters(a), kB * kSplitAv, 0, s>>>(a);
     if (a.unionMax == 0 || a.unionMax > (uint32_t)kChAv) // else every workgroup of it would exit after one load
-        avSwitchesKernel<kChAvLarge, SX_SPLIT_AV_LARGE, kChAv + 1, 0><<<clusters(a), kB * SX_SPLIT_AV_LARGE, 0, s>>>(a);
+        avSwitchesKernel<kChAvLarge, kSplitAvLarge, kChAv + 1, 0><<<clusters(a), kB * kSplitAvLarge, 0, s>>>(a);
 }
 //! min over the per-workgroup Courant time-steps of one launch -> *minDt (one atomic)
 __global__ __launch_bounds__(1024) void reduceBlockDtKernel(const float* v, uint32_t n, float* minDt)
@@ -1354,20 +1251,20 @@ void momentumEnergy(const PairArgs& a, hipStream_t s)
     const uint32_t ncl = clusters(a);
     if (!a.numGroups || !ncl) return;
     const uint32_t grid = momentumGrid(ncl);
-    if (a.avClean) momentumEnergyKernel<kChMeAvc, SX_SPLIT_ME_AVC, true><<<grid, kB * SX_SPLIT_ME_AVC, 0, s>>>(a, ncl);
-    else momentumEnergyKernel<kChMe, SX_SPLIT_ME, false><<<grid, kB * SX_SPLIT_ME, 0, s>>>(a, ncl);
+    if (a.avClean) momentumEnergyKernel<kChMeAvc, kSplitMeAvc, true><<<grid, kB * kSplitMeAvc, 0, s>>>(a, ncl);
+    else momentumEnergyKernel<kChMe, kSplitMe, false><<<grid, kB * kSplitMe, 0, s>>>(a, ncl);
     if (a.blockDt) reduceBlockDtKernel<<<1, 1024, 0, s>>>(a.blockDt, grid, a.minDt);
 }
 // std propagator: the IAD kernel without velocity derivatives (16 B records), momentum with 68 B records
 constexpr int kChIadStd = 2048, kChMeStd = 2048;
 void iadStd(const PairArgs& a, hipStream_t s)
 {
-    if (a.numGroups && clusters(a)) iadDivvCurlvKernel<kChIadStd, SX_SPLIT_IAD, true><<<clusters(a), kB * SX_SPLIT_IAD, 0, s>>>(a);
+    if (a.numGroups && clusters(a)) iadStdKernel<kChIadStd, kSplitIad><<<clusters(a), kB * kSplitIad, 0, s>>>(a);
 }
 void momentumStd(const PairArgs& a, hipStream_t s)
 {
     if (!a.numGroups || !clusters(a)) return;
-    momentumStdKernel<kChMeStd, SX_SPLIT_ME><<<clusters(a), kB * SX_SPLIT_ME, 0, s>>>(a);
+    momentumStdKernel<kChMeStd, kSplitMe><<<clusters(a), kB * kSplitMe, 0, s>>>(a);
     reduceBlockDt(a, s);
 }
 

@@ -77,16 +77,9 @@ constexpr int kCandWords = kCandSpace / 32;
 constexpr int kBatch = SX_NS_BATCH; //!< chunks whose hit masks a wave keeps before expanding them into its lists
 static_assert(kBatch <= 32, "nonzero-chunk bits per lane");
 
-#ifndef SX_NS_NT_LIST
-#define SX_NS_NT_LIST 0
-#endif
-//! a u16-pair list word: the lists are read only by later kernels, a streaming store keeps them from evicting the
-//! hit-mask rows and candidate coordinates this kernel re-reads from L2 (variant SX_NS_NT_LIST)
-__device__ __forceinline__ void storeList(uint32_t* p, uint32_t w)
-{
-    if constexpr (SX_NS_NT_LIST) __builtin_nontemporal_store(w, p);
-    else *p = w;
-}
+//! a u16-pair list word, by a plain store (the variant with a streaming store, meant to keep the lists from evicting
+//! the hit-mask rows and candidate coordinates this kernel re-reads from L2, was not kept)
+__device__ __forceinline__ void storeList(uint32_t* p, uint32_t w) { *p = w; }
 
 
 __device__ __forceinline__ uint32_t bitRank(const uint32_t* bits, const uint32_t* pre, uint32_t idx)
@@ -178,7 +171,7 @@ __device__ __forceinline__ int clusterCollectLeaves(const int32_t* __restrict__ 
 {
     const uint64_t ltMask  = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     int            numCand = 0, qh = 0, qt = 0;
-    overflow               = 0u; // bit 64: traversal queue, bit 32: candidate leaves (stats[0] bits)
+    overflow               = 0u; // kFlagQueue: traversal queue, kFlagLeaves: candidate leaves
     if (overlaps(0))
     {
         const int c0 = childOffsets[0];
@@ -223,12 +216,12 @@ __device__ __forceinline__ int clusterCollectLeaves(const int32_t* __restrict__ 
         numCand += (int)totL;
         qt += (int)totI;
         qh += consumed;
-        if (qt - qh > kQCap) overflow |= 64u;
+        if (qt - qh > kQCap) overflow |= kFlagQueue;
         __syncthreads(); // the queue and cand writes are visible; s_cnt is rewritten by the next step
     }
     if (numCand > kCCap)
     {
-        overflow |= 32u;
+        overflow |= kFlagLeaves;
         numCand = kCCap;
     }
     return numCand;
@@ -262,7 +255,7 @@ findNeighborsKernel(NsArgs a)
         a.redoList ? __builtin_amdgcn_readfirstlane(a.redoList[0]) : (a.numGroups + kClusterWaves - 1) / kClusterWaves;
     if (numClusters == 0) return;
 #ifdef SX_NS_SMALL
-    if (a.redo && blockIdx.x == 0 && threadIdx.x == 0) a.stats[11] = 1u; // the compact build ran first
+    if (a.redo && blockIdx.x == 0 && threadIdx.x == 0) a.stats[kStatCompactFirst] = 1u;
 #endif
     const int      wave        = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // wave-uniform: scalar
     const int      lane        = threadIdx.x & 63;
@@ -517,7 +510,7 @@ findNeighborsKernel(NsArgs a)
             lane, overflow);
         if (wave == 0)
         {
-            if (lane == 0 && s_nreg > kMaxRegions) overflow |= 16u; // regions dropped: the candidates may be short
+            if (lane == 0 && s_nreg > kMaxRegions) overflow |= kFlagRegions; // the candidates may be short
             // exclusive scan of the candidate leaf sizes
             uint32_t run = 0;
             for (int b = 0; b < nCand; b += kWave)
@@ -543,11 +536,10 @@ findNeighborsKernel(NsArgs a)
             if (lane == 0)
             {
                 s_cOff[nCand] = run;
-                // error bits: 2 = traversal queue / candidate-leaf list full / regions dropped (which: 64 / 32 /
-                // 16), 4 = candidate space beyond u16
-                unsigned f = (overflow ? 2u | overflow : 0u) | ((local && run > (uint32_t)kCandSpace) ? 4u : 0u);
+                unsigned f = (overflow ? kFlagWalk | overflow : 0u) |
+                             ((local && run > (uint32_t)kCandSpace) ? kFlagCandSpace : 0u);
 #ifdef SX_NS_SMALL
-                if (a.forceOverflow) f |= 4u; // test hook (sx_set_search_mode 3): exercise the device-side fallback
+                if (a.forceOverflow) f |= kFlagCandSpace; // test hook (sx_set_search_mode 3): exercise the device-side fallback
 #endif
                 // with a redo list (compact build first) an over-capacity cluster is handed to the large build; a
                 // skin build's cluster over the large build's capacities is left unbuilt with an over-capacity union
@@ -558,17 +550,18 @@ findNeighborsKernel(NsArgs a)
                 {
                     a.redo[1 + atomicAdd(&a.redo[0], 1u)] = c;
 #ifdef SX_NS_SMALL
-                    atomicAdd(&a.stats[10], 1u); // compact -> large
+                    atomicAdd(&a.stats[kStatToLarge], 1u); // compact -> large
 #else
-                    atomicAdd(&a.stats[17], 1u); // large -> large with smaller search regions
+                    atomicAdd(&a.stats[kStatToSmallRegs], 1u); // large -> large with smaller search regions
 #endif
                 }
                 else if (f && skinB) a.ucount[c] = 0xffffffffu;
                 else if (f)
                 {
-                    atomicOr(&a.stats[0], 1u | f);
+                    atomicOr(&a.stats[kStatFlags], kFlagError | f);
                     // a failing cluster for the error report: its index, candidate leaves and search regions
-                    if (atomicCAS(&a.stats[14], 0u, c + 1u) == 0u) a.stats[15] = (uint32_t)nCand, a.stats[16] = s_nreg;
+                    if (atomicCAS(&a.stats[kStatOverCluster], 0u, c + 1u) == 0u)
+                        a.stats[kStatOverLeaves] = (uint32_t)nCand, a.stats[kStatOverRegions] = s_nreg;
                 }
                 s_numCand = f ? 0 : nCand;
             }
@@ -999,7 +992,7 @@ findNeighborsKernel(NsArgs a)
                 while (s_cOff[cc + 1] <= idx)
                     ++cc;
                 if (run < a.ucap - a.uoff) uni[run] = s_p0[cc] + (idx - s_cOff[cc]);
-                else if (!(a.skin1 > 0.0f)) atomicOr(&a.stats[0], 1u | 8u); // union beyond its capacity (bit 8);
+                else if (!(a.skin1 > 0.0f)) atomicOr(&a.stats[kStatFlags], kFlagError | kFlagUnion);
                 // a skin build records the true size (ucount) instead: the filter sends such a cluster to the exact search
                 ++run;
             }
@@ -1097,7 +1090,7 @@ findNeighborsKernel(NsArgs a)
     const unsigned long long tested = waveSum(valid ? candTested : 0ull);
     if (lane == 0)
     {
-        if (nfail && !abandoned) atomicAdd(&a.stats[1], nfail); // failures only: rare
+        if (nfail && !abandoned) atomicAdd(&a.stats[kStatFailed], nfail); // failures only: rare
         s_cst[wave] = make_uint4(maxCnt, (uint32_t)nstore, (uint32_t)tested, 0u);
     }
     if (threadIdx.x == 0) s_next = grabCluster(a.work, numClusters, ticket);
@@ -1177,7 +1170,6 @@ unsigned searchGrid()
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, findNeighborsKernel, kCluster, 0);
         grid = (unsigned)std::max(1, cus) * (unsigned)std::max(1, perCu);
-        if (getenv("SX_NS_DEBUG_GRID")) fprintf(stderr, "search grid %u (%d per CU)\n", grid, perCu);
     }
     return grid;
 }

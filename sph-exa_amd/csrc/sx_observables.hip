@@ -83,17 +83,11 @@ __global__ __launch_bounds__(256) void conservedFinalKernel(const double* partia
 // in a fixed order, the wave, the block and the final pass sum in fixed trees: the result is the same from run to
 // run and on any device.  Per workgroup and sum one waveSum, then all sums cross LDS behind ONE barrier.
 
-// overridable for A/B timing builds (make EXTRA="-DSX_OBS_UNROLL=4 -DSX_OBS_GRID=512"); results depend on both
-#ifndef SX_OBS_UNROLL
-#define SX_OBS_UNROLL 2
-#endif
-#ifndef SX_OBS_GRID
-#define SX_OBS_GRID 1024
-#endif
+// the results depend on kObsUnroll and kObsGrid (the partition)
 constexpr int kObsBlock  = 256;
-constexpr int kObsUnroll = SX_OBS_UNROLL;
+constexpr int kObsUnroll = 2;
 constexpr int kObsChunk  = kObsBlock * kObsUnroll;
-constexpr int kObsGrid   = SX_OBS_GRID; // 4 workgroups per CU of an MI355X, 2 loads of every field in flight per lane
+constexpr int kObsGrid   = 1024; // 4 workgroups per CU of an MI355X, 2 loads of every field in flight per lane
 // register budget (128 VGPRs) at which the whole grid is resident at once there; the KH growth's double exp, sin and
 // cos would spill under it and take one wave less (that kind is bound by their arithmetic, not by residency)
 constexpr int kObsWavesPerSimd = 4;

@@ -452,39 +452,6 @@ int buildSearchArgs(sx_sim* s, NsArgs& na)
     return SX_OK;
 }
 
-//! timing hook for search A/B runs (scripts/ab_search.sh, SX_SEARCH_REPS): the search without the h iteration,
-//! repeated on this step's state before the real search
-int searchReps(sx_sim* s, const NsArgs& na, hipStream_t st)
-{
-    const char* reps = getenv("SX_SEARCH_REPS");
-    if (!reps) return SX_OK;
-    NsArgs x     = na;
-    x.iterateH   = 0;
-    NsPolicy pol;
-    pol.mode = getenv("SX_SEARCH_LARGE") ? 1 : 2; // compact build first (as in the real search)
-    x.policy = &pol;
-    const int R  = std::max(1, atoi(reps));
-    s->skin.listsKept = false; // this search rewrites the exact lists
-    s->skin.lb        = ListsB{};
-    hipEvent_t t0 = nullptr, t1 = nullptr; // its own: the step's timer is mid-step (a failing run keeps them)
-    SIM_HIP(hipEventCreate(&t0));
-    SIM_HIP(hipEventCreate(&t1));
-    SIM_HIP(hipEventRecord(t0, st));
-    for (int r = 0; r < R; ++r)
-    {
-        SIM_HIP(hipMemsetAsync(s->stats, 0, kStatsWords * 4, st));
-        SIM_HIP(findNeighbors(x, st));
-    }
-    SIM_HIP(hipEventRecord(t1, st));
-    SIM_HIP(hipEventSynchronize(t1));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, t0, t1);
-    (void)hipEventDestroy(t0);
-    (void)hipEventDestroy(t1);
-    fprintf(stderr, "search-reps: %.3f ms per search (%d reps)\n", ms / R, R);
-    return SX_OK;
-}
-
 //! a reuse step that cannot stand (the exact search over capacity on the drifted tree; several ranks: on some rank, or
 //! a sphere searched again outside the build's halo region): h as before the filter, then this step's search again
 //! after a full sync + build
@@ -545,7 +512,7 @@ int searchOnce(sx_sim* s, StepCtx& c, const NsArgs& na, SkinCounts& skc, bool& r
         if (!c.dist)
         {
             if (resync) return skinRedoFromSync(s, c);
-            skinDecide(s->skin, c.reuse, skc, skc.stale, skc.clusters);
+            skinBookkeeping(s->skin, c.reuse, skc, skc.stale, skc.clusters);
             s->skin.stepClusters = skc.clusters;
         }
     }
@@ -566,7 +533,7 @@ int searchOnce(sx_sim* s, StepCtx& c, const NsArgs& na, SkinCounts& skc, bool& r
  *  request margin (a build or a plain search); on a reuse step, the spheres of the clusters searched again this step
  *  (coverListKernel).  One exchange of five words carries every decision the ranks take together: [0] halo margin too
  *  small, [1] the reuse step must be redone from a full sync + build, [2] stale clusters, [3] clusters, [4] clusters
- *  whose skin would not survive another such drift (the filter's stats[13]).  dec: the summed words (host) */
+ *  whose skin would not survive another such drift (the filter's kStatSkinThin).  dec: the summed words (host) */
 int exchangeDecisions(sx_sim* s, StepCtx& c, const SkinCounts& skc, bool resync, double reqMargin, uint32_t*& dec)
 {
     hipStream_t st  = c.st;
@@ -577,7 +544,7 @@ int exchangeDecisions(sx_sim* s, StepCtx& c, const SkinCounts& skc, bool resync,
     SIM_HIP(hipMemcpyAsync(flg, dec, 5 * 4, hipMemcpyHostToDevice, st));
     if (!c.reuse) chunkCheck(s, reqMargin, flg, st);
     else if (int e = skinCoverCheck(s, skc, flg + 1, st)) return e;
-    if (c.skinOn) SIM_HIP(hipMemcpyAsync(flg + 4, s->stats + 13, 4, hipMemcpyDeviceToDevice, st));
+    if (c.skinOn) SIM_HIP(hipMemcpyAsync(flg + 4, s->stats + kStatSkinThin, 4, hipMemcpyDeviceToDevice, st));
     // the retry decision must be global: a rank redoing the sync alone would deadlock the collectives
     SIM_COMM(s->comm->allreduceSumU32(flg, 5, st));
     SIM_HIP(hipMemcpyAsync(dec, flg, 5 * 4, hipMemcpyDeviceToHost, st));
@@ -587,7 +554,7 @@ int exchangeDecisions(sx_sim* s, StepCtx& c, const SkinCounts& skc, bool resync,
     SIM_HIP(hipStreamSynchronize(st));
     if (syncErrFailed(s)) return SX_ERR_TRAVERSAL;
     if (overlapping(s, c.H)) s->nInterior = s->clsHost[0], s->nBoundary = s->clsHost[1];
-    s->statsHost[3] = dec[0];
+    s->statsHost[kStatHaloShort] = dec[0];
     return SX_OK;
 }
 
@@ -620,8 +587,6 @@ int searchStage(sx_sim* s, StepCtx& c)
         NsArgs na{};
         if (int e = buildSearchArgs(s, na)) return e;
         c.powTab = na.powTab;
-        if (attempt == 0)
-            if (int e = searchReps(s, na, st)) return e;
         bool resync = false;
         if (int e = searchOnce(s, c, na, skc, resync)) return e;
         if (!c.dist)
@@ -648,7 +613,7 @@ int searchStage(sx_sim* s, StepCtx& c)
         }
         if (c.skinOn)
         {
-            skinDecide(s->skin, c.reuse, skc, dec[2], dec[3]);
+            skinBookkeeping(s->skin, c.reuse, skc, dec[2], dec[3]);
             s->skin.stepClusters = dec[3];
             s->skin.stepS13      = dec[4];
         }
@@ -798,7 +763,7 @@ int forcesVe(sx_sim* s, StepCtx& c, PairArgs pa)
                 q.rtOut    = fused ? s->rt : nullptr; // AV writes the locals' records with the new alpha
                 // the largest union of this step's search: the host waits here for the search to finish
                 // (long done on the device when the kernels queued before AV still run, so nothing idles)
-                if (s->evStats && hipEventSynchronize(s->evStats) == hipSuccess) q.unionMax = s->statsHost[12];
+                if (s->evStats && hipEventSynchronize(s->evStats) == hipSuccess) q.unionMax = s->statsHost[kStatMaxUnion];
                 H.avSwitches(q, st);
             },
             pa, st))
@@ -862,29 +827,25 @@ int finishStep(sx_sim* s, const StepCtx& c)
     if (s->turb)
         for (int k = 0; k < 2; ++k)
             (void)hipEventElapsedTime(&s->turb->ms[k], s->turb->ev[k], s->turb->ev[k + 1]);
-    s->lastStats.numFailed     = s->statsHost[1];
-    s->lastStats.maxNeighbors  = s->statsHost[2];
-    s->lastStats.sumNeighbors  = *reinterpret_cast<uint64_t*>(s->statsHost + 4);
-    s->lastStats.sumCandidates = *reinterpret_cast<uint64_t*>(s->statsHost + 6);
-    s->lastStats.sumUnion      = *reinterpret_cast<uint64_t*>(s->statsHost + 8);
-    s->lastStats.maxUnion      = s->statsHost[12];
-    if (c.skinOn && c.reuse) s->skin.keptClusters += s->statsHost[18], s->skin.frozenClusters += s->statsHost[19];
-    s->nsPolicy.observe(s->statsHost, (uint32_t)(s->last - s->first));
+    const uint32_t* sh = s->statsHost;
+    if (c.skinOn && c.reuse) s->skin.keptClusters += sh[kStatKept], s->skin.frozenClusters += sh[kStatFrozen];
+    s->nsPolicy.observe(sh, (uint32_t)(s->last - s->first));
+    s->lastStats = nbStats(sh, s->nsPolicy.lastBuild);
     if (c.reuse && s->skin.cleanSinceBuild <= 1 && !s->skin.forceBuild)
     {
         // the first clean step after a build, but most clusters would not survive another such drift: the skin
         // cannot outlast two steps; stop using it now rather than after a stale-heavy step (several ranks: the
         // counts of all ranks, exchanged with the step's decisions)
-        const double s13 = c.dist ? (double)s->skin.stepS13 : (double)s->statsHost[13];
+        const double s13 = c.dist ? (double)s->skin.stepS13 : (double)sh[kStatSkinThin];
         if (s13 > s->skin.staleLimit * (double)s->skin.stepClusters) skinTooThin(s->skin);
     }
-    s->lastStats.build         = s->nsPolicy.lastBuild;
-    if (s->statsHost[0] & 1u)
+    if (sh[kStatFlags] & kFlagError)
     {
-        fprintf(stderr, "sx_sim_step: neighbor search capacity exceeded (flags 0x%x: 2 walk capacity -- 0x40 traversal "
-                        "queue, 0x20 candidate leaves, 0x10 search regions --, 4 candidate space, 8 union); cluster %d: %u "
-                        "candidate leaves, %u search regions\n",
-                s->statsHost[0], (int)s->statsHost[14] - 1, s->statsHost[15], s->statsHost[16]);
+        fprintf(stderr, "sx_sim_step: neighbor search capacity exceeded (flags 0x%x: %x walk capacity -- 0x%x traversal "
+                        "queue, 0x%x candidate leaves, 0x%x search regions --, %x candidate space, %x union); cluster "
+                        "%d: %u candidate leaves, %u search regions\n",
+                sh[kStatFlags], kFlagWalk, kFlagQueue, kFlagLeaves, kFlagRegions, kFlagCandSpace, kFlagUnion,
+                (int)sh[kStatOverCluster] - 1, sh[kStatOverLeaves], sh[kStatOverRegions]);
         return SX_ERR_TRAVERSAL;
     }
     if (s->p.g != 0.0)
@@ -999,12 +960,10 @@ extern "C"
         (void)hipEventCreateWithFlags(&s->evStats, hipEventDisableTiming);
         {
             // the highest priority: its few workgroups (one per directly stale cluster) are dispatched ahead of the
-            // rebuild's persistent grid instead of sharing the CUs with it (SX_SKIN_AUX_PRIO=0: default priority)
+            // rebuild's persistent grid instead of sharing the CUs with it
             int least = 0, greatest = 0;
             (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-            const char* ap = getenv("SX_SKIN_AUX_PRIO");
-            const int   pr = ap && atoi(ap) == 0 ? least : greatest;
-            if (hipStreamCreateWithPriority(&s->auxStream, hipStreamNonBlocking, pr) != hipSuccess) s->auxStream = nullptr;
+            if (hipStreamCreateWithPriority(&s->auxStream, hipStreamNonBlocking, greatest) != hipSuccess) s->auxStream = nullptr;
         }
         (void)hipEventCreateWithFlags(&s->evAuxIn, hipEventDisableTiming);
         (void)hipEventCreateWithFlags(&s->evAuxOut, hipEventDisableTiming);
@@ -1083,6 +1042,14 @@ extern "C"
         s->skin.built    = factor;
         s->skin.maxReuse = maxReuse;
         s->skin.valid    = false;
+        return SX_OK;
+    }
+
+    //! test switch of the frozen kernel's staging (SkinState::frozenStage): entries staged, 0: the default
+    int sx_sim_set_skin_frozen_stage_internal(sx_sim* s, uint32_t entries)
+    {
+        if (!s || entries > (uint32_t)kSkinFrozenCap) return SX_ERR_ARG;
+        s->skin.frozenStage = entries;
         return SX_OK;
     }
 

@@ -97,6 +97,9 @@ struct SkinState
     bool     forceBuild{false};
     int      sinceBuild{0};
     uint32_t ngmaxS{0};         // skin-list capacity per target
+    // exact-union entries the frozen kernel stages in LDS; 0: kSkinFrozenCap.  Tests set a smaller staging, so that
+    // small unions take the path of oversized ones (sx_sim_set_skin_frozen_stage_internal)
+    uint32_t frozenStage{0};
     // a skin that does not outlast its build by two steps (fast flows: every cluster stale at once) costs more than it
     // saves: the next backoff steps search without it, backoffLen doubling with every such failure (up to 32)
     int      backoff{0}, backoffLen{4};
@@ -108,7 +111,7 @@ struct SkinState
     // the exact search on the drifted tree's boxes could outgrow its capacities)
     uint64_t resyncs{0};
     uint32_t lastStale{0}, lastExact{0};
-    // this step's clusters and stats[13] count (over all ranks with several; the "outlast two steps" test)
+    // this step's clusters and kStatSkinThin count (over all ranks with several; the "outlast two steps" test)
     uint64_t stepClusters{0}, stepS13{0};
     // this step: the filter computed XMass of every cluster but the exact-search ones (exactList[1 ..], lastExact)
     bool      xmFused{false};
@@ -137,7 +140,7 @@ struct SkinBuffers
     // skinReserveSearch (skinSearch)
     float *   rel{nullptr}, *hb{nullptr}, *acc{nullptr};
     uint32_t *sloc{nullptr}, *scnt{nullptr}, *ucountS{nullptr}, *l1{nullptr}, *l2{nullptr}, *l3{nullptr};
-    uint8_t*  dec{nullptr}; // a reuse step's decision per cluster (skinDecide)
+    uint8_t*  dec{nullptr}; // a reuse step's decision per cluster (sx::skinDecide)
     uint32_t* host{nullptr}; // pinned: the list counts read back
     uint8_t * streak{nullptr}, *same{nullptr};
     uint32_t* hitmask{nullptr};

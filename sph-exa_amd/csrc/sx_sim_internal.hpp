@@ -171,7 +171,7 @@ bool skinUsable(const sx_sim* s);
 void skinTooThin(SkinState& K);
 bool skinParticleBuffers(sx_sim* s, PosArgs& q, hipStream_t st);
 int  skinSearch(sx_sim* s, const NsArgs& na, bool reuse, hipStream_t st, float* xmOut, RecT* rtXm, SkinCounts& out);
-void skinDecide(SkinState& K, bool reuse, const SkinCounts& c, uint64_t staleAll, uint64_t clustersAll);
+void skinBookkeeping(SkinState& K, bool reuse, const SkinCounts& c, uint64_t staleAll, uint64_t clustersAll);
 int  skinHaloRefresh(sx_sim* s, hipStream_t st);
 //! a build with several ranks: the drift bounds of coverListKernel zeroed, the locals' positions kept (x0, y0, z0)
 int  skinBuildSnapshot(sx_sim* s, hipStream_t st);

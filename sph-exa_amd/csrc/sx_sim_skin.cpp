@@ -244,7 +244,7 @@ int skinSearch(sx_sim* s, const NsArgs& na, bool reuse, hipStream_t st, float* x
     if (!reuse) K.built = K.cur; // (also with no local cluster: every rank's skin state stays the same)
     if (!ncl) return SX_OK;
     if (!reuse) K.ngmaxS = skinCapacity(s->p.ngmax, K.built);
-    const bool twoSets = na.ucap / 4 >= (uint32_t)kSkinCap && !getenv("SX_SKIN_ONESET");
+    const bool twoSets = na.ucap / 4 >= (uint32_t)kSkinCap;
     if (!skinReserveSearch(s, na, ncl, twoSets)) return SX_ERR_NOMEM;
     const SkinBuffers& B = s->skinBuf;
     uint32_t *const l1 = B.l1, *const l2 = B.l2, *const l3 = B.l3, *const hl = B.host;
@@ -273,7 +273,7 @@ int skinSearch(sx_sim* s, const NsArgs& na, bool reuse, hipStream_t st, float* x
     fa.hitMask   = hmask;
     fa.same      = same;
     fa.nlocB = nlocB, fa.ucountB = B.ucountB, fa.hitMaskB = B.hitmaskB, fa.uoffB = na.ucap / 4;
-    fa.frz       = getenv("SX_SKIN_NOFREEZE") ? nullptr : frz; // (A/B: every reuse step walks its skin lists)
+    fa.frz       = frz;
     fa.keepLists = reuse && K.listsKept && K.keptNloc == na.nloc && K.keptUni == na.uni && K.keptMask == hmask &&
                    K.keptSame == same && K.keptFrz == frz && K.keptNlocB == nlocB;
     K.listsKept  = false; // until this search completes
@@ -309,9 +309,7 @@ int skinSearch(sx_sim* s, const NsArgs& na, bool reuse, hipStream_t st, float* x
         // decide first (every cluster: stale, frozen or walk), then the frozen clusters' XMass over their exact lists
         // and the walk of the others; a consumer's workgroup leaves at once when its cluster is not marked for it
         fa.dec = B.dec;
-        // (SX_SKIN_FROZEN_STAGE: a smaller staging, so that small test unions take the path of oversized ones)
-        const char* fs = getenv("SX_SKIN_FROZEN_STAGE");
-        fa.frozenStage = fs ? (uint32_t)std::max(0, atoi(fs)) : (uint32_t)kSkinFrozenCap;
+        fa.frozenStage = K.frozenStage ? K.frozenStage : (uint32_t)kSkinFrozenCap;
         SIM_HIP(skinDecide(fa, ncl, st));
         SIM_HIP(skinFrozen(fa, ncl, st));
     }
@@ -341,7 +339,7 @@ int skinSearch(sx_sim* s, const NsArgs& na, bool reuse, hipStream_t st, float* x
     // the directly stale clusters' exact search does not depend on the rebuild of the others (disjoint clusters: their
     // lists, unions, h, nc and records; only the statistics words are shared, reduced again below): with both, it runs
     // on the auxiliary stream with its own search scratch while the rebuild and its filter run here
-    const bool early = n1 && nd && reuse && s->auxStream && s->evAuxIn && s->evAuxOut && !getenv("SX_SKIN_SERIAL_EXACT");
+    const bool early = n1 && nd && reuse && s->auxStream && s->evAuxIn && s->evAuxOut;
     if (early)
     {
         NsArgs xd   = x;
@@ -350,14 +348,10 @@ int skinSearch(sx_sim* s, const NsArgs& na, bool reuse, hipStream_t st, float* x
         xd.hSave    = s->mem.get<float>("skin.aux.over", ncl + 1);
         xd.hitMasks = s->mem.get<uint64_t>("skin.aux.masks", searchScratchBytes() / sizeof(uint64_t));
         // one workgroup per cluster here, the rest of the resident grid for the rebuild: a persistent rebuild grid
-        // holding every slot would leave this search waiting for it (SX_SKIN_AUX_SHARE=0: both take the whole grid)
-        const char* sh = getenv("SX_SKIN_AUX_SHARE");
-        if (!sh || atoi(sh) != 0)
-        {
-            const unsigned G = searchGrid();
-            xd.maxGrid       = std::min(nd, G / 2);
-            b.maxGrid        = G - xd.maxGrid;
-        }
+        // holding every slot would leave this search waiting for it
+        const unsigned G = searchGrid();
+        xd.maxGrid       = std::min(nd, G / 2);
+        b.maxGrid        = G - xd.maxGrid;
         if (!xd.work || !xd.hSave || !xd.hitMasks) return SX_ERR_NOMEM;
         SIM_HIP(hipEventRecord(s->evAuxIn, st));
         SIM_HIP(hipStreamWaitEvent(s->auxStream, s->evAuxIn, 0));
@@ -409,11 +403,11 @@ int skinSearch(sx_sim* s, const NsArgs& na, bool reuse, hipStream_t st, float* x
             {
                 // on a reuse step the walk takes the drifted tree's refreshed boxes, which overlap: should the exact
                 // search outgrow its capacities there, the step's search is redone from a full sync
-                SIM_HIP(hipMemcpyAsync(hl, na.stats, 4, hipMemcpyDeviceToHost, st));
+                SIM_HIP(hipMemcpyAsync(hl, na.stats + kStatFlags, 4, hipMemcpyDeviceToHost, st));
                 SIM_HIP(hipStreamSynchronize(st));
-                if (hl[0] & 1u)
+                if (hl[0] & kFlagError)
                 {
-                    SIM_HIP(hipMemsetAsync(na.stats, 0, 4, st));
+                    SIM_HIP(hipMemsetAsync(na.stats + kStatFlags, 0, 4, st));
                     return kSkinResync;
                 }
             }
@@ -425,21 +419,13 @@ int skinSearch(sx_sim* s, const NsArgs& na, bool reuse, hipStream_t st, float* x
     K.keptNlocB = nlocB;
     // the pair kernels read each cluster's current set
     K.lb = twoSets ? ListsB{same, nlocB, B.ucountB, na.ucap / 4} : ListsB{};
-    if (getenv("SX_SKIN_DEBUG"))
-    {
-        uint32_t f = 0;
-        SIM_HIP(hipMemcpyAsync(&f, na.stats, 4, hipMemcpyDeviceToHost, st));
-        SIM_HIP(hipStreamSynchronize(st));
-        fprintf(stderr, "skin: reuse %d s %.3f clusters %u stale %u exact %u (direct %u) flags 0x%x mode %d\n",
-                (int)reuse, K.built, ncl, n1 + nd, n2, nd, f, s->nsPolicy.mode);
-    }
     return SX_OK;
 }
 
 /*! the skin's bookkeeping after a step's search: statistics of this rank, and the build decisions from the stale share
  *  of all ranks (staleAll of clustersAll: with several ranks the sums over every rank, so that every rank takes the
  *  same decisions and the next step is a full sync + build on all of them or on none) */
-void skinDecide(SkinState& K, bool reuse, const SkinCounts& c, uint64_t staleAll, uint64_t clustersAll)
+void skinBookkeeping(SkinState& K, bool reuse, const SkinCounts& c, uint64_t staleAll, uint64_t clustersAll)
 {
     K.lastStale = c.stale, K.lastExact = c.exact;
     K.staleClusters += c.stale, K.exactClusters += c.exact;

@@ -156,13 +156,13 @@ __global__ __launch_bounds__(1024) void reduceClusterStatsKernel(const uint4* cl
         for (int k = 1; k < (int)(blockDim.x >> 6); ++k)
             mx = max(mx, s_max[0][k]), mu = max(mu, s_max[1][k]), kp += s_max[2][k], fz += s_max[3][k], st += s_sum[0][k],
             te += s_sum[1][k], un += s_sum[2][k];
-        stats[2]                                          = mx;
-        stats[18]                                         = kp;
-        stats[19]                                         = fz;
-        stats[12]                                         = mu;
-        *reinterpret_cast<unsigned long long*>(stats + 4) = st;
-        *reinterpret_cast<unsigned long long*>(stats + 6) = te;
-        *reinterpret_cast<unsigned long long*>(stats + 8) = un;
+        stats[kStatMaxCount]                                        = mx;
+        stats[kStatKept]                                            = kp;
+        stats[kStatFrozen]                                          = fz;
+        stats[kStatMaxUnion]                                        = mu;
+        *reinterpret_cast<unsigned long long*>(stats + kStatStored) = st;
+        *reinterpret_cast<unsigned long long*>(stats + kStatTested) = te;
+        *reinterpret_cast<unsigned long long*>(stats + kStatUnion)  = un;
     }
 }
 
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(kB) void skinDecideKernel(SkinArgs a)
     // a target's skin holds every current neighbor while 2h + d + A <= R (1 - eps); a build that overflowed a capacity
     // (skin list beyond ngmaxS, union beyond the slot) never serves, nor a union beyond the LDS capacity
     const bool bad = valid && (scount > a.ngmaxS || !(2.0f * hi + di + A <= Ri * (1.0f - kEps)));
-    // one more drift like the one since the build would make the cluster stale (stats[13]: the host stops using
+    // one more drift like the one since the build would make the cluster stale (kStatSkinThin: the host stops using
     // skins that cannot outlast two steps, sx_sim.cpp)
     const bool thin = valid && 2.0f * hi + 2.0f * (di + A) > Ri * (1.0f - kEps);
     // ---- 1b. frozen: since the last pass that walked this cluster (its reference: per target the smallest distance
@@ -319,7 +319,7 @@ __global__ __launch_bounds__(kB) void skinDecideKernel(SkinArgs a)
     if (valid) a.rel[i] = di;
     if (threadIdx.x == 0)
     {
-        if (v & 2u) atomicAdd(&a.stats[13], 1u);
+        if (v & 2u) atomicAdd(&a.stats[kStatSkinThin], 1u);
         a.acc[c] = A;
         a.dec[c] = (mayFreeze && !(v & 4u)) ? kSkinFrozen : kSkinWalk;
     }
@@ -963,7 +963,7 @@ __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(4))) void sk
     const float kp = waveMin(valid ? frzK + 2.0f * hi : INFINITY), km = waveMin(valid ? frzK - 2.0f * hi : INFINITY);
     if (lane == 0)
     {
-        if (nfail) atomicAdd(&a.stats[1], nfail);
+        if (nfail) atomicAdd(&a.stats[kStatFailed], nfail);
         // (LDS: 40960 B is exactly a quarter of the CU's, four workgroups; no byte more)
         s_cst[wave]  = make_uint4(maxCnt, (uint32_t)nst, (uint32_t)walked, __float_as_uint(kp));
         s_wsum[wave] = __float_as_uint(km);

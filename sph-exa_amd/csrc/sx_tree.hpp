@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/sphexa_hip.h"
 #include "sx_device.hpp"
 
 /*! in a host function with a std::string err that returns a status: a failed HIP call leaves "<who>: <call>: <HIP's
@@ -171,14 +172,59 @@ struct NbLists
     }
 };
 
-constexpr int kStatsWords = 28; //!< [0] error flags, [1] failures, [2] max count, [3] scratch, u64 at [4] stored
-                                //!< neighbors, [6] candidates tested, [8] union entries, [10] clusters the
-                                //!< compact build handed to the large one, [11] the compact build ran first,
-                                //!< [12] the largest cluster union (local lists), [13] clusters whose skin
-                                //!< the next step's drift would exhaust (sx_skin.hip), [14] 1 + a cluster
-                                //!< over the large build's capacities, [15] its candidate leaves (capped),
-                                //!< [16] its search regions, [17] clusters the large build handed to its
-                                //!< smaller-region pass, [18..27] spare
+/*! the words of a search's statistics (NsArgs::stats on the device, the callers' statsHost): written by the search
+ *  (sx_neighbors.hip), the skin filter and the reduction of the per-cluster statistics (sx_skin.hip), zeroed by the
+ *  caller before each search */
+enum StatWord : int
+{
+    kStatFlags        = 0,  //!< error bits (StatFlag)
+    kStatFailed       = 1,  //!< targets whose h iteration failed
+    kStatMaxCount     = 2,  //!< the largest neighbor count
+    kStatHaloShort    = 3,  //!< host only, several ranks: the ranks' summed "halo margin too small" flags, last attempt
+    kStatStored       = 4,  //!< u64: stored neighbors
+    kStatTested       = 6,  //!< u64: candidates tested
+    kStatUnion        = 8,  //!< u64: union entries
+    kStatToLarge      = 10, //!< clusters the compact build handed to the large one
+    kStatCompactFirst = 11, //!< the compact build ran first
+    kStatMaxUnion     = 12, //!< the largest cluster union (local lists)
+    kStatSkinThin     = 13, //!< clusters whose skin the next step's drift would exhaust (sx_skin.hip)
+    kStatOverCluster  = 14, //!< 1 + a cluster over the large build's capacities
+    kStatOverLeaves   = 15, //!< its candidate leaves (capped)
+    kStatOverRegions  = 16, //!< its search regions
+    kStatToSmallRegs  = 17, //!< clusters the large build handed to its smaller-region pass
+    kStatKept         = 18, //!< a reuse step's clusters served from their skin lists
+    kStatFrozen       = 19, //!< of those, the frozen ones (the lean kernel)
+    kStatsWords       = 28  //!< [20..27] spare
+};
+//! the bits of stats[kStatFlags]
+enum StatFlag : uint32_t
+{
+    kFlagError     = 1u,    //!< the search failed (set with every other bit)
+    kFlagWalk      = 2u,    //!< a capacity of the tree walk, which one in kFlagRegions / kFlagLeaves / kFlagQueue
+    kFlagCandSpace = 4u,    //!< candidate particles beyond the u16 space
+    kFlagUnion     = 8u,    //!< a cluster's union beyond its capacity
+    kFlagRegions   = 0x10u, //!< search regions dropped: the candidates may be short
+    kFlagLeaves    = 0x20u, //!< the candidate-leaf list full
+    kFlagQueue     = 0x40u  //!< the traversal queue full
+};
+//! a u64 statistic (kStatStored, kStatTested, kStatUnion) of a host copy
+inline uint64_t stat64(const uint32_t* statsHost, StatWord w)
+{
+    return *reinterpret_cast<const uint64_t*>(statsHost + w);
+}
+//! the public statistics of a finished search; build: NsPolicy::lastBuild after observe()
+inline sx_nbstats nbStats(const uint32_t* statsHost, uint32_t build)
+{
+    sx_nbstats o{};
+    o.numFailed     = statsHost[kStatFailed];
+    o.maxNeighbors  = statsHost[kStatMaxCount];
+    o.sumNeighbors  = stat64(statsHost, kStatStored);
+    o.sumCandidates = stat64(statsHost, kStatTested);
+    o.sumUnion      = stat64(statsHost, kStatUnion);
+    o.build         = build;
+    o.maxUnion      = statsHost[kStatMaxUnion];
+    return o;
+}
 
 //! which search build runs: the compact one (four workgroups per CU) with a device-side fallback to the large one,
 //! or the large one directly.  Host state of one caller (context or sim), fed with the stats of each finished
@@ -194,11 +240,11 @@ struct NsPolicy
 
     void observe(const uint32_t* statsHost, uint32_t targets)
     {
-        lastBuild = statsHost[10] ? 2u : (statsHost[11] ? 0u : 1u);
+        lastBuild = statsHost[kStatToLarge] ? 2u : (statsHost[kStatCompactFirst] ? 0u : 1u);
         // redoing a few clusters costs little; when more than an eighth of them overflow, go large directly
         const uint64_t clusters = (targets + kCluster - 1) / kCluster;
-        if (8ull * statsHost[10] > clusters) largeRuns = 64;
-        prevStored  = *reinterpret_cast<const uint64_t*>(statsHost + 4);
+        if (8ull * statsHost[kStatToLarge] > clusters) largeRuns = 64;
+        prevStored  = stat64(statsHost, kStatStored);
         prevTargets = targets;
     }
     //! the large build directly only after a search in which many clusters overflowed the compact one (with the
@@ -248,7 +294,7 @@ struct NsArgs
     const float*    powTab; // glibc powf(1 + 1023*ng0/nc, 0.1f) by nc (updateH)
     int             prefilter; // 1: packed f32 distance test in the cluster frame, exact double test only for the
                                // ambiguous chunks; 0: the exact double test for every candidate
-    uint32_t*       stats;     // kStatsWords words, see above
+    uint32_t*       stats;     // kStatsWords words (StatWord)
     const uint8_t*  active;    // nullable: targets with active[i] == 0 are skipped (no h iteration, h and nc kept)
     uint4*          clStats;   // per cluster {max count, stored, tested, union}: reduced into stats by one small
                                // kernel after the search (per-wave atomics on the stats words serialised: 10 ms of a

@@ -725,6 +725,7 @@ def lib():
                                         C.c_float, vp, C.POINTER(C.c_double)]),
         "sx_set_direct_splits": (C.c_int, [vp, u32]),
         "sx_ctx_direct_targets_per_lane_internal": (C.c_int, [vp, u32]),
+        "sx_sim_set_skin_frozen_stage_internal": (C.c_int, [vp, u32]),
         "sx_domain_halo_layout": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, vp, vp]),
         "sx_turb_default_settings": (C.c_int, [C.POINTER(SxTurbSettings)]),
         "sx_turb_create": (C.c_int, [C.POINTER(vp), C.POINTER(SxTurbSettings)]),

@@ -33,9 +33,10 @@ pytestmark = pytest.mark.gpu
 COUNTS = ("reuse_steps", "stale_clusters", "exact_clusters", "kept_clusters", "frozen_clusters")
 
 
-def _steps_vs_fresh(ctx, st, obox, steps, factor, label):
+def _steps_vs_fresh(ctx, st, obox, steps, factor, label, frozen_stage=0):
     """runs `steps` steps with the skin, each against a fresh search of the same state; returns per step the growth of
-    the COUNTS of skin_stats, and the number of clusters"""
+    the COUNTS of skin_stats, and the number of clusters.  frozen_stage: the union entries the frozen kernel stages
+    (sx_sim_set_skin_frozen_stage_internal; 0: the default)"""
     box = gutil.box_to_sx(obox)
     a = sx.Sim(ctx, st.n, box)
     a.set_skin(factor, 24)
@@ -44,6 +45,7 @@ def _steps_vs_fresh(ctx, st, obox, steps, factor, label):
     a.set_state(st.arrays, st.minDt, st.minDt_m1)
     per_step = []
     try:
+        assert a.L.sx_sim_set_skin_frozen_stage_internal(a.h, frozen_stage) == sx.SX_OK
         last = a.skin_stats()
         for s in range(steps):
             g = a.get(STATE)
@@ -65,8 +67,10 @@ def _steps_vs_fresh(ctx, st, obox, steps, factor, label):
         print(label, factor, (st.n + 255) // 256, "clusters", per_step)
         return per_step, (st.n + 255) // 256
     finally:
+        restored = a.L.sx_sim_set_skin_frozen_stage_internal(a.h, 0)
         a.close()
         b.close()
+        assert restored == sx.SX_OK
 
 
 def _walked(p, ncl):
@@ -126,12 +130,12 @@ def test_split_u16_lists(ctx):
 
 
 @pytest.mark.parametrize("pack_max", [None, 256])
-def test_split_union_beyond_the_staging(ctx, monkeypatch, pack_max):
-    monkeypatch.setenv("SX_SKIN_FROZEN_STAGE", "512")
+def test_split_union_beyond_the_staging(ctx, pack_max):
     st, obox = po.sedov_state(21)
     ctx.set_pack12_max(pack_max)
     try:
-        per, ncl = _steps_vs_fresh(ctx, st, obox, 4, 0.05, f"sedov 21, staging 512, packMax {pack_max}")
+        per, ncl = _steps_vs_fresh(ctx, st, obox, 4, 0.05, f"sedov 21, staging 512, packMax {pack_max}",
+                                   frozen_stage=512)
     finally:
         ctx.set_pack12_max(None)
     assert sum(p["frozen_clusters"] for p in per) > 0, per

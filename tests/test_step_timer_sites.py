@@ -3,7 +3,7 @@
 The stage and kernel times used to be event arrays indexed by a running counter and by magic numbers: one record too
 many or too few moved every later time under the wrong name, and nothing failed.  So sx_sim*.cpp and sx_bdt.cpp hold
 no such event array any more; they mark `Stage::X` / `Kernel::X` on the timer, and only the timer turns events into
-times.  Two timings of their own remain in those files: the search A/B hook (searchReps) and the turbulence stirring.
+times.  One timing of its own remains in those files: the turbulence stirring.
 """
 import glob
 import os
@@ -24,12 +24,6 @@ def driver_sources():
         with open(path) as f:
             out[os.path.basename(path)] = f.read()
     return out
-
-
-def function_span(text, signature):
-    """[start, end) of the function at namespace level whose definition starts with `signature`"""
-    start = text.index("\n" + signature) + 1
-    return start, text.index("\n}\n", start) + 3
 
 
 def test_no_indexed_stage_or_kernel_events():
@@ -57,12 +51,10 @@ def test_elapsed_time_is_read_by_the_timer_alone():
         timer = f.read()
     assert "hipEventElapsedTime" in timer
     for name, text in driver_sources().items():
-        reps = function_span(text, "int searchReps(") if name == "sx_sim.cpp" else (0, 0)
         for m in re.finditer(r"hipEventElapsedTime", text):
             line_start = text.rfind("\n", 0, m.start()) + 1
             line = text[line_start:text.index("\n", m.start())]
-            in_reps = reps[0] <= m.start() < reps[1]
-            assert in_reps or "turb->" in line, "%s:%d: %s" % (name, text.count("\n", 0, m.start()) + 1, line.strip())
+            assert "turb->" in line, "%s:%d: %s" % (name, text.count("\n", 0, m.start()) + 1, line.strip())
     # every step driver ends in the one collect()
     sources = driver_sources()
     for name in ("sx_sim.cpp", "sx_sim_nbody.cpp", "sx_bdt.cpp"):
