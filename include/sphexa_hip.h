@@ -743,6 +743,99 @@ int sx_fof_stats(sx_ctx* ctx, uint64_t out[4]);
 int sx_set_fof_timing(sx_ctx* ctx, int on);
 int sx_fof_times(sx_ctx* ctx, double out[4]);
 
+/* ---- group properties: density cut, shape, dispersion, spin, self-energy (sph-exa_amd/csrc/sx_halo.hpp) ----------
+ *
+ * Arithmetic. IEEE double, every operation rounded on its own (the file is built with -ffp-contract=off), brackets as
+ *             written, unless a line says float.  Float columns are widened first; that conversion is exact.
+ * Selection.  A particle of [first, last) is selected iff rhoMin <= 0 or rho >= rhoMin, rho by the rule of SX_PROF_RHO:
+ *             the float (kx * m) / xm, or the float column rho when std != 0, then widened.  A NaN rho is not selected.
+ *             Unselected particles link nothing and belong to no group: their label is UINT64_MAX and they count in
+ *             neither entry of numGroups.  (A selected particle with a NaN x counts as unselected.)
+ * Groups, labels, catalogue order, mass, com, vel.  Exactly sx_fof's, over the selected particles; with rhoMin <= 0
+ *             the same bits as sx_fof_compute returns for the same input.
+ * Moments (SX_HALO_MOMENTS), per catalogue group with X = com, V = vel, M = mass as returned:
+ *             d_a = minimage(x_a - X_a) by the rule of sx_fof (L_a added or subtracted once where |d_a| > L_a / 2),
+ *             w_a = (double)v_a - V_a, and with the components ab in the order xx, xy, xz, yy, yz, zz
+ *               sigma[ab] = (sum (m * w_a) * w_b) / M        shape[ab] = (sum (m * d_a) * d_b) / M
+ *               angmom    = sum m * ((d_y * w_z) - (d_z * w_y)),  m * ((d_z * w_x) - (d_x * w_z)),
+ *                               m * ((d_x * w_y) - (d_y * w_x))
+ *               rmax      = sqrt(max ((d_x * d_x + d_y * d_y) + d_z * d_z)), the exact maximum, one sqrt.
+ *             The caveat of com applies: a group must span less than half a periodic box.
+ * Thermal (SX_HALO_THERMAL).  eint = sum m * (cv * temp), cv as the profile section defines it.
+ * Potential (SX_HALO_POTENTIAL).  epot = -(G * sum over the unordered member pairs i < j of m_i m_j r^2 / r_eff^3), r^2
+ *             from the minimum-image differences (formed in double), r_eff^2 = max(r^2, (h_i + h_j)^2) with h_i + h_j
+ *             and its square formed in float: the P2P of sx_gravity_direct, so a group uploaded alone has epot == egrav of that call up
+ *             to rounding.  A pair with r^2 = 0 contributes 0.  A group with more than maxPairMembers members gets
+ *             epot = NaN.
+ *             Accuracy contract: |epot - W| <= 2^-15 |W| with W the sum in exact arithmetic (every term has the same
+ *             sign).  The kernel rounds the double differences to float, evaluates a term in float with the hardware's
+ *             reciprocal square root (1 ulp), adds at most 64 terms in one float accumulator and goes on in double:
+ *             (23 + 63) 2^-24 = 2^-17.6 at worst, so the contract has a factor 5 of margin.  It assumes
+ *             that m_j / r_eff and the squares of the differences stay inside the float range.
+ * Order.      Moments and eint: the members in ascending id (or index), 256 partial sums, partial k taking members
+ *             k, k + 256, ..., then a pairwise tree: the catalogue's rule.  epot: the members of a group in ascending id
+ *             in tiles of 256; work item k = b (b + 1) / 2 + a of the group is the pair of tiles a <= b (the diagonal
+ *             item takes j > i only); inside an item target lane t adds its sources s ascending into accumulator s % 4,
+ *             the lanes are added by a pairwise tree, and the group's items by 256 partial sums over k, k + 256, ... and
+ *             a pairwise tree.  All of it is a function of the member count alone; no floating-point atomic anywhere:
+ *             the same bits on every run and, with ids, under any permutation of the input.
+ * One rank.   As sx_sim_fof, sx_sim_halos refuses a communicator of more than one rank. */
+#define SX_HALO_MOMENTS 1u
+#define SX_HALO_THERMAL 2u
+#define SX_HALO_POTENTIAL 4u
+typedef struct sx_halo
+{
+    double   linking;        /* as in sx_fof */
+    uint32_t minMembers;     /* as in sx_fof */
+    uint32_t maxGroups;      /* as in sx_fof */
+    double   rhoMin;         /* the density cut; <= 0: none */
+    int32_t  std;            /* which density rule applies, as sx_profile_compute takes it */
+    float    G;              /* gravitational constant of epot */
+    uint32_t flags;          /* SX_HALO_* */
+    float    muiConst;       /* thermal only */
+    double   gamma;          /* thermal only */
+    uint32_t maxPairMembers; /* groups above it get epot = NaN; 0 means 2^20 */
+} sx_halo;
+/*! every pointer nullable (then not written); device pointers for sx_halo_compute, host pointers for sx_sim_halos.  An
+ *  array whose flag is clear is not written either. */
+typedef struct sx_halo_result
+{
+    uint64_t* label;      /* the seven of sx_fof_result */
+    uint64_t* groupLabel;
+    uint32_t* groupCount;
+    double*   groupMass;
+    double*   groupCom;
+    double*   groupVel;
+    uint64_t* numGroups;
+    double*   groupSigma;  /* [maxGroups][6]  SX_HALO_MOMENTS */
+    double*   groupShape;  /* [maxGroups][6]  SX_HALO_MOMENTS */
+    double*   groupAngmom; /* [maxGroups][3]  SX_HALO_MOMENTS */
+    double*   groupRmax;   /* [maxGroups]     SX_HALO_MOMENTS */
+    double*   groupEint;   /* [maxGroups]     SX_HALO_THERMAL */
+    double*   groupEpot;   /* [maxGroups]     SX_HALO_POTENTIAL */
+} sx_halo_result;
+/*! host only, needs no GPU: SX_OK, or SX_ERR_ARG with the reason in sx_last_error(NULL) (per thread).  Refused: whatever
+ *  sx_fof_check refuses for (linking, minMembers, maxGroups), a rhoMin or G that is not finite, unknown flags, and with
+ *  SX_HALO_THERMAL a gamma <= 1 or a muiConst <= 0 (or either not finite). */
+int sx_halo_check(const sx_halo* halo, const sx_box* box);
+/*! the groups of the particles [first, last) of f and their properties into the device arrays of deviceOut.  Columns:
+ *  sx_fof_compute's; kx, m, xm (or rho with std) for rhoMin > 0; temp and m for the thermal energy; h and m for the
+ *  potential.  Stages: sx_fof_compute's (the cut is a pass behind its gather), one workgroup per catalogue group for the
+ *  moments, then for the potential a scan of the groups' work items, one workgroup of 256 lanes per pair of member tiles
+ *  (the sources staged in 8 KB of LDS) and one workgroup per group for its items.  The search's scratch is the context's
+ *  fof.* (sx_fof_stats then reports this call's search); the rest lives under halo.*: 144 bytes per catalogue entry and
+ *  8 bytes per work item.  SX_ERR_ARG: whatever sx_halo_check or sx_fof_compute refuses and a flag or cut whose columns
+ *  are NULL, each with its reason.  Synchronises. */
+int sx_halo_compute(sx_ctx* ctx, const sx_fields* f, const sx_box* box, uint32_t first, uint32_t last,
+                    const uint64_t* id, const sx_halo* halo, const sx_halo_result* deviceOut);
+/*! the context's last call: {pair terms evaluated (= sum c (c - 1) / 2 over the groups that got an epot), pair work
+ *  items, groups with an epot, groups over maxPairMembers}; SX_ERR_ARG before the first */
+int sx_halo_stats(sx_ctx* ctx, uint64_t out[4]);
+/*! measurement: with on != 0 the following calls time their stages with HIP events; sx_halo_times: {group search,
+ *  moments, pair kernel (with the scan and the host's read of the item count), combination and copies} in ms */
+int sx_set_halo_timing(sx_ctx* ctx, int on);
+int sx_halo_times(sx_ctx* ctx, double out[4]);
+
 /* ---- two-point statistics: pair counts and velocity structure functions (sph-exa_amd/csrc/sx_twopoint.hpp) -------
  *
  * Arithmetic. Double precision, every operation rounded on its own (the file is built with -ffp-contract=off), brackets
@@ -1138,6 +1231,16 @@ int    sx_sim_profile_stats(sx_sim* sim, uint64_t out[4]);
  *  sim's last call. */
 int    sx_sim_fof(sx_sim* sim, const sx_fof* fof, const sx_fof_result* hostOut);
 int    sx_sim_fof_stats(sx_sim* sim, uint64_t out[4]);
+/*! sx_halo_compute of the locals of the current state with the sim's id column, into the host arrays of hostOut (the
+ *  properties through a pinned buffer); synchronises.  G, muiConst, gamma and std are taken from the sim's parameters
+ *  (those fields of `halo` are ignored); rhoMin, flags and the rest from `halo`.  Every propagator: the gravity-only
+ *  layout serves with rhoMin <= 0 and without the thermal energy, and is refused with a reason otherwise.  Nothing in
+ *  sx_sim_step calls it and it changes no field and no scalar.  The buffers live in the sim's arena under the tags fof.*
+ *  (shared with sx_sim_fof) and halo.*, are allocated by the first call and counted by sx_sim_memory from then on.  A
+ *  communicator of more than one rank is refused on every rank before any collective.  sx_sim_halos_stats:
+ *  sx_halo_stats of the sim's last call. */
+int    sx_sim_halos(sx_sim* sim, const sx_halo* halo, const sx_halo_result* hostOut);
+int    sx_sim_halos_stats(sx_sim* sim, uint64_t out[4]);
 /*! sx_twopoint_compute of the locals of the current state with the sim's id column, into the host arrays of hostOut
  *  through a pinned buffer; synchronises.  Reads x, y, z, vx, vy, vz, m and id only: every propagator, the gravity-only
  *  one included, under ve-bdt between any two substeps; nothing in sx_sim_step calls it and it changes no field and no

@@ -23,6 +23,7 @@
 #include "sx_observables.hpp"
 #include "sx_profile.hpp"
 #include "sx_fof.hpp"
+#include "sx_halo.hpp"
 #include "sx_twopoint.hpp"
 #include "sx_spectrum.hpp"
 #include "sx_tree.hpp"
@@ -132,6 +133,7 @@ struct sx_ctx
     sx::spectrum::SpecBuffers specBuf;   // scratch, per-n tables, meshes and figures of the spectra
     sx::profile::ProfBuffers profBuf;    // accumulators, uploaded edges and tables and figures of the profiles
     sx::fof::FofBuffers fofBuf;          // grid, union-find and catalogue scratch and figures of the group finder
+    sx::halo::HaloBuffers haloBuf;       // results, work items and figures of the group properties (the search: fofBuf)
     sx::twopoint::TwoPointBuffers tpBuf; // grid, sorted columns and accumulators of the two-point statistics
     float2*     wh{nullptr};
     float2*     whd{nullptr};
@@ -228,6 +230,7 @@ extern "C"
     void          sx_ctx_set_error_internal(sx_ctx* c, const char* msg) { fail(c, SX_ERR_ARG, msg); }
     uint32_t      sx_ctx_pack12_max_internal(sx_ctx* c) { return c->packMax(); }
     sx::fof::FofBuffers* sx_ctx_fof_buffers_internal(sx_ctx* c) { return &c->fofBuf; }
+    sx::halo::HaloBuffers* sx_ctx_halo_buffers_internal(sx_ctx* c) { return &c->haloBuf; }
     sx::twopoint::TwoPointBuffers* sx_ctx_twopoint_buffers_internal(sx_ctx* c) { return &c->tpBuf; }
 
     int sx_set_pack12_max(sx_ctx* c, uint32_t maxUnion)
@@ -303,6 +306,7 @@ extern "C"
         sx::pairbin::release(c->specBuf.bin);
         sx::profile::release(c->profBuf);
         sx::fof::release(c->fofBuf);
+        sx::halo::release(c->haloBuf);
         sx::twopoint::release(c->tpBuf);
         c->arena.release();
         if (c->own) (void)hipStreamDestroy(c->own);
@@ -1733,6 +1737,47 @@ extern "C"
         if (!c || !out) return SX_ERR_ARG;
         for (int k = 0; k < 4; ++k)
             out[k] = c->fofBuf.clock.ms[k];
+        return SX_OK;
+    }
+
+    // ---- group properties (sx_halo.hpp) ---------------------------------------------------------------------------
+    int sx_halo_check(const sx_halo* p, const sx_box* box)
+    {
+        if (std::string why = sx::halo::checkSpec(p, box); !why.empty()) return fail(nullptr, SX_ERR_ARG, why);
+        return SX_OK;
+    }
+
+    int sx_halo_compute(sx_ctx* c, const sx_fields* f, const sx_box* box, uint32_t first, uint32_t last,
+                        const uint64_t* id, const sx_halo* p, const sx_halo_result* res)
+    {
+        if (!c) return SX_ERR_ARG;
+        if (std::string why = sx::halo::whyRefused(p, box, f, first, last, res); !why.empty()) return fail(c, SX_ERR_ARG, why);
+        std::string err;
+        const int   rc = sx::halo::compute(c->arena, c->fofBuf, c->haloBuf, *p, *f, *box, first, last, id, *res, false,
+                                           c->stream, err);
+        return rc == SX_OK ? SX_OK : fail(c, rc, err);
+    }
+
+    int sx_halo_stats(sx_ctx* c, uint64_t out[4])
+    {
+        if (!c || !out) return SX_ERR_ARG;
+        if (!c->haloBuf.done) return fail(c, SX_ERR_ARG, "sx_halo_stats: no group properties have been computed");
+        std::copy(c->haloBuf.stats, c->haloBuf.stats + 4, out);
+        return SX_OK;
+    }
+
+    int sx_set_halo_timing(sx_ctx* c, int on)
+    {
+        if (!c) return SX_ERR_ARG;
+        c->haloBuf.clock.on = on != 0;
+        return SX_OK;
+    }
+
+    int sx_halo_times(sx_ctx* c, double out[4])
+    {
+        if (!c || !out) return SX_ERR_ARG;
+        for (int k = 0; k < 4; ++k)
+            out[k] = c->haloBuf.clock.ms[k];
         return SX_OK;
     }
 

@@ -81,6 +81,19 @@ __global__ __launch_bounds__(kBlock) void gatherKernel(const double* __restrict_
     parent[s] = s, count[s] = 0, minId[s] = ~0ull, rankOf[s] = kNoGroup;
 }
 
+//! the density cut of the group properties: an unselected particle (a NaN density included) gets a NaN sorted x
+__global__ __launch_bounds__(kBlock) void maskKernel(const float* __restrict__ kx, const float* __restrict__ m,
+                                                     const float* __restrict__ xm, const float* __restrict__ rho,
+                                                     int std, double rhoMin, uint32_t first, uint32_t n,
+                                                     const uint32_t* __restrict__ order, double* __restrict__ xs)
+{
+    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n) return;
+    const size_t p = (size_t)first + order[s];
+    const float  r = std ? rho[p] : (kx[p] * m[p]) / xm[p];
+    if (!((double)r >= rhoMin)) xs[s] = __builtin_nan("");
+}
+
 //! a load that another compute unit's store reaches: the first-level cache is per compute unit and not coherent
 __device__ __forceinline__ uint32_t loadShared(const uint32_t* p)
 {
@@ -167,8 +180,10 @@ __global__ __launch_bounds__(kBlock) void linkKernel(LinkArgs a)
 
 /*! pointer jumping to the end: root[s] is the root above s (nothing stores to parent[] here).  The label is the minimum
  *  id per root, the member count an integer add: the same totals whatever the order. */
+template<bool Masked>
 __global__ __launch_bounds__(kBlock) void compressKernel(const uint32_t* __restrict__ parent, uint32_t n, uint32_t first,
                                                          const uint32_t* __restrict__ order,
+                                                         const double* __restrict__ xs,
                                                          const uint64_t* __restrict__ id, uint32_t* __restrict__ root,
                                                          unsigned long long* __restrict__ minId,
                                                          uint32_t* __restrict__ count, uint64_t* __restrict__ idKeys,
@@ -209,7 +224,7 @@ __global__ __launch_bounds__(kBlock) void compressKernel(const uint32_t* __restr
             atomicAdd(count + r0, 64u);
         }
     }
-    else if (in)
+    else if (in && !(Masked && xs[s] != xs[s])) // an unselected particle is its own root: no label, no count
     {
         atomicMin(minId + r, v);
         atomicAdd(count + r, 1u);
@@ -217,8 +232,10 @@ __global__ __launch_bounds__(kBlock) void compressKernel(const uint32_t* __restr
 }
 
 //! the labels in the order of the columns; the roots counted, those with minMembers members or more appended
+template<bool Masked>
 __global__ __launch_bounds__(kBlock) void labelKernel(const uint32_t* __restrict__ root, uint32_t n,
                                                       const uint32_t* __restrict__ order,
+                                                      const double* __restrict__ xs,
                                                       const unsigned long long* __restrict__ minId,
                                                       const uint32_t* __restrict__ count, uint32_t minMembers,
                                                       uint64_t* __restrict__ label, uint64_t* __restrict__ selLabel,
@@ -227,8 +244,8 @@ __global__ __launch_bounds__(kBlock) void labelKernel(const uint32_t* __restrict
     const uint32_t s      = blockIdx.x * kBlock + threadIdx.x;
     const bool     in     = s < n;
     const uint32_t r      = in ? root[s] : 0;
-    const bool     isRoot = in && r == s;
-    if (in) label[order[s]] = minId[r];
+    const bool     isRoot = in && r == s && !(Masked && xs[s] != xs[s]);
+    if (in) label[order[s]] = minId[r]; // of an unselected particle: still ~0
     const unsigned long long roots = __popcll(__ballot(isRoot));
     if ((threadIdx.x & 63) == 0 && roots) atomicAdd(counters + 2, roots);
     if (isRoot && count[s] >= minMembers)
@@ -344,13 +361,15 @@ constexpr const char* kWho = "sx_fof"; // in front of the messages of SX_TRY_HIP
 // ---- the launcher ------------------------------------------------------------------------------------------------
 
 int compute(Arena& arena, FofBuffers& b, const sx_fof& p, const sx_fields& f, const sx_box& box, uint32_t first,
-            uint32_t last, const uint64_t* id, const sx_fof_result& res, bool toHost, hipStream_t s, std::string& err)
+            uint32_t last, const uint64_t* id, const sx_fof_result& res, bool toHost, hipStream_t s, std::string& err,
+            const Extra* extra)
 {
     const uint32_t n = last - first;
     uint32_t       dims[3];
     chooseGrid(p, box, n, dims);
     const uint32_t minMembers = std::max(1u, p.minMembers);
-    const bool     wantReal   = res.groupMass || res.groupCom || res.groupVel;
+    const bool     masked     = extra && extra->rhoMin > 0.0;
+    const bool     wantReal   = res.groupMass || res.groupCom || res.groupVel || (extra && extra->members);
     const bool     wantCat    = wantReal || res.groupLabel || res.groupCount;
     const uint32_t cap        = wantCat ? std::min(p.maxGroups, std::max(n, 1u)) : 0;
     const auto     kind       = toHost ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
@@ -362,6 +381,7 @@ int compute(Arena& arena, FofBuffers& b, const sx_fof& p, const sx_fields& f, co
         err = "sx_fof: counter buffers";
         return SX_ERR_NOMEM;
     }
+    b.catGroups = 0, b.members = false;
     SX_TRY_HIP(kWho, b.clock.begin());
     SX_TRY_HIP(kWho, hipMemsetAsync(b.counters, 0, 4 * sizeof(uint64_t), s));
     if (n == 0)
@@ -409,15 +429,29 @@ int compute(Arena& arena, FofBuffers& b, const sx_fof& p, const sx_fields& f, co
         return rc;
     gatherKernel<<<blocks(n), kBlock, 0, s>>>(f.x, f.y, f.z, first, n, ix.order, b.xs, b.ys, b.zs, b.parent, b.count,
                                               minId, b.rankOf);
+    if (masked)
+        maskKernel<<<blocks(n), kBlock, 0, s>>>(extra->kx, f.m, extra->xm, extra->rho, extra->std, extra->rhoMin, first, n,
+                                                ix.order, b.xs);
     SX_TRY_HIP(kWho, b.clock.mark(1, s));
     // ---- link
     LinkArgs la{b.xs, b.ys, b.zs, ix.keysSorted, ix.cellStart, b.parent, n, g, counters};
     linkKernel<<<blocks(n), kBlock, 0, s>>>(la);
     SX_TRY_HIP(kWho, b.clock.mark(2, s));
     // ---- compress, labels, counts
-    compressKernel<<<blocks(n), kBlock, 0, s>>>(b.parent, n, first, ix.order, id, b.root, minId, b.count, b.idKeys, b.mem);
-    labelKernel<<<blocks(n), kBlock, 0, s>>>(b.root, n, ix.order, minId, b.count, minMembers, b.label, b.selLabel,
-                                             b.selRoot, counters);
+    if (masked)
+    {
+        compressKernel<true><<<blocks(n), kBlock, 0, s>>>(b.parent, n, first, ix.order, b.xs, id, b.root, minId, b.count,
+                                                          b.idKeys, b.mem);
+        labelKernel<true><<<blocks(n), kBlock, 0, s>>>(b.root, n, ix.order, b.xs, minId, b.count, minMembers, b.label,
+                                                       b.selLabel, b.selRoot, counters);
+    }
+    else
+    {
+        compressKernel<false><<<blocks(n), kBlock, 0, s>>>(b.parent, n, first, ix.order, b.xs, id, b.root, minId, b.count,
+                                                           b.idKeys, b.mem);
+        labelKernel<false><<<blocks(n), kBlock, 0, s>>>(b.root, n, ix.order, b.xs, minId, b.count, minMembers, b.label,
+                                                        b.selLabel, b.selRoot, counters);
+    }
     SX_TRY_HIP(kWho, b.clock.mark(3, s));
     SX_TRY_HIP(kWho, hipGetLastError());
     SX_TRY_HIP(kWho, hipMemcpyAsync(b.countersHost, b.counters, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -433,6 +467,7 @@ int compute(Arena& arena, FofBuffers& b, const sx_fof& p, const sx_fields& f, co
     }
 
     // ---- catalogue
+    b.catGroups = Gc;
     if (Gc)
     {
         b.selLabelSorted = arena.get<uint64_t>("fof.selLabelSorted", n);
@@ -488,6 +523,7 @@ int compute(Arena& arena, FofBuffers& b, const sx_fof& p, const sx_fields& f, co
             ReduceArgs ra{b.memSorted, b.segStart, b.outCount, ix.order, b.xs, b.ys, b.zs, f.m, f.vx, f.vy, f.vz, first, Gc, g,
                           b.outReal};
             reduceKernel<<<Gc, kBlock, 0, s>>>(ra);
+            b.members = true;
             if (res.groupMass)
                 SX_TRY_HIP(kWho, hipMemcpyAsync(res.groupMass, b.outReal, (size_t)Gc * sizeof(double), kind, s));
             if (res.groupCom)

@@ -54,16 +54,31 @@ struct FofBuffers
     uint32_t* outCount{nullptr};
     double*   outReal{nullptr}; // [mass G | com 3 G | vel 3 G]
     uint64_t *counters{nullptr}, *countersHost{nullptr}; // pair tests, union retries, all groups, selected groups
+    uint32_t      catGroups{0};   // catalogue groups of the last call: entries of segStart, segCount, outCount, outReal
+    bool          members{false}; // the last call sorted the members and reduced them (memSorted, outReal)
     bool          done{false};
     StageClock<4> clock; // grid, link, compress and labels, catalogue
     uint64_t      stats[4]{};
+};
+
+/*! what the group properties (sx_halo.hip) ask of the search beyond sx_fof, which passes none.  A particle is selected
+ *  iff rhoMin <= 0 or its density (the rule of SX_PROF_RHO) is >= rhoMin; an unselected one gets a NaN sorted coordinate,
+ *  so every link test on it fails, and is kept out of the labels and counts.  members: sort the members and reduce the
+ *  catalogue whether or not res asks for mass, centre or velocity. */
+struct Extra
+{
+    double       rhoMin{0.0};
+    int          std{0};
+    const float *kx{nullptr}, *xm{nullptr}, *rho{nullptr}; // m is f.m
+    bool         members{false};
 };
 
 /*! all stages over [first, last) of f; the results go to the non-null arrays of res, device pointers (toHost false) or
  *  host pointers (true).  Synchronises after the compress stage (the number of groups sizes the catalogue's sorts) and
  *  at the end. */
 int compute(Arena& arena, FofBuffers& b, const sx_fof& p, const sx_fields& f, const sx_box& box, uint32_t first,
-            uint32_t last, const uint64_t* id, const sx_fof_result& res, bool toHost, hipStream_t s, std::string& err);
+            uint32_t last, const uint64_t* id, const sx_fof_result& res, bool toHost, hipStream_t s, std::string& err,
+            const Extra* extra = nullptr);
 //! the reason a call on [first, last) of f is refused, or empty: checkSpec, the columns, the range, the capacity
 std::string whyRefused(const sx_fof* p, const sx_box* box, const sx_fields* f, uint32_t first, uint32_t last,
                        const sx_fof_result* res);

@@ -989,6 +989,7 @@ extern "C"
         sx::pairbin::release(s->specBuf.bin);
         sx::profile::release(s->profBuf);
         sx::fof::release(s->fofBuf);
+        sx::halo::release(s->haloBuf);
         sx::twopoint::release(s->tpBuf);
         delete s;
     }

@@ -19,6 +19,7 @@
 #include "sx_hydro.hpp"
 #include "sx_map.hpp"
 #include "sx_profile.hpp"
+#include "sx_halo.hpp"
 #include "sx_fof.hpp"
 #include "sx_twopoint.hpp"
 #include "sx_spectrum.hpp"
@@ -280,6 +281,7 @@ struct sx_sim
     sx::spectrum::SpecBuffers specBuf; // sx_sim_spectrum: meshes, tables and pair scratch (in `work`, from the first call on)
     sx::profile::ProfBuffers profBuf; // sx_sim_profile: accumulators, edges, tables and the pinned result (in `work`, from the first call on)
     sx::fof::FofBuffers fofBuf; // sx_sim_fof: grid, union-find and catalogue scratch (in `work`, from the first call on)
+    sx::halo::HaloBuffers haloBuf; // sx_sim_halos: results and work items of the group properties (in `work`; the search: fofBuf)
     sx::twopoint::TwoPointBuffers tpBuf; // sx_sim_twopoint: grid, sorted columns and accumulators (in `work`, from the first call on)
     sx::turb::SimTurb* turb{nullptr}; // turbulence stirring (sx_sim_set_turbulence), VE propagator on one rank
 

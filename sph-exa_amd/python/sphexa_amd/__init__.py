@@ -467,6 +467,85 @@ def _fof_dict(arr, n, cap):
     return out
 
 
+HALO_FLAGS = {"moments": 1, "thermal": 2, "potential": 4}
+
+
+def halo_flags(names):
+    """the SX_HALO_* bits of an iterable of names ("moments", "thermal", "potential") or of an int"""
+    if isinstance(names, int):
+        return names
+    bits = 0
+    for k in names:
+        if k not in HALO_FLAGS:
+            raise ValueError(f"unknown group property {k!r}: one of {sorted(HALO_FLAGS)}")
+        bits |= HALO_FLAGS[k]
+    return bits
+
+
+class SxHalo(C.Structure):
+    """sx_halo: sx_fof's three, the density cut (rho_min <= 0: none; std: the rho column instead of kx m / xm), G, the
+    flags, muiConst and gamma of the thermal energy, and the largest group that still gets a potential (0: 2^20)"""
+    _fields_ = [("linking", C.c_double), ("minMembers", C.c_uint32), ("maxGroups", C.c_uint32), ("rhoMin", C.c_double),
+                ("std", C.c_int32), ("G", C.c_float), ("flags", C.c_uint32), ("muiConst", C.c_float),
+                ("gamma", C.c_double), ("maxPairMembers", C.c_uint32)]
+
+    def __init__(self, linking=0.0, min_members=20, max_groups=4096, rho_min=0.0, std=False, G=1.0,
+                 flags=("moments", "potential"), mui_const=10.0, gamma=5.0 / 3.0, max_pair_members=0):
+        super().__init__(float(linking), int(min_members), int(max_groups), float(rho_min), int(bool(std)), float(G),
+                         halo_flags(flags), float(mui_const), float(gamma), int(max_pair_members))
+
+
+class SxHaloResult(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("label", "groupLabel", "groupCount", "groupMass", "groupCom", "groupVel",
+                                          "numGroups", "groupSigma", "groupShape", "groupAngmom", "groupRmax",
+                                          "groupEint", "groupEpot")]
+
+
+def halo_check(spec, box):
+    """sx_halo_check: raises SxError with the reason for a specification a call would refuse.  Needs no GPU."""
+    if lib().sx_halo_check(C.byref(spec) if spec is not None else None, C.byref(box) if box is not None else None) != SX_OK:
+        raise SxError(lib().sx_last_error(None).decode())
+
+
+#: key of the dict -> (sx_halo_result member, trailing shape, flag)
+_HALO_EXTRA = {"sigma": ("groupSigma", (6,), 1), "shape": ("groupShape", (6,), 1), "angmom": ("groupAngmom", (3,), 1),
+               "rmax": ("groupRmax", (), 1), "eint": ("groupEint", (), 2), "epot": ("groupEpot", (), 4)}
+
+
+def _halo_arrays(n, cap, labels, flags):
+    """host arrays of a group-property call: those of _fof_arrays and, for the flags that are set, the properties
+    (filled with NaN: an entry the call does not write stays NaN)"""
+    out = _fof_arrays(n, cap, labels)
+    for key, (member, tail, bit) in _HALO_EXTRA.items():
+        if flags & bit:
+            out[key] = (np.full((max(1, cap),) + tail, np.nan), member)
+    return out
+
+
+def _halo_dict(arr, n, cap, flags):
+    """the dict Context.halos and Sim.halos return: _fof_dict's and the properties, then what follows from them: ekin =
+    0.5 M (sigma_xx + sigma_yy + sigma_zz), alpha_vir = 2 ekin / |epot|, bound = ekin + eint + epot < 0 (eint 0 without
+    the thermal flag), axes = the eigenvalues of shape, ascending"""
+    out = _fof_dict(arr, n, cap)
+    k = len(out["count"])
+    for key in _HALO_EXTRA:
+        out[key] = arr[key][0][:k] if key in arr else None
+    if flags & 1:
+        sg, sh = out["sigma"], out["shape"]
+        out["ekin"] = 0.5 * out["mass"] * (sg[:, 0] + sg[:, 3] + sg[:, 5])
+        full = sh[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(k, 3, 3)
+        out["axes"] = np.linalg.eigvalsh(full) if k else np.zeros((0, 3))
+    else:
+        out["ekin"] = out["axes"] = None
+    if flags & 1 and flags & 4:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["alpha_vir"] = 2.0 * out["ekin"] / np.abs(out["epot"])
+        out["bound"] = out["ekin"] + (out["eint"] if flags & 2 else 0.0) + out["epot"] < 0.0
+    else:
+        out["alpha_vir"] = out["bound"] = None
+    return out
+
+
 class SxTwoPoint(C.Structure):
     """sx_twopoint: the bin edges (kept alive here), the series flags, and the target rule key % stride == phase"""
     _fields_ = [("edges", C.c_void_p), ("nbins", C.c_uint32), ("series", C.c_uint32), ("stride", C.c_uint32),
@@ -809,6 +888,14 @@ def lib():
         "sx_fof_times": (C.c_int, [vp, C.POINTER(C.c_double)]),
         "sx_sim_fof": (C.c_int, [vp, C.POINTER(SxFof), C.POINTER(SxFofResult)]),
         "sx_sim_fof_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        "sx_halo_check": (C.c_int, [C.POINTER(SxHalo), C.POINTER(SxBox)]),
+        "sx_halo_compute": (C.c_int, [vp, C.POINTER(SxFields), C.POINTER(SxBox), u32, u32, vp, C.POINTER(SxHalo),
+                                      C.POINTER(SxHaloResult)]),
+        "sx_halo_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        "sx_set_halo_timing": (C.c_int, [vp, C.c_int]),
+        "sx_halo_times": (C.c_int, [vp, C.POINTER(C.c_double)]),
+        "sx_sim_halos": (C.c_int, [vp, C.POINTER(SxHalo), C.POINTER(SxHaloResult)]),
+        "sx_sim_halos_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         "sx_twopoint_check": (C.c_int, [C.POINTER(SxTwoPoint), C.POINTER(SxBox)]),
         "sx_twopoint_grid": (C.c_int, [C.POINTER(SxTwoPoint), C.POINTER(SxBox), C.c_uint64, C.POINTER(u32)]),
         "sx_twopoint_compute": (C.c_int, [vp, C.POINTER(SxFields), C.POINTER(SxBox), u32, u32, vp,
@@ -1330,6 +1417,46 @@ class Context:
         out = (C.c_double * 4)()
         self.check(self.L.sx_fof_times(self.h, out), "sx_fof_times")
         return {"grid_ms": out[0], "link_ms": out[1], "compress_ms": out[2], "catalogue_ms": out[3]}
+
+    # ---- group properties ----------------------------------------------------------------------------------------
+    def halos(self, fields, box, spec, id=None, first=0, last=None, labels=True):
+        """the friends-of-friends groups `spec` (an SxHalo) of the particles [first, last) of an SxFields behind the
+        density cut, and their properties (sx_halo_compute).  The dict of fof() -- an unselected particle's label is
+        2^64 - 1 -- and per catalogue entry sigma (k, 6), shape (k, 6) (xx xy xz yy yz zz), angmom (k, 3), rmax, eint,
+        epot (None where the flag is clear; epot NaN for a group over max_pair_members), and derived from them ekin,
+        alpha_vir, bound and axes (see _halo_dict)."""
+        last = fields.n if last is None else last
+        n, cap, flags = max(0, int(last) - int(first)), int(spec.maxGroups), int(spec.flags)
+        if id is not None and id.dtype != np.dtype(np.uint64):
+            raise TypeError("halos: id must be uint64")
+        host = _halo_arrays(n, cap, labels, flags)
+        dev = {k: self.upload(a.reshape(-1)) for k, (a, _) in host.items()}
+        res = SxHaloResult(**{host[k][1]: d.ptr for k, d in dev.items()})
+        try:
+            self.check(self.L.sx_halo_compute(self.h, C.byref(fields), C.byref(box), int(first), int(last),
+                                              id.ptr if id is not None else None, C.byref(spec), C.byref(res)),
+                       "sx_halo_compute")
+            got = {k: (dev[k].get().reshape(a.shape), m) for k, (a, m) in host.items()}
+            return _halo_dict(got, n, cap, flags)
+        finally:
+            for d in dev.values():
+                self.free(d)
+
+    def halo_stats(self):
+        """the last halos(): {pair terms evaluated, pair work items, groups with an epot, groups over the cap}"""
+        out = (C.c_uint64 * 4)()
+        self.check(self.L.sx_halo_stats(self.h, out), "sx_halo_stats")
+        return dict(zip(["pair_terms", "pair_items", "with_epot", "over_cap"], [int(v) for v in out]))
+
+    def set_halo_timing(self, on=True):
+        self.check(self.L.sx_set_halo_timing(self.h, 1 if on else 0), "sx_set_halo_timing")
+
+    def halo_times(self):
+        """{group search, moments, pair kernel, combination and copies} in ms of the last halos() of the context or of
+        a Sim on it (after set_halo_timing)"""
+        out = (C.c_double * 4)()
+        self.check(self.L.sx_halo_times(self.h, out), "sx_halo_times")
+        return {"search_ms": out[0], "moments_ms": out[1], "pairs_ms": out[2], "combine_ms": out[3]}
 
     # ---- two-point statistics -----------------------------------------------------------------------------------
     def twopoint(self, fields, box, spec, id=None, first=0, last=None):
@@ -1979,6 +2106,35 @@ class Sim:
         out = (C.c_uint64 * 4)()
         self.ctx.check(self.L.sx_sim_fof_stats(self.h, out), "sx_sim_fof_stats")
         return dict(zip(["pair_tests", "union_retries", "num_all", "num_groups"], [int(v) for v in out]))
+
+    def halos_spec(self, linking=0.2, length=None, min_members=20, max_groups=4096, rho_min=0.0,
+                   flags=("moments", "potential"), max_pair_members=0):
+        """the SxHalo of halos(): the linking length as in fof_spec; G, muiConst, gamma and the density rule are the
+        sim's (sx_sim_halos reads them from its parameters)"""
+        length = self.fof_spec(linking, length).linking
+        p = self.params
+        return SxHalo(length, min_members, max_groups, rho_min, p.propagator == 1, p.g, flags, p.muiConst, p.gamma,
+                      max_pair_members)
+
+    def halos(self, linking=0.2, length=None, min_members=20, max_groups=4096, rho_min=0.0,
+              flags=("moments", "potential"), max_pair_members=0, labels=False, spec=None):
+        """the friends-of-friends groups of the current state among the particles with a density of rho_min or more
+        (rho_min <= 0: all), and their properties (sx_sim_halos; one rank): the dict of Context.halos.  flags: any of
+        "moments", "thermal", "potential".  The gravity-only propagator serves without a cut and without "thermal".
+        Changes no state."""
+        spec = spec if spec is not None else self.halos_spec(linking, length, min_members, max_groups, rho_min, flags,
+                                                             max_pair_members)
+        n, cap, bits = self.size(), int(spec.maxGroups), int(spec.flags)
+        arr = _halo_arrays(n, cap, labels, bits)
+        res = SxHaloResult(**{m: a.ctypes.data for a, m in arr.values()})
+        self.ctx.check(self.L.sx_sim_halos(self.h, C.byref(spec), C.byref(res)), "sx_sim_halos")
+        return _halo_dict(arr, n, cap, bits)
+
+    def halos_stats(self):
+        """the last halos(): {pair terms evaluated, pair work items, groups with an epot, groups over the cap}"""
+        out = (C.c_uint64 * 4)()
+        self.ctx.check(self.L.sx_sim_halos_stats(self.h, out), "sx_sim_halos_stats")
+        return dict(zip(["pair_terms", "pair_items", "with_epot", "over_cap"], [int(v) for v in out]))
 
     def twopoint_spec(self, edges, series=("count", "vel"), stride=1, phase=0, mass=False):
         """the SxTwoPoint of twopoint(): absolute bin edges, the series ("count", "vel", "mass" or single names), and
