@@ -45,6 +45,8 @@
  *   sx_gravity_direct      ryoanji::directSum                   ryoanji/interface/multipole_holder.cuh:72-74, nbody/direct.cuh:52-123
  *                                                               (CPU form: nbody/traversal_cpu.hpp:234-270)
  *   sx_sim_set_turbulence  TurbVeProp::computeForces            main/src/propagator/turb_ve.hpp:114-119
+ *   sx_cool, sx_sim_set_cooling  the energy sink of HydroGrackleProp, main/src/propagator/std_hydro_grackle.hpp:155-226, as an
+ *                                                               exact integration of a tabulated cooling function on the device
  *   sx_observables         sphexa::gpuGrowthRate, machSquareSumGpu, survivorsGpu  main/src/observables/gpu_reductions.cu:69-168;
  *                                                               d2QuadpoleMomentum grav_waves_calculations.hpp:87-121
  *   sx_sim_observe         IObservables::computeAndWrite        main/src/observables/factory.hpp:46-69
@@ -1370,6 +1372,64 @@ int sx_sim_set_turbulence_state(sx_sim* sim, const double scalars[4], uint64_t n
 /*! device time (ms, HIP events) of the last step's {noise advance, stirring kernel}; both are part of the
  *  UpdateQuantities stage of sx_sim_stage_times */
 int sx_sim_turbulence_times(sx_sim* sim, float out[2]);
+
+/* ---- optically thin radiative cooling (no line-by-line counterpart: the reference's std-cooling propagator,
+ * main/src/propagator/std_hydro_grackle.hpp:155-226, drives GRACKLE on the host; its time-step criterion ct_crit is
+ * physics/cooling/include/cooling/cooler.hpp:103, cooler.cpp:79-83) ----
+ * A tabulated cooling function in code units, integrated exactly over the step for every particle (Townsend 2009,
+ * ApJS 181, 391) on the device.  Model: dT/dt = -rho L(T) / cv at the rho of the step, L(T) = L_k (T / T_k)^alpha_k on
+ * [T_k, T_k+1]; the last segment's law continues above T_N; below T_1, the temperature floor, L = 0.  T is the sim's
+ * temp column (u / cv), so du/dt = -rho L. */
+#define SX_COOLING_MAX_NODES 256
+typedef struct sx_cooling sx_cooling;
+
+/*! host only, needs no GPU.  n nodes T_1 < ... < T_n, 2 <= n <= SX_COOLING_MAX_NODES, with values lambda_k > 0.
+ *  Builds, in double, alpha_k = ln(lambda_k+1 / lambda_k) / ln(T_k+1 / T_k) and Townsend's temporal evolution function
+ *  Y_k = (lambda_n / T_n) int_{T_k}^{T_n} dT / L(T): dimensionless, Y_n = 0, growing as T falls.  SX_ERR_ARG for n out of
+ *  range, T not strictly increasing, an entry that is not finite or not positive, and a table whose Y does not come
+ *  out finite and strictly decreasing in k (exponents or ratios beyond double). */
+int      sx_cooling_create(sx_cooling** out, const double* T, const double* lambda, uint32_t n);
+void     sx_cooling_destroy(sx_cooling* c);
+uint32_t sx_cooling_num_nodes(const sx_cooling* c);
+/*! the table: n entries each, every pointer nullable; alpha[n - 1] repeats alpha[n - 2], the law above T_n */
+int      sx_cooling_get_table(const sx_cooling* c, double* T, double* lambda, double* alpha, double* Y);
+/*! the arithmetic of the kernels on the host, operation by operation (libm's log, exp, log1p, expm1 in place of the
+ *  device's): L(T), and T after s = rho dt / cv */
+double   sx_cooling_rate_host(const sx_cooling* c, double T);
+double   sx_cooling_integrate_host(const sx_cooling* c, double T0, double s);
+/*! *minTc = min over i < n of cv temp_i / (rho_i L(temp_i)), +inf where L = 0 everywhere (and for n == 0).  rho, temp:
+ *  device arrays (float, double); minTc: host.  Synchronises. */
+int sx_cooling_time(sx_ctx* ctx, const sx_cooling* c, uint32_t n, const float* rho, const double* temp, double cv,
+                    double* minTc);
+/*! temp_i <- the exact solution after dt at rho_i, in place (device arrays; rho, m float, temp double).  stats (host):
+ *  {sum_i m_i cv (T_old - T_new), the energy radiated; particles that ended on the floor T_1; particles on or above
+ *  the floor before the call}.  The sum is taken in a fixed order (block partials in a buffer whose length depends on
+ *  n alone, folded by one block; no floating-point atomics): the same bits on every run of the same input.  Exact
+ *  whatever rounding does: T_new <= T_old; T_new >= T_1 where T_old >= T_1; a particle with T_old < T_1 is left
+ *  unchanged; dt == 0 leaves every bit unchanged.  Synchronises. */
+int sx_cool(sx_ctx* ctx, const sx_cooling* c, uint32_t n, const float* rho, const float* m, double* temp, double cv,
+            double dt, double stats[3]);
+/*! sx_set_cooling_timing(1): sx_cool and sx_cooling_time record HIP events round their kernels (the table is uploaded
+ *  only when it differs from the last call's and lies outside them).  sx_cooling_times: device ms of the kernels of the
+ *  last {sx_cool, sx_cooling_time}; zeros with the timing off. */
+int sx_set_cooling_timing(sx_ctx* ctx, int on);
+int sx_cooling_times(sx_ctx* ctx, double out[2]);
+/*! from now on every VE or std step of sim cools: an operator-split update of temp directly after the position and
+ *  energy update, with the rho of the step's force stage (VE: (kx m) / xm) and the step's minDt read on the device; du
+ *  and du_m1 stay purely hydrodynamic.  Before the step's time-step, ct_crit min_i t_cool,i of the locals joins the
+ *  rank's time-step candidates (ct_crit <= 0: no limiter).  The table is copied: c stays the caller's.  c NULL: off
+ *  again, and the sim steps as one that never cooled.  Any number of ranks.  SX_ERR_ARG (sx_last_error has the reason)
+ *  for the ve-bdt and gravity-only propagators. */
+int sx_sim_set_cooling(sx_sim* sim, const sx_cooling* c, double ct_crit);
+/*! this rank's {ct_crit min t_cool of the last step (+inf without the limiter), energy radiated in the last step,
+ *  energy radiated since sx_sim_set_state / sx_sim_init_sedov / sx_sim_set_cooling_radiated, particles on the floor
+ *  after the last step}; the caller sums over ranks.  Synchronises.  SX_ERR_ARG without sx_sim_set_cooling. */
+int sx_sim_cooling_stats(sx_sim* sim, double out[4]);
+/*! restart: the running total of the energy radiated */
+int sx_sim_set_cooling_radiated(sx_sim* sim, double erad);
+/*! device time (ms, HIP events; the step timer's own slots) of the last step's {cooling-time kernel, cooling kernel};
+ *  both are part of the UpdateQuantities stage of sx_sim_stage_times */
+int sx_sim_cooling_times(sx_sim* sim, float out[2]);
 
 #ifdef __cplusplus
 }

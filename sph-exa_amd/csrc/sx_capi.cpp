@@ -29,6 +29,8 @@
 #include "sx_tree.hpp"
 #include "sx_timestep.hpp"
 #include "sx_turb.hpp"
+#include "sx_cool.hpp"
+#include "sx_step_timer.hpp"
 
 using namespace sx;
 
@@ -135,6 +137,10 @@ struct sx_ctx
     sx::fof::FofBuffers fofBuf;          // grid, union-find and catalogue scratch and figures of the group finder
     sx::halo::HaloBuffers haloBuf;       // results, work items and figures of the group properties (the search: fofBuf)
     sx::twopoint::TwoPointBuffers tpBuf; // grid, sorted columns and accumulators of the two-point statistics
+    // sx_cool / sx_cooling_time: the table now on the device (uploaded again only when it changes) and the kernels'
+    // times of the last call of each (sx_set_cooling_timing)
+    std::vector<double> coolTable;
+    sx::StageClock<1>   coolClock, coolTimeClock;
     float2*     wh{nullptr};
     float2*     whd{nullptr};
     double      K{0};
@@ -308,6 +314,8 @@ extern "C"
         sx::fof::release(c->fofBuf);
         sx::halo::release(c->haloBuf);
         sx::twopoint::release(c->tpBuf);
+        c->coolClock.release();
+        c->coolTimeClock.release();
         c->arena.release();
         if (c->own) (void)hipStreamDestroy(c->own);
         delete c;
@@ -1178,6 +1186,83 @@ extern "C"
         SX_HIP(c, hipStreamSynchronize(c->stream));
         return stirHostTables(c, g, f, numModes, h.data(), h.data() + 3 * numModes, h.data() + 6 * numModes,
                               h.data() + 9 * numModes, solWeightNorm);
+    }
+
+    // ---- radiative cooling on caller-owned columns (sx_cool.hpp) ----------------------------------------------------
+
+    //! the table of t on the device (in the context's arena, uploaded on the stream)
+    static int coolingTable(sx_ctx* c, const sx_cooling* t, const char* fn, const double*& dev)
+    {
+        std::vector<double> p = sx::cool::packedTable(*t);
+        double* d = c->arena.get<double>("cool.table", 4 * sx::cool::kMaxNodes);
+        if (!d) return fail(c, SX_ERR_NOMEM, std::string(fn) + ": table");
+        dev = d;
+        if (p == c->coolTable) return SX_OK; // the table of the last call: already there
+        // p is a local: the copy is done with it before it becomes the record of what is on the device
+        c->coolTable.clear();
+        SX_HIP(c, hipMemcpyAsync(d, p.data(), p.size() * 8, hipMemcpyHostToDevice, c->stream));
+        SX_HIP(c, hipStreamSynchronize(c->stream));
+        c->coolTable = std::move(p);
+        return SX_OK;
+    }
+
+    int sx_set_cooling_timing(sx_ctx* c, int on)
+    {
+        if (!c) return SX_ERR_ARG;
+        c->coolClock.on = c->coolTimeClock.on = on != 0;
+        return SX_OK;
+    }
+
+    int sx_cooling_times(sx_ctx* c, double out[2])
+    {
+        if (!c || !out) return SX_ERR_ARG;
+        out[0] = c->coolClock.ms[0], out[1] = c->coolTimeClock.ms[0];
+        return SX_OK;
+    }
+
+    int sx_cooling_time(sx_ctx* c, const sx_cooling* t, uint32_t n, const float* rho, const double* temp, double cv,
+                        double* minTc)
+    {
+        if (!t || !minTc || (n && (!rho || !temp)) || !(cv > 0.0))
+            return fail(c, SX_ERR_ARG, "sx_cooling_time: bad arguments");
+        sx::cool::CoolTimeArgs a{};
+        if (int e = coolingTable(c, t, "sx_cooling_time", a.table)) return e;
+        a.n = n, a.d = {rho, nullptr, nullptr, nullptr}, a.temp = temp, a.cv = cv;
+        a.numNodes = (uint32_t)t->T.size();
+        a.minBits  = c->arena.get<unsigned long long>("cool.min", 1);
+        if (!a.minBits) return fail(c, SX_ERR_NOMEM, "sx_cooling_time: scratch");
+        SX_HIP(c, c->coolTimeClock.begin());
+        SX_HIP(c, c->coolTimeClock.mark(0, c->stream));
+        SX_HIP(c, sx::cool::coolingTimeLaunch(a, c->stream));
+        SX_HIP(c, c->coolTimeClock.mark(1, c->stream));
+        SX_HIP(c, hipMemcpyAsync(minTc, a.minBits, 8, hipMemcpyDeviceToHost, c->stream));
+        SX_HIP(c, hipStreamSynchronize(c->stream));
+        c->coolTimeClock.finish();
+        return SX_OK;
+    }
+
+    int sx_cool(sx_ctx* c, const sx_cooling* t, uint32_t n, const float* rho, const float* m, double* temp, double cv,
+                double dt, double stats[3])
+    {
+        if (!t || !stats || (n && (!rho || !m || !temp)) || !(cv > 0.0) || !(dt >= 0.0))
+            return fail(c, SX_ERR_ARG, "sx_cool: bad arguments");
+        sx::cool::CoolArgs a{};
+        if (int e = coolingTable(c, t, "sx_cool", a.table)) return e;
+        const uint32_t blocks = sx::cool::partialBlocks(n);
+        a.n = n, a.d = {rho, nullptr, nullptr, nullptr}, a.m = m, a.temp = temp, a.cv = cv, a.dt = dt;
+        a.numNodes = (uint32_t)t->T.size();
+        a.ePart    = c->arena.get<double>("cool.epart", blocks);
+        a.cPart    = c->arena.get<uint32_t>("cool.cpart", 2 * blocks);
+        a.stats    = c->arena.get<double>("cool.stats", 3);
+        if (!a.ePart || !a.cPart || !a.stats) return fail(c, SX_ERR_NOMEM, "sx_cool: scratch");
+        SX_HIP(c, c->coolClock.begin());
+        SX_HIP(c, c->coolClock.mark(0, c->stream));
+        SX_HIP(c, sx::cool::coolLaunch(a, c->stream));
+        SX_HIP(c, c->coolClock.mark(1, c->stream));
+        SX_HIP(c, hipMemcpyAsync(stats, a.stats, 3 * 8, hipMemcpyDeviceToHost, c->stream));
+        SX_HIP(c, hipStreamSynchronize(c->stream));
+        c->coolClock.finish();
+        return SX_OK;
     }
 
     int sx_max_divv(sx_ctx* c, uint32_t first, uint32_t last, const float* divv, float* out)

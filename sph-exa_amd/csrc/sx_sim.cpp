@@ -4,7 +4,7 @@
  *
  * Step = sync -> neighbor search with h-nc iteration -> XMass -> [halo xm] -> VeDefGradh -> EOS
  *        -> [halo v,prho,c,kx] -> IAD+divv/curlv -> [halo c_ij,divv] -> AV switches -> [halo alpha]
- *        -> momentum/energy -> global time-step min -> positions/energy -> h update.
+ *        -> momentum/energy -> [cooling time] -> global time-step min -> positions/energy -> [cooling] -> h update.
  *
  * This file: the sx_sim_* C API and the step, stepImpl, an orchestrator over named stages (searchStage, forcesStd /
  * forcesVe, gravityStage, integrateStage, finishStep).  The sync is sx_sim_domain.cpp, self-gravity
@@ -65,8 +65,9 @@ __global__ void dtCandidateKernel(Scalars* s, double Krho, double maxDtIncrease,
     double minDtAcc = INFINITY;
     if (g != 0.0) minDtAcc = etaAcc * sqrt(eps / sqrt(__longlong_as_double((long long)s->maxAccSqBits)));
     double m       = INFINITY;
-    double cand[4] = {minDtAcc, s->minDtCourant, s->minDtRho, maxDtIncrease * s->minDt};
-    for (int k = 0; k < 4; ++k)
+    // minDtCool: the cooling-time criterion of a sim that cools (sx_sim_set_cooling), INFINITY otherwise
+    double cand[5] = {minDtAcc, s->minDtCourant, s->minDtRho, maxDtIncrease * s->minDt, s->minDtCool};
+    for (int k = 0; k < 5; ++k)
         m = cand[k] < m ? cand[k] : m;
     s->dtCand = m;
 }
@@ -377,6 +378,62 @@ int turbStep(sx_sim* s, hipStream_t st)
         SIM_HIP(hipMemsetAsync(&s->sc->maxAccSqBits, 0, sizeof(unsigned long long), st));
         maxAccSq(s, st);
     }
+    return SX_OK;
+}
+
+// ---- radiative cooling (sx_cool.hpp) --------------------------------------------------------------------------------
+
+//! rho of the step's force stage: the std propagator's column, (kx m) / xm under VE
+sx::cool::Density coolDensity(const sx_sim* s)
+{
+    const size_t f = s->first;
+    if (s->p.propagator == 1) return {s->rho + f, nullptr, nullptr, nullptr};
+    return {nullptr, s->kx + f, s->xm + f, s->m + f};
+}
+
+/*! the cooling-time criterion (cooler.cpp:79-83: ct_crit times the shortest cooling time) of the locals' temp and this
+ *  step's rho into Scalars::minDtCool, where dtCandidateKernel reads it.  Without the limiter minDtCool stays INFINITY
+ *  (freshScalars, sx_sim_set_cooling) and nothing is launched */
+int coolTimeStage(sx_sim* s, hipStream_t st)
+{
+    const CoolState& C = s->cool;
+    if (!C.on || !(C.ctCrit > 0.0)) return SX_OK;
+    sx::cool::CoolTimeArgs a{};
+    a.n = (uint32_t)(s->last - s->first), a.d = coolDensity(s), a.temp = s->temp + s->first;
+    a.cv    = (double)idealGasCv(s->p.muiConst, s->p.gamma);
+    a.table = C.table, a.numNodes = C.numNodes, a.minBits = C.minBits;
+    SIM_HIP(s->timer.coolingBegin(Cooling::coolingTime, st));
+    SIM_HIP(sx::cool::coolingTimeLaunch(a, st));
+    SIM_HIP(sx::cool::scaledMin(C.minBits, C.ctCrit, &s->sc->minDtCool, st));
+    SIM_HIP(s->timer.coolingEnd(Cooling::coolingTime, st));
+    return SX_OK;
+}
+
+/*! the operator-split energy sink, directly after the position and energy update: temp of the locals over the step's
+ *  minDt (read on the device) at the rho of this step's force stage.  A deviation from the reference, which adds
+ *  (u_cooled - u) / dt to du (std_hydro_grackle.hpp:214-219) and lets the AB2 energy update extrapolate it: here du and
+ *  du_m1 stay purely hydrodynamic, gas at rest follows the exact cooling curve for any dt, and AB2 cannot carry a
+ *  strongly cooling particle below zero */
+int coolStage(sx_sim* s, hipStream_t st)
+{
+    const CoolState& C = s->cool;
+    if (!C.on) return SX_OK;
+    sx::cool::CoolArgs a{};
+    a.n = (uint32_t)(s->last - s->first), a.d = coolDensity(s), a.m = s->m + s->first, a.temp = s->temp + s->first;
+    a.cv    = (double)idealGasCv(s->p.muiConst, s->p.gamma);
+    a.dtPtr = &s->sc->minDt;
+    a.table = C.table, a.numNodes = C.numNodes;
+    a.ePart = C.ePart, a.cPart = C.cPart, a.stats = C.stats, a.total = C.stats + 3;
+    SIM_HIP(s->timer.coolingBegin(Cooling::cool, st));
+    SIM_HIP(sx::cool::coolLaunch(a, st));
+    SIM_HIP(s->timer.coolingEnd(Cooling::cool, st));
+    return SX_OK;
+}
+
+//! a new state (sx_sim_set_state, sx_sim_init_sedov): nothing radiated yet
+int coolResetStats(sx_sim* s, hipStream_t st)
+{
+    if (s->cool.stats) SIM_HIP(hipMemsetAsync(s->cool.stats, 0, 4 * sizeof(double), st));
     return SX_OK;
 }
 
@@ -799,6 +856,7 @@ int forcesVe(sx_sim* s, StepCtx& c, PairArgs pa)
 int integrateStage(sx_sim* s, StepCtx& c)
 {
     hipStream_t st = c.st;
+    if (int e = coolTimeStage(s, st)) return e;
     if (int e = globalTimestep(s, c.dist, st)) return e;
     PosArgs qa = posArgs((uint32_t)s->first, (uint32_t)s->last, simFields(s), s->dbox, s->p.muiConst, s->p.gamma);
     qa.dtPtr   = &s->sc->minDt;
@@ -810,6 +868,7 @@ int integrateStage(sx_sim* s, StepCtx& c)
     qa.keys    = (!c.dist && s->p.propagator != 2 && !reuseNext) ? s->keys : nullptr;
     if (c.skinOn && !skinParticleBuffers(s, qa, st)) return SX_ERR_NOMEM;
     c.H.positions(qa, st);
+    if (int e = coolStage(s, st)) return e;
     s->keysFresh = qa.keys != nullptr;
     c.H.updateH((uint32_t)s->first, (uint32_t)s->last, s->p.ng0, s->nc, s->h, c.powTab, st);
     SIM_HIP(s->timer.stageEnd(Stage::UpdateQuantities, st));
@@ -1136,6 +1195,7 @@ extern "C"
         s->bdt.started = false;
         const Scalars init = freshScalars();
         SIM_HIP(hipMemcpyAsync(s->sc, &init, sizeof(Scalars), hipMemcpyHostToDevice, st));
+        if (int e = coolResetStats(s, st)) return e;
         SIM_HIP(hipStreamSynchronize(st));
         return SX_OK;
     }
@@ -1179,6 +1239,8 @@ extern "C"
         s->bdt.started = false;
         const Scalars init = freshScalars(minDt, minDt_m1);
         SIM_HIP(hipMemcpy(s->sc, &init, sizeof(Scalars), hipMemcpyHostToDevice));
+        const double nothingRadiated[4] = {0.0, 0.0, 0.0, 0.0};
+        if (s->cool.stats) SIM_HIP(hipMemcpy(s->cool.stats, nothingRadiated, sizeof(nothingRadiated), hipMemcpyHostToDevice));
         return SX_OK;
     }
 
@@ -1539,6 +1601,97 @@ extern "C"
     {
         if (!s || !out || !s->turb) return SX_ERR_ARG;
         out[0] = s->turb->ms[0], out[1] = s->turb->ms[1];
+        return SX_OK;
+    }
+
+    // ---- radiative cooling ------------------------------------------------------------------------------------------
+
+    int sx_sim_set_cooling(sx_sim* s, const sx_cooling* c, double ctCrit)
+    {
+        if (!s) return SX_ERR_ARG;
+        const char* why = nullptr;
+        if (s->p.propagator == 3) why = "sx_sim_set_cooling: the gravity-only propagator does not cool (it keeps no "
+                                        "thermal field, nbody.hpp:74-77)";
+        else if (s->p.propagator == 2) why = "sx_sim_set_cooling: cooling with block time-steps (ve-bdt) is not "
+                                             "supported by sx_sim; sx_cool takes the columns of the active rungs";
+        if (why && c) // switching off is always accepted
+        {
+            sx_ctx_set_error_internal(s->ctx, why);
+            return SX_ERR_ARG;
+        }
+        hipStream_t st = (hipStream_t)sx_ctx_stream_internal(s->ctx);
+        CoolState&  C  = s->cool;
+        SIM_HIP(hipStreamSynchronize(st));
+        // without the limiter, and without cooling, the candidate is INFINITY: the step's time-step is what it was
+        const double inf = INFINITY;
+        SIM_HIP(hipMemcpy(&s->sc->minDtCool, &inf, sizeof(double), hipMemcpyHostToDevice));
+        if (!c)
+        {
+            C.on = false;
+            return SX_OK;
+        }
+        const std::vector<double> p = sx::cool::packedTable(*c);
+        C.table   = s->mem.get<double>("cool.table", 4 * sx::cool::kMaxNodes);
+        C.minBits = s->mem.get<unsigned long long>("cool.min", 1);
+        C.ePart   = s->mem.get<double>("cool.epart", sx::cool::partialBlocks((uint32_t)s->cap));
+        C.cPart   = s->mem.get<uint32_t>("cool.cpart", 2 * sx::cool::partialBlocks((uint32_t)s->cap));
+        const bool fresh = !C.stats;
+        C.stats          = s->mem.get<double>("cool.stats", 4);
+        if (!C.table || !C.minBits || !C.ePart || !C.cPart || !C.stats)
+        {
+            C.on = false;
+            return SX_ERR_NOMEM;
+        }
+        SIM_HIP(hipMemcpy(C.table, p.data(), p.size() * sizeof(double), hipMemcpyHostToDevice));
+        // a second table continues the first one's account of the energy radiated
+        const double nothingRadiated[4] = {0.0, 0.0, 0.0, 0.0};
+        if (fresh) SIM_HIP(hipMemcpy(C.stats, nothingRadiated, sizeof(nothingRadiated), hipMemcpyHostToDevice));
+        C.numNodes = (uint32_t)c->T.size();
+        C.ctCrit   = ctCrit;
+        C.on       = true;
+        return SX_OK;
+    }
+
+    int sx_sim_cooling_stats(sx_sim* s, double out[4])
+    {
+        if (!s || !out) return SX_ERR_ARG;
+        if (!s->cool.on)
+        {
+            sx_ctx_set_error_internal(s->ctx, "sx_sim_cooling_stats: sx_sim_set_cooling was not called");
+            return SX_ERR_ARG;
+        }
+        hipStream_t st = (hipStream_t)sx_ctx_stream_internal(s->ctx);
+        double      h[4];
+        SIM_HIP(hipMemcpyAsync(h, s->cool.stats, sizeof(h), hipMemcpyDeviceToHost, st));
+        SIM_HIP(hipMemcpyAsync(out, &s->sc->minDtCool, sizeof(double), hipMemcpyDeviceToHost, st));
+        SIM_HIP(hipStreamSynchronize(st));
+        out[1] = h[0], out[2] = h[3], out[3] = h[1];
+        return SX_OK;
+    }
+
+    int sx_sim_set_cooling_radiated(sx_sim* s, double erad)
+    {
+        if (!s || !std::isfinite(erad)) return SX_ERR_ARG;
+        if (!s->cool.on)
+        {
+            sx_ctx_set_error_internal(s->ctx, "sx_sim_set_cooling_radiated: sx_sim_set_cooling was not called");
+            return SX_ERR_ARG;
+        }
+        hipStream_t st = (hipStream_t)sx_ctx_stream_internal(s->ctx);
+        SIM_HIP(hipStreamSynchronize(st));
+        SIM_HIP(hipMemcpy(s->cool.stats + 3, &erad, sizeof(double), hipMemcpyHostToDevice));
+        return SX_OK;
+    }
+
+    int sx_sim_cooling_times(sx_sim* s, float out[2])
+    {
+        if (!s || !out) return SX_ERR_ARG;
+        if (!s->cool.on)
+        {
+            sx_ctx_set_error_internal(s->ctx, "sx_sim_cooling_times: sx_sim_set_cooling was not called");
+            return SX_ERR_ARG;
+        }
+        out[0] = s->timer.coolingMs[(int)Cooling::coolingTime], out[1] = s->timer.coolingMs[(int)Cooling::cool];
         return SX_OK;
     }
 

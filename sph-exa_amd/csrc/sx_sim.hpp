@@ -44,6 +44,7 @@ struct Scalars
     double   egrav;    // gravitational potential energy (ParticlesData::egrav)
     unsigned long long maxAccSqBits; // max |a|^2 of the locals (bit image of a non-negative double)
     unsigned gravErr;
+    double   minDtCool; // ct_crit min t_cool of the locals (sx_sim_set_cooling); INFINITY without the limiter
 };
 
 //! the scalars of a state that has not stepped: the time-steps given, ttot 0, the step's accumulators at their start
@@ -51,7 +52,8 @@ struct Scalars
 inline Scalars freshScalars(double minDt = 1e-6, double minDt_m1 = 1e-6)
 {
     return Scalars{.minDt = minDt, .minDt_m1 = minDt_m1, .ttot = 0.0, .minDtCourant = INFINITY, .minDtRho = INFINITY,
-                   .dtCand = 0.0, .courant = 1e10f, .maxDivvU = 0u, .egrav = 0.0, .maxAccSqBits = 0ull, .gravErr = 0u};
+                   .dtCand = 0.0, .courant = 1e10f, .maxDivvU = 0u, .egrav = 0.0, .maxAccSqBits = 0ull, .gravErr = 0u,
+                   .minDtCool = INFINITY};
 }
 
 //! the conserved fields that travel with a particle in the SFC exchange (rung: ve-bdt only, else nullptr)
@@ -150,6 +152,19 @@ struct SkinBuffers
     // skinReserveDrift: several ranks -- the drift bounds of coverListKernel and the locals' positions at the build
     double *drift{nullptr}, *relg{nullptr}, *x0{nullptr}, *y0{nullptr}, *z0{nullptr};
     float* h0{nullptr}; // h before a reuse step's filter (searchStage)
+};
+
+//! radiative cooling of the step (sx_sim_set_cooling; sx_cool.hpp): the sim's copy of the table and the kernels' scratch
+struct CoolState
+{
+    bool                on{false};
+    double              ctCrit{0.0};      // <= 0: no time-step limiter
+    uint32_t            numNodes{0};
+    double*             table{nullptr};   // [T | lambda | alpha | Y], numNodes each
+    unsigned long long* minBits{nullptr}; // the cooling-time kernel's minimum
+    double*             ePart{nullptr};   // block partials of the energy radiated
+    uint32_t*           cPart{nullptr};
+    double*             stats{nullptr};   // {energy radiated in the last step, on the floor, cooled, running total}
 };
 
 struct ReqBox; // sx_sim_internal.hpp
@@ -284,6 +299,7 @@ struct sx_sim
     sx::halo::HaloBuffers haloBuf; // sx_sim_halos: results and work items of the group properties (in `work`; the search: fofBuf)
     sx::twopoint::TwoPointBuffers tpBuf; // sx_sim_twopoint: grid, sorted columns and accumulators (in `work`, from the first call on)
     sx::turb::SimTurb* turb{nullptr}; // turbulence stirring (sx_sim_set_turbulence), VE propagator on one rank
+    sx::sim::CoolState cool;          // radiative cooling (sx_sim_set_cooling), VE and std propagators
 
     // the observable of sx_sim_observe (observablesFactory, main/src/observables/factory.hpp:46-69)
     int             obsKind{0};

@@ -23,6 +23,7 @@
 #include "../../include/sphexa_hip.h"
 #include "sx_args.hpp"
 #include "sx_comm.hpp"
+#include "sx_cool.hpp"
 #include "sx_gravity.hpp"
 #include "sx_hydro.hpp"
 #include "sx_nbody.hpp"

@@ -29,11 +29,15 @@ inline constexpr const char* kStageNames[kNumStages]   = {"sync",         "FindN
                                                           "Gravity",      "UpdateQuantities"};
 inline constexpr const char* kKernelNames[kNumKernels] = {"findNeighbors", "xmass",          "veDefGradh", "iadDivvCurlv",
                                                           "avSwitches",    "momentumEnergy", "gravity",    "nbodyIntegrate"};
+// the kernels of the radiative cooling (sx_cool.hpp), marked by a sim that cools: slots of their own, read through
+// sx_sim_cooling_times, so that the names and positions above stay what consumers index by
+enum class Cooling : int { coolingTime, cool, count };
+constexpr int kNumCooling = (int)Cooling::count;
 
 class StepTimer
 {
 public:
-    float stageMs[kNumStages]{}, kernelMs[kNumKernels]{};
+    float stageMs[kNumStages]{}, kernelMs[kNumKernels]{}, coolingMs[kNumCooling]{};
 
     StepTimer() { forEachEvent([](hipEvent_t& e) { (void)hipEventCreate(&e); }); }
     ~StepTimer() { forEachEvent([](hipEvent_t& e) { if (e) (void)hipEventDestroy(e); }); }
@@ -46,6 +50,8 @@ public:
         for (auto& f : stageFrom_)
             f = nullptr;
         for (auto& k : kernelState_)
+            k = kIdle;
+        for (auto& k : coolingState_)
             k = kIdle;
         last_ = start_;
         return hipEventRecord(start_, st);
@@ -72,6 +78,18 @@ public:
         return hipEventRecord(kernel_[(int)k][1], st);
     }
 
+    hipError_t coolingBegin(Cooling k, hipStream_t st)
+    {
+        coolingState_[(int)k] = kBegun;
+        return hipEventRecord(cooling_[(int)k][0], st);
+    }
+
+    hipError_t coolingEnd(Cooling k, hipStream_t st)
+    {
+        coolingState_[(int)k] = coolingState_[(int)k] == kBegun ? kDone : kIdle;
+        return hipEventRecord(cooling_[(int)k][1], st);
+    }
+
     //! after the stream's synchronisation: the times of what this step marked, 0.0 for the rest
     void collect()
     {
@@ -79,6 +97,8 @@ public:
             stageMs[g] = stageFrom_[g] ? elapsed(stageFrom_[g], stageEnd_[g]) : 0.f;
         for (int k = 0; k < kNumKernels; ++k)
             kernelMs[k] = kernelState_[k] == kDone ? elapsed(kernel_[k][0], kernel_[k][1]) : 0.f;
+        for (int k = 0; k < kNumCooling; ++k)
+            coolingMs[k] = coolingState_[k] == kDone ? elapsed(cooling_[k][0], cooling_[k][1]) : 0.f;
     }
 
 private:
@@ -98,12 +118,14 @@ private:
             fn(e);
         for (auto& pair : kernel_)
             fn(pair[0]), fn(pair[1]);
+        for (auto& pair : cooling_)
+            fn(pair[0]), fn(pair[1]);
     }
 
-    hipEvent_t    start_{nullptr}, stageEnd_[kNumStages]{}, kernel_[kNumKernels][2]{};
+    hipEvent_t    start_{nullptr}, stageEnd_[kNumStages]{}, kernel_[kNumKernels][2]{}, cooling_[kNumCooling][2]{};
     hipEvent_t    last_{nullptr};           // the last boundary recorded in this step
     hipEvent_t    stageFrom_[kNumStages]{}; // where each stage marked in this step began; nullptr: not marked
-    unsigned char kernelState_[kNumKernels]{};
+    unsigned char kernelState_[kNumKernels]{}, coolingState_[kNumCooling]{};
 };
 
 } // namespace sx::sim

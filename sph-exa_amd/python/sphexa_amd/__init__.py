@@ -909,6 +909,20 @@ def lib():
         "sx_twopoint_from_fixed": (C.c_int, [vp, i32, C.POINTER(C.c_double)]),
         "sx_sim_twopoint": (C.c_int, [vp, C.POINTER(SxTwoPoint), C.POINTER(SxTwoPointResult)]),
         "sx_sim_twopoint_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        "sx_cooling_create": (C.c_int, [C.POINTER(vp), vp, vp, u32]),
+        "sx_cooling_destroy": (None, [vp]),
+        "sx_cooling_num_nodes": (u32, [vp]),
+        "sx_cooling_get_table": (C.c_int, [vp, vp, vp, vp, vp]),
+        "sx_cooling_rate_host": (C.c_double, [vp, C.c_double]),
+        "sx_cooling_integrate_host": (C.c_double, [vp, C.c_double, C.c_double]),
+        "sx_cooling_time": (C.c_int, [vp, vp, u32, vp, vp, C.c_double, C.POINTER(C.c_double)]),
+        "sx_cool": (C.c_int, [vp, vp, u32, vp, vp, vp, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+        "sx_set_cooling_timing": (C.c_int, [vp, C.c_int]),
+        "sx_cooling_times": (C.c_int, [vp, C.POINTER(C.c_double)]),
+        "sx_sim_set_cooling": (C.c_int, [vp, vp, C.c_double]),
+        "sx_sim_cooling_stats": (C.c_int, [vp, C.POINTER(C.c_double)]),
+        "sx_sim_set_cooling_radiated": (C.c_int, [vp, C.c_double]),
+        "sx_sim_cooling_times": (C.c_int, [vp, C.POINTER(C.c_float)]),
     }
     for name, (res, args) in sig.items():
         # a measurement build named by SPHEXA_AMD_LIB (an A/B against an older library) may predate an entry
@@ -1001,6 +1015,10 @@ class SxError(RuntimeError):
 TURBULENCE_ATTRIBUTES = ["turbulence::variance", "turbulence::decayTime", "turbulence::solWeight",
                          "turbulence::solWeightNorm", "turbulence::numModes", "turbulence::modes",
                          "turbulence::amplitudes", "turbulence::phases", "rngEngineState"]
+
+
+#: what a checkpoint of a cooling Sim adds: the table's nodes and values, the limiter, this rank's energy radiated
+COOLING_ATTRIBUTES = ["cooling::T", "cooling::lambda", "cooling::ct_crit", "cooling::erad"]
 
 
 class Turbulence:
@@ -1661,6 +1679,8 @@ class Sim:
         self.iteration = 0  # completed steps (the reference's "iteration" attribute)
         self.stirred = False  # set_turbulence was called: checkpoints carry the turbulence state
         self.last_sum1 = None  # sum1 of the last render() with a field (the numerator of its mean); None without one
+        self.cooling = None  # the table of set_cooling (checkpoints carry it, ct_crit and the energy radiated)
+        self.ct_crit = 0.0
         self.h = C.c_void_p()
         ctx.check(self.L.sx_sim_create(C.byref(self.h), ctx.h, int(capacity), C.byref(self.params), C.byref(box),
                                        bucket), "sx_sim_create")
@@ -1701,6 +1721,30 @@ class Sim:
         out = (C.c_float * 2)()
         self.ctx.check(self.L.sx_sim_turbulence_times(self.h, out), "turbulence_times")
         return dict(noise=out[0], stirring=out[1])
+
+    def set_cooling(self, cooling, ct_crit=0.1):
+        """every following step cools (sx_sim_set_cooling; VE and std propagators, any number of ranks): an exact,
+        operator-split update of temp after the position update, and ct_crit times the shortest cooling time among the
+        time-step candidates (ct_crit <= 0: no limiter).  cooling: a cooling.Cooling, whose table is copied; None: off
+        again"""
+        self.ctx.check(self.L.sx_sim_set_cooling(self.h, cooling.h if cooling is not None else None, float(ct_crit)),
+                       "set_cooling")
+        self.cooling = cooling.table() if cooling is not None else None
+        self.ct_crit = float(ct_crit)
+
+    def cooling_stats(self):
+        """this rank's figures of the cooling (sx_sim_cooling_stats): minDtCool (ct_crit min t_cool of the last step,
+        inf without the limiter), radiated (energy, last step), radiated_total (since set_state or load_checkpoint),
+        on_floor (particles at the floor temperature after the last step); sum over the ranks yourself"""
+        out = (C.c_double * 4)()
+        self.ctx.check(self.L.sx_sim_cooling_stats(self.h, out), "cooling_stats")
+        return dict(minDtCool=out[0], radiated=out[1], radiated_total=out[2], on_floor=int(out[3]))
+
+    def cooling_times(self):
+        """device ms of the last step's cooling-time kernel and cooling kernel (sx_sim_cooling_times)"""
+        out = (C.c_float * 2)()
+        self.ctx.check(self.L.sx_sim_cooling_times(self.h, out), "cooling_times")
+        return dict(coolingTime=out[0], cool=out[1])
 
     def set_overlap(self, on):
         self.ctx.check(self.L.sx_sim_set_overlap(self.h, int(bool(on))), "set_overlap")
@@ -1780,6 +1824,11 @@ class Sim:
             attrs["ts::dt_m1"] = np.array(ts["dt_m1"], dtype=np.float32)
         if self.stirred:  # TurbVeProp::save (turb_ve.hpp:121): TurbulenceData::loadOrStore
             attrs.update(self.turbulence_state())
+        if self.cooling is not None:  # the table, the limiter and this rank's account of the energy radiated
+            attrs["cooling::T"] = self.cooling["T"]
+            attrs["cooling::lambda"] = self.cooling["lam"]
+            attrs["cooling::ct_crit"] = np.float64(self.ct_crit)
+            attrs["cooling::erad"] = np.float64(self.cooling_stats()["radiated_total"])
         if str(path).endswith(".h5"):
             from . import h5part
 
@@ -1812,6 +1861,7 @@ class Sim:
             types.update({"ts::numRungs": np.int32, "ts::dt_m1": np.float32, "ttot": np.float64})
             types.update({k: np.float64 for k in TURBULENCE_ATTRIBUTES})
             types.update({"turbulence::numModes": np.uint64, "rngEngineState": np.uint8})
+            types.update({k: np.float64 for k in COOLING_ATTRIBUTES})
             _, attrs = h5part.read_step(path, {}, {k: t for k, t in types.items() if k in present}, step)
             return {**fields, **attrs}
         with np.load(path, allow_pickle=False) as d:
@@ -1851,6 +1901,21 @@ class Sim:
             # TurbVeProp::load (turb_ve.hpp:123-135); a file without the attributes keeps the state of set_turbulence,
             # as the reference's optional attributes do
             self.set_turbulence_state(d)
+        if "cooling::T" in d:
+            if self.cooling is None:
+                raise ValueError("restart file carries a cooling table (cooling::*) but this Sim does not cool: call "
+                                 "set_cooling before load_checkpoint")
+            # the table and ct_crit are parameters of this Sim (set_cooling), as PARAM_ATTRIBUTES are: the energy radiated
+            # under one curve does not continue under another
+            same = (np.array_equal(np.atleast_1d(d["cooling::T"]), self.cooling["T"]) and
+                    np.array_equal(np.atleast_1d(d["cooling::lambda"]), self.cooling["lam"]) and
+                    float(np.asarray(d["cooling::ct_crit"]).ravel()[0]) == self.ct_crit)
+            if not same:
+                raise ValueError("restart file's cooling table or ct_crit (cooling::T, cooling::lambda, "
+                                 "cooling::ct_crit) differ from those of this Sim's set_cooling")
+            # the running total of the energy radiated continues
+            self.ctx.check(self.L.sx_sim_set_cooling_radiated(self.h, float(np.asarray(d["cooling::erad"]).ravel()[0])),
+                           "set_cooling_radiated")
         self.iteration = int(d["iteration"]) if "iteration" in d else 0
         t = float(d["time"] if "time" in d else d["ttot"])
         self.ctx.check(self.L.sx_sim_set_time(self.h, t), "set_time")
